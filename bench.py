@@ -18,13 +18,20 @@ assembly of nzval on one rank ("a single RCCL gather over xGMI", fd_comm_gatherv
 after the timed region and reported next to it (`gather`, `value_with_gather`); `--gather-in-step` puts it inside the
 timed step instead.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line on stdout (schema in the task contract) with `roofline` (fused diff+decompress kernel: HBM
-bytes actually moved / HIP-event time on the launch stream) and `cpu_baseline` (the CPU restatement of the reference
-path on this host, 1 core -- plus an all-cores OpenMP variant as an upper bound).  Every rank prints one diagnostic
-JSON line on stderr (device, RCCL library / version, per-stage times).
+Rank 0 prints ONE JSON line on stdout (schema in the task contract).  A plain run sets up, warms up, times the K steps
+(no events inside them) and prints the headline fields only (metric, value, unit, ms_per_step, dtype, config ...).
+With --full the timed steps carry HIP events around the graded kernel (every 4th step) and the line also holds
+`roofline` (fused diff+decompress kernel: HBM bytes actually moved / HIP-event time on the launch stream), the medians,
+the side runs, `result_check` and `cpu_baseline` (the CPU restatement of the reference path on this host, 1 core -- plus
+an all-cores OpenMP variant as an upper bound); every rank then prints one diagnostic JSON line on stderr (device, RCCL
+library / version, per-stage times), and a failed result check exits non-zero.
+
+--dump-outputs DIR writes what the timed steps computed in the last one (nzval, in the element type of the run) as
+DIR/nzval.npy; an nzval above 64 MB is written as the entries at a fixed sample of positions (the first and last 4096
+plus 2^21 drawn with numpy PCG64 seed 0, sorted, duplicates dropped) -- the same positions for the same arguments.
 """
 import argparse
 import json
@@ -100,13 +107,48 @@ def parse():
     ap.add_argument("--sweep", default="", metavar="DIR",
                     help="after the headline line, run the other BASELINE configs (c2, c3, c5; plus c4 in Float32) as child "
                          "processes and write their JSON lines to DIR/bench_<config>.json (single GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: kernel events, medians, roofline / live PMC, side runs, consumer solve, "
+                         "result checks, CPU baseline, soak (--sides / --sweep imply it); without it only the timed steps run")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the nzval of the last one to DIR/nzval.npy (N>1: DIR/nzval_rank<r>.npy); above "
+                         "64 MB a fixed, seeded sample of its entries")
     args = ap.parse_args()
     if args.sweep:
         args.sides = True
+    if args.sides:
+        args.full = True
     explicit = any(a.split("=")[0] in ("--weak", "--x-layout", "--eps", "--small-messages", "--shard", "--gather-in-step") for a in sys.argv[1:])
     if explicit or args.config not in ("c2", "c4"):
         args.variant = "flags"
     return args
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_EDGE = 4096
+DUMP_SAMPLE = 1 << 21
+
+
+def dump_outputs(dirname, name, t):
+    """Write the 1-D device tensor `t` to dirname/name.npy: whole when it fits in DUMP_MAX_BYTES, else its entries at a fixed set of
+    positions (both ends + DUMP_SAMPLE seeded draws) -- the same positions for the same length, so two builds compare entry by entry."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    n = t.numel()
+    if n * t.element_size() > DUMP_MAX_BYTES:
+        pos = np.unique(np.concatenate([np.arange(DUMP_EDGE), np.arange(n - DUMP_EDGE, n),
+                                        np.random.default_rng(0).integers(0, n, DUMP_SAMPLE)]))
+        t = t[torch.as_tensor(pos, device=t.device)]
+    np.save(os.path.join(dirname, name + ".npy"), t.cpu().numpy())
+
+
+def emit_line(line, json_fd=None):
+    """The ONE result line: stdout, or the saved descriptor when fd 1 points at stderr (N>1)."""
+    if json_fd is not None:
+        os.write(json_fd, line.encode())
+    else:
+        sys.stdout.write(line)
+        sys.stdout.flush()
 
 
 def emit_failure(args, what, json_fd=None):
@@ -115,11 +157,7 @@ def emit_failure(args, what, json_fd=None):
                        "value": None, "unit": "columns/s", "n_gpus": args.gpus, "steps": args.steps, "warmup": args.warmup, "ms_per_step": None,
                        "higher_is_better": True, "scaling": "weak" if args.weak else "strong", "vs_baseline": None, "dtype": args.dtype,
                        "data": "synthetic", "config": {"workload": "not measured", "name": args.config}, "error": what, "comm_error": what}) + "\n"
-    if json_fd is not None:
-        os.write(json_fd, line.encode())
-    else:
-        sys.stdout.write(line)
-        sys.stdout.flush()
+    emit_line(line, json_fd)
 
 
 def self_spawn(args):
@@ -240,7 +278,7 @@ def live_pmc(cfg, dtype, kernel_like, timeout_s=150.0):
     with tempfile.TemporaryDirectory(prefix="fdjac_pmc_", dir="/tmp") as tmp:
         env = dict(os.environ, FDJAC_BENCH_PMC_CHILD="1", TMPDIR="/tmp")
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", cfg, "--dtype", dtype, "--steps", "5", "--warmup", "2",
-               "--no-cpu-baseline", "--soak-seconds", "0", "--no-plain-handover"]
+               "--full", "--no-cpu-baseline", "--soak-seconds", "0", "--no-plain-handover"]
         for counter in ("FETCH_SIZE", "WRITE_SIZE"):
             d = os.path.join(tmp, counter)
             try:
@@ -698,18 +736,78 @@ def main():
         if gather_in_step:
             do_gather()
 
+    def release():
+        """N>1: every rank leaves together, releasing in dependency order: plans, then the communicator, then torch's group."""
+        nonlocal enqueue, plan
+        if world > 1:
+            dist.barrier()
+            torch.cuda.synchronize()
+            del enqueue, plan
+            if comm is not None:
+                comm._fin()
+            dist.destroy_process_group()
+
     for _ in range(args.warmup):
         step()
     fence()
-    # HIP events around the graded kernel, on the launch stream, on every 4th timed step (the 1st, 5th, ...): a pair of events costs ~8 us
-    # of stream time per call (scripts/ubench/ext_launch_probe.hip) -- on every step it was 7 % of the headline step, 40 % of c2's
-    plan.enable_timing(1)
-    plan.set_timing_stride(4 if args.steps >= 8 else 1)
+    if args.full:
+        # HIP events around the graded kernel, on the launch stream, on every 4th timed step (the 1st, 5th, ...): a pair of events costs ~8 us
+        # of stream time per call (scripts/ubench/ext_launch_probe.hip) -- on every step it was 7 % of the headline step, 40 % of c2's
+        plan.enable_timing(1)
+        plan.set_timing_stride(4 if args.steps >= 8 else 1)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "nzval" if world == 1 else "nzval_rank%d" % rank, out)
+    t_max = torch.tensor([elapsed], dtype=torch.float64, device=dev)
+    if world > 1:
+        dist.all_reduce(t_max, op=dist.ReduceOp.MAX)
+    elapsed = float(t_max.item())
+    ms_step = elapsed / args.steps * 1e3
+    eps_desc = "sharded" if eps_sharded else "replicated"
+    x_layout_desc = "sharded (halo exchange per step)" if x_sharded else "replicated"
+    headline = {
+        "metric": "Jacobian columns/s (coloured sparse finite-difference Jacobian; headline config N=10^7 tridiagonal forward)",
+        "value": N / (ms_step * 1e-3),
+        "unit": "columns/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_step,
+        "higher_is_better": True,
+        "scaling": "weak" if (args.weak and world > 1) else "strong",
+        "vs_baseline": None,
+        "dtype": args.dtype,
+        "data": "synthetic",
+        "config": {"workload": wl, "name": cfg, "fdtype": fdtype, "colors": C,
+                   "parallelism": ("colours x%d" % world) if by_color else ("columns x%d" % world),
+                   "output": ("nzval in HBM" if world == 1 else
+                              "nzval assembled on rank 0 inside the step" if gather_in_step else
+                              "nzval device-resident, sharded by column range (rank r holds its contiguous slice)"),
+                   "f_mode": ("built-in device f! behind fd_f_launch_lazy with FD_LAZY_CAP_STORE (1 launch: lazily perturbed points, "
+                              "difference quotients stored into nzval by the same launch)" if (f_mode == "lazy" and lazy_store) else
+                              "built-in device f! behind fd_f_launch_lazy with FD_LAZY_CAP_DIFF (1 launch: lazily perturbed points, "
+                              "written as differences from f(x) / from the minus point)" if (f_mode == "lazy" and lazy_diff) else
+                              "built-in device f! behind fd_f_launch_lazy (1 launch: base + lazily perturbed points)"
+                              if f_mode == "lazy" else
+                              "built-in device f! behind fd_f_launch (materialised points, one batched launch)"),
+                   "eps_reduction": eps_desc, "x_layout": x_layout_desc, "gather_in_step": bool(gather_in_step),
+                   "small_messages": (p2p_note or "rccl") if world > 1 else None,
+                   "variant": ((("weak" if args.weak else "strong") + "-" + ("sharded" if x_sharded else "replicated")) if (world > 1 and not by_color) else None),
+                   "variant_selection": ("fastest of the four timed in this run (see `variants`)" if variants else "as the flags say") if world > 1 else None,
+                   "step_exchange": in_call if world > 1 else None,
+                   "problem": ("N = %d = %d x 10^7 columns (weak scaling)" % (N, world)) if (args.weak and world > 1) else None,
+                   "collective_backend": (("rccl via libfdjac fd_comm_* (%s)" % comm.info()["library"]) if comm is not None
+                                          else backend) if world > 1 else None},
+    }
+    if not args.full:
+        if rank == 0:
+            emit_line(json.dumps(headline) + "\n", json_fd)
+        release()
+        return
     tm = plan.timings()
     dec_samples = plan.timing_samples("decompress")          # the graded kernel, one HIP-event span per timed step
     timed_result = out.clone()
@@ -778,12 +876,6 @@ def main():
         import bench_sides
         sd = bench_sides.side_runs(dict(locals()))
         placements, handover, opaque, jit_path, dropin = (sd.get(k) for k in ("placements", "handover", "opaque", "jit_path", "dropin"))
-
-    t_max = torch.tensor([elapsed], dtype=torch.float64, device=dev)
-    if world > 1:
-        dist.all_reduce(t_max, op=dist.ReduceOp.MAX)
-    elapsed = float(t_max.item())
-    ms_step = elapsed / args.steps * 1e3
 
     # ---- the assembly of nzval, measured on its own right after the timed region (HIP events on the launch stream) ----
     gather_info = None
@@ -909,8 +1001,7 @@ def main():
             "columns": [c0, c1], "stored_values": int(counts[rank] if world > 1 and not by_color else sum(counts)),
             "stages_ms": stages, "plan_build_ms": plan_build_ms, "check": check,
             "rccl": comm.info() if comm is not None else None, "backend": backend if world > 1 else None,
-            "eps": ("sharded" if eps_sharded else "replicated"), "x_layout": "sharded (halo exchange per step)" if x_sharded else "replicated",
-            "gather": gather_info, "consumer": consumer}
+            "eps": eps_desc, "x_layout": x_layout_desc, "gather": gather_info, "consumer": consumer}
     sys.stderr.write("[bench rank %d] %s\n" % (rank, json.dumps(diag)))
     sys.stderr.flush()
 
@@ -963,39 +1054,7 @@ def main():
         if placements and "median_ms" in placements:
             for key in ("min_ms", "median_ms", "max_ms"):
                 placements["frac_at_" + key] = traffic / (placements[key] * 1e-3) / 1e9 / HBM_PEAK_GBPS
-        res = {
-            "metric": "Jacobian columns/s (coloured sparse finite-difference Jacobian; headline config N=10^7 tridiagonal forward)",
-            "value": N / (ms_step * 1e-3),
-            "unit": "columns/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_step,
-            "higher_is_better": True,
-            "scaling": "weak" if (args.weak and world > 1) else "strong",
-            "vs_baseline": None,
-            "dtype": args.dtype,
-            "data": "synthetic",
-            "config": {"workload": wl, "name": cfg, "fdtype": fdtype, "colors": C,
-                       "parallelism": ("colours x%d" % world) if by_color else ("columns x%d" % world),
-                       "output": ("nzval in HBM" if world == 1 else
-                                  "nzval assembled on rank 0 inside the step" if gather_in_step else
-                                  "nzval device-resident, sharded by column range (rank r holds its contiguous slice)"),
-                       "f_mode": ("built-in device f! behind fd_f_launch_lazy with FD_LAZY_CAP_STORE (1 launch: lazily perturbed points, "
-                                  "difference quotients stored into nzval by the same launch)" if (f_mode == "lazy" and lazy_store) else
-                                  "built-in device f! behind fd_f_launch_lazy with FD_LAZY_CAP_DIFF (1 launch: lazily perturbed points, "
-                                  "written as differences from f(x) / from the minus point)" if (f_mode == "lazy" and lazy_diff) else
-                                  "built-in device f! behind fd_f_launch_lazy (1 launch: base + lazily perturbed points)"
-                                  if f_mode == "lazy" else
-                                  "built-in device f! behind fd_f_launch (materialised points, one batched launch)"),
-                       "eps_reduction": diag["eps"], "x_layout": diag["x_layout"], "gather_in_step": bool(gather_in_step),
-                       "small_messages": (p2p_note or "rccl") if world > 1 else None,
-                       "variant": ((("weak" if args.weak else "strong") + "-" + ("sharded" if x_sharded else "replicated")) if (world > 1 and not by_color) else None),
-                       "variant_selection": ("fastest of the four timed in this run (see `variants`)" if variants else "as the flags say") if world > 1 else None,
-                       "step_exchange": in_call if world > 1 else None,
-                       "problem": ("N = %d = %d x 10^7 columns (weak scaling)" % (N, world)) if (args.weak and world > 1) else None,
-                       "collective_backend": (("rccl via libfdjac fd_comm_* (%s)" % comm.info()["library"]) if comm is not None
-                                              else backend) if world > 1 else None},
+        res = dict(headline, **{
             "value_cold_x": (N / (rotating["median_ms_per_step"] * 1e-3)) if (rotating and rotating.get("median_ms_per_step")) else None,
             "value_cold_x_note": "the same call on an x that is NOT cache-resident from the call before (rotating_x): the rate a caller "
                                  "who produces a fresh x elsewhere sees; quote the lower of value / value_cold_x",
@@ -1046,7 +1105,7 @@ def main():
             "value_with_gather": (N / ((ms_step + (0.0 if gather_in_step else gather_info["ms"])) * 1e-3)
                                   if (gather_info and "ms" in gather_info) else None),
             "result_check": check,
-        }
+        })
         try:
             res["stream_copy_gbps"] = ctx.stream_copy_gbps(1 << 30, 10)
             res["roofline"]["frac_of_copy_ceiling"] = achieved / res["stream_copy_gbps"]
@@ -1059,11 +1118,7 @@ def main():
             except Exception as e:  # pragma: no cover
                 res["cpu_baseline"] = {"error": str(e)}
         line = json.dumps(res) + "\n"
-        if json_fd is not None:
-            os.write(json_fd, line.encode())
-        else:
-            sys.stdout.write(line)
-            sys.stdout.flush()
+        emit_line(line, json_fd)
         if args.sweep and world == 1:
             # the other BASELINE configs as child processes (own plans / buffers), one JSON line per file
             import subprocess
@@ -1074,7 +1129,7 @@ def main():
                 if c == cfg and not extra:
                     continue
                 cmd = [sys.executable, os.path.abspath(__file__), "--config", c, "--steps", str(args.steps), "--warmup", str(args.warmup),
-                       "--no-cpu-baseline", "--soak-seconds", "0"] + extra
+                       "--full", "--no-cpu-baseline", "--soak-seconds", "0"] + extra
                 name = "bench_%s%s.json" % (c, "_f32" if extra else "")
                 with open(os.path.join(args.sweep, name), "w") as fh, open(os.path.join(args.sweep, name.replace(".json", ".err")), "w") as eh:
                     subprocess.run(cmd, stdout=fh, stderr=eh, timeout=600, check=False)
@@ -1091,13 +1146,7 @@ def main():
                 dist.all_reduce(go, op=dist.ReduceOp.MIN)
             if not go.item():
                 break
-    if world > 1:
-        dist.barrier()
-        torch.cuda.synchronize()
-        del enqueue, plan                 # release in dependency order: plans, then the communicator, then torch's group
-        if comm is not None:
-            comm._fin()
-        dist.destroy_process_group()
+    release()
     if not check["ok"]:
         raise SystemExit("bench.py: result check FAILED: %s" % json.dumps(check))
 

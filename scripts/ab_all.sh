@@ -1,6 +1,7 @@
 #!/bin/bash
 # A/B of one library variant on the graded kernels of c3 / c4 / c5 and the Float32 forms of c3 / c5 (one box)
 cd "$(dirname "$0")/.."
+OUT=${OUT:-bench_out}; mkdir -p "$OUT"
 v=$1
 show() { python - "$1" "$2" <<'PY'
 import json, sys
@@ -11,7 +12,7 @@ PY
 }
 for cfg in "c3" "c3 --dtype f32" "c5" "c5 --dtype f32" "c4" "c4 --dtype f32"; do
 for rep in 1 2; do
-python bench.py --config $cfg --soak-seconds 0 --no-cpu-baseline --no-plain-handover > gpurun_out/ab_base.json 2>/dev/null; show "base $cfg" gpurun_out/ab_base.json
-scripts/with_variant.sh $v python bench.py --config $cfg --soak-seconds 0 --no-cpu-baseline --no-plain-handover > gpurun_out/ab_$v.json 2>/dev/null; show "$v $cfg" gpurun_out/ab_$v.json
+python bench.py --full --config $cfg --soak-seconds 0 --no-cpu-baseline --no-plain-handover > $OUT/ab_base.json 2>/dev/null; show "base $cfg" $OUT/ab_base.json
+scripts/with_variant.sh $v python bench.py --full --config $cfg --soak-seconds 0 --no-cpu-baseline --no-plain-handover > $OUT/ab_$v.json 2>/dev/null; show "$v $cfg" $OUT/ab_$v.json
 done
 done

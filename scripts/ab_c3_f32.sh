@@ -1,10 +1,10 @@
-mkdir -p gpurun_out/r06_s3
+OUT=${OUT:-bench_out/c3_f32}; mkdir -p "$OUT"
 python -m pytest tests/test_gpu_float32.py -x -q -m gpu 2>&1 | tail -8
 export FDJAC_TEST_SWITCHES=1
 for rep in 1 2; do
 for v in 1 0; do
-FDJAC_S5_WAVE4=$v python bench.py --config c3 --dtype f32 --soak-seconds 0 --no-cpu-baseline --no-plain-handover > gpurun_out/r06_s3/c3f32_w$v.json 2>gpurun_out/r06_s3/c3f32_w$v.err
-python - gpurun_out/r06_s3/c3f32_w$v.json $v <<'PY'
+FDJAC_S5_WAVE4=$v python bench.py --full --config c3 --dtype f32 --soak-seconds 0 --no-cpu-baseline --no-plain-handover > $OUT/c3f32_w$v.json 2>$OUT/c3f32_w$v.err
+python - $OUT/c3f32_w$v.json $v <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 r = d["roofline"]

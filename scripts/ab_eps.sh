@@ -8,7 +8,7 @@ print('%-8s %-3s ms/step %.4f  eps stage %.4f  store %.4f' % ('$1', '$2', d['ms_
 "; }
 for rep in 1 2 3; do
 for c in c4 c3 c2; do
-  python bench.py --config $c --soak-seconds 0 --no-cpu-baseline --no-plain-handover 2>/dev/null | show new $c
-  scripts/with_variant.sh oldload python bench.py --config $c --soak-seconds 0 --no-cpu-baseline --no-plain-handover 2>/dev/null | show old $c
+  python bench.py --full --config $c --soak-seconds 0 --no-cpu-baseline --no-plain-handover 2>/dev/null | show new $c
+  scripts/with_variant.sh oldload python bench.py --full --config $c --soak-seconds 0 --no-cpu-baseline --no-plain-handover 2>/dev/null | show old $c
 done
 done

@@ -13,7 +13,7 @@ DIFF=1; [ "${FDJAC_LAZY_DIFF:-1}" = "0" ] && DIFF=0; [ "$CFG" = "c5" ] && DIFF=0
 # (a storing f! launch is the graded kernel of the exact-band configs unless FDJAC_LAZY_STORE=0)
 STORE=0; case "$KERN" in *store*|*fused*) STORE=1;; esac
 python $REPO/scripts/make_pmc_json.py $F $W $N 1 $KERN $DIFF $STORE > $OUT/pmc.json 2>> $OUT/summary.err
-cd $REPO && python bench.py --config $CFG "$@" > $OUT/bench.json 2> $OUT/bench.err
+cd $REPO && python bench.py --full --config $CFG "$@" > $OUT/bench.json 2> $OUT/bench.err
 python - $OUT >> $OUT/summary.md <<'PY'
 import re, sys
 d = sys.argv[1]

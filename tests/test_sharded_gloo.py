@@ -146,7 +146,7 @@ def test_bench_two_ranks_dry_run_variants(variant):
              "weak": ["--weak"]}[variant]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=port, FDJAC_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-           "127.0.0.1", "--master-port", port, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3",
+           "127.0.0.1", "--master-port", port, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3",
            "--warmup", "1", "--size", "300001", "--soak-seconds", "0"] + extra
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=380)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
@@ -175,7 +175,7 @@ def test_bench_spawns_its_own_ranks_and_times_every_variant():
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(FDJAC_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--size", "300001", "--soak-seconds", "0.3"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--size", "300001", "--soak-seconds", "0.3"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=560)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-6000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -226,7 +226,7 @@ def test_bench_two_ranks_share_one_gpu(tmp_path, in_step):
     port = "29519" if in_step else "29523"
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=port, FDJAC_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-           "127.0.0.1", "--master-port", port, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3",
+           "127.0.0.1", "--master-port", port, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3",
            "--warmup", "1", "--size", "300001", "--soak-seconds", "0", "--variant", "flags"] + (["--gather-in-step"] if in_step else [])
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=380)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]

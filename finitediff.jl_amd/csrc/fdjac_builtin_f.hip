@@ -290,7 +290,7 @@ k_f_tridiag_fused(const real_t *__restrict__ x, int64_t n, fd_band_store bst, in
     real_t (*s_win)[FD_BAND_WAVE_LDS(3)] = reinterpret_cast<real_t (*)[FD_BAND_WAVE_LDS(3)]>(s_lds);
     double *s_red = reinterpret_cast<double *>(s_lds);
     const int b = (int)blockIdx.x, nfin = fz.eg.C;
-    if (b < nfin) { fused_finisher(fz, b, s_red); return; }
+    if (b < nfin) { fused_finisher(fz, b, s_red, x, n); return; }
     if (b < nfin + fz.nblocks) { fused_eps_block<NC, PIPE>(x, n, fz, b - nfin, reinterpret_cast<double (*)[NC]>(s_red)); return; }
     // a storing workgroup: its wavefronts walk the 128-column tiles gw, gw + stride, ... (the launcher keeps the whole grid resident,
     // so nobody is dispatched after the step sizes are out); the first tile's x is in flight while the workgroup waits
@@ -396,7 +396,7 @@ k_f_tridiag_fused4(const real_t *__restrict__ x, int64_t n, fd_band_store bst, i
     real_t (*s_win)[FD_BAND_WAVE4_LDS(3)] = reinterpret_cast<real_t (*)[FD_BAND_WAVE4_LDS(3)]>(s_lds);
     double *s_red = reinterpret_cast<double *>(s_lds);
     const int b = (int)blockIdx.x, nfin = fz.eg.C;
-    if (b < nfin) { fused_finisher(fz, b, s_red); return; }
+    if (b < nfin) { fused_finisher(fz, b, s_red, x, n); return; }
     if (b < nfin + fz.nblocks) { fused_eps_block<NC, PIPE>(x, n, fz, b - nfin, reinterpret_cast<double (*)[NC]>(s_red)); return; }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int cb = b - nfin - fz.nblocks;

@@ -47,6 +47,34 @@ template <> __device__ __forceinline__ void load_color_pair<int32_t>(const int32
     c1 = v.y;
 }
 
+// the colour of element i of x as eps_block_sum reads it (complex-valued x: the (re, im) pair takes the colour of its first slot)
+template <typename CT, bool CYC>
+__device__ __forceinline__ int eps_color_of(const CT *__restrict__ color, int64_t i, int cyc_C, int cyc_shift, int pair)
+{
+    if (pair) i &= ~(int64_t)1;
+    return CYC ? (int)((i + cyc_shift) % cyc_C) : (int)color[i];
+}
+
+// the norm of colour cc summed once more with the exact scaling 2^k (eps_rescale_exp: k = -600 after an overflow, +600 after an
+// underflow): sqrt(sum (x_j * 2^k)^2) * 2^-k.  ONE whole wavefront calls it with wave-uniform arguments; every lane gets the norm.
+// Reached only when the plain sum left the range: its order is this function's own.  Not inlined: the cold loop (64-bit modulo
+// of the cyclic colours included) then adds nothing to the register allocation of the reductions and the fused step -- inlined,
+// k_eps_partial_reg took one VGPR more.
+template <typename CT, bool CYC>
+__device__ __noinline__ double eps_rescan_norm_wave(const real_t *__restrict__ x, const CT *__restrict__ color, int64_t n, int cyc_C,
+                                                       int cyc_shift, int pair, int cc, int k)
+{
+    const double sc = k < 0 ? 0x1p-600 : 0x1p600, unsc = k < 0 ? 0x1p600 : 0x1p-600;
+    double acc = 0.0;
+    for (int64_t i = threadIdx.x & 63; i < n; i += 64)
+        if (eps_color_of<CT, CYC>(color, i, cyc_C, cyc_shift, pair) == cc) {
+            const double v = (double)x[i] * sc;
+            acc += v * v;
+        }
+    acc = wave_sum(acc);
+    return sqrt(__shfl(acc, 0, 64)) * unsc;
+}
+
 constexpr int kEpsU = 4;  // independent 16-B loads in flight per thread
 
 // The reduction is DEFINED as a rank-aligned two-level sum, a function of N alone (see k_eps_partial_reg, fdjac_kernels.hip).
@@ -282,7 +310,11 @@ __device__ __forceinline__ void fused_eps_block(const real_t *__restrict__ x, in
 //  per colour with per-lane address lists: 3.6 / 6-9 us (scattered again); this form: profiles/r06_fused_trace.md.)
 // lds: kFzMaxBlocks + 2 * kEpsGroups doubles.
 constexpr int kFzMaxBlocks = kEpsGroups * kEpsBlocksPerGroup;      // 1024
-__device__ __forceinline__ void fused_finisher(const FusedEps &fz, int c, double *lds)
+// x / color / n: the colour map the reduction workgroups read (cyclic unless CYC = false) -- rescanned by wavefront 0 when colour c's
+// plain sum over- or underflowed (eps_rescale_exp; never on a sharded step: there x is not all here, and the step size stays +Inf).
+template <typename CT = uint8_t, bool CYC = true>
+__device__ __forceinline__ void fused_finisher(const FusedEps &fz, int c, double *lds, const real_t *__restrict__ x, int64_t n,
+                                               const CT *__restrict__ color = nullptr)
 {
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, nb = fz.nblocks, bpg = fz.eg.bpg;
     const bool sharded = fz.nranks > 1;
@@ -392,8 +424,13 @@ __device__ __forceinline__ void fused_finisher(const FusedEps &fz, int c, double
 #pragma unroll
         for (int k = 0; k < 16; ++k) tot += w[k];
     }
-    real_t e = eps_rule<real_t>(tot, fz.eg.relstep, fz.eg.absstep, fz.eg.dir, fz.eg.is_forward);
-    if (bad) e = fz_from_bits(FzBits<real_t>::sentinel ^ 1);      // (a NaN that is not the sentinel: the storing wavefronts go on and store NaNs)
+    double nrm = sqrt(tot);
+    const int k = sharded || bad ? 0 : eps_rescale_exp(tot, fz.eg.relstep, fz.eg.absstep);      // (wave-uniform: every lane holds tot)
+    if (k != 0) nrm = eps_rescan_norm_wave<CT, CYC>(x, color, n, fz.cyc_C, fz.cyc_shift, fz.pair, c, k);
+    real_t e = eps_rule_norm<real_t>(nrm, fz.eg.relstep, fz.eg.absstep, fz.eg.dir, fz.eg.is_forward);
+    // (a NaN that is not the sentinel: the storing wavefronts go on and store NaNs -- after a time-out, or when a NaN of x carried the
+    //  sentinel's payload into the step size, which is no error)
+    if (bad || fz_to_bits(e) == FzBits<real_t>::sentinel) e = fz_from_bits(FzBits<real_t>::sentinel ^ 1);
     __hip_atomic_store(fz.epsr + lane * kFzPitch + c, fz_to_bits(e), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // replica `lane`
     if (t == 0) {
         if (bad) __hip_atomic_store(fz.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);

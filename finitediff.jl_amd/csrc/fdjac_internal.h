@@ -224,18 +224,44 @@ __device__ inline int64_t xcd_tile(int64_t block, int64_t ntiles)
     return (block & 7) * xcd_chunks(ntiles) + (block >> 3);
 }
 
-// the step rule applied to a masked sum of squares t = sum_{color[j] == c} x[j]^2 (every step-size kernel ends in this)
-template <typename T> __device__ __forceinline__ T eps_rule(double t, double relstep, double absstep, double dir, int is_forward)
+// max(a, absstep) as Julia's max: a NaN on either side is the result (src/epsilons.jl:26-29, 50-53 -- compute_epsilon)
+template <typename T> __host__ __device__ __forceinline__ T eps_max(T a, T absstep)
+{
+    return (a > absstep || a != a) ? a : absstep;
+}
+
+// the step rule applied to a 2-norm `nrm` of the colour's coordinates
+template <typename T> __device__ __forceinline__ T eps_rule_norm(double nrm, double relstep, double absstep, double dir, int is_forward)
 {
     // norm(x2), sqrt and the step rule in the element type, as the reference computes them:
     //   forward: max(relstep*abs(sqrt(norm)), absstep)*dir   (src/epsilons.jl:26-29; the sqrt of the 2-norm is src/jacobians.jl:561)
     //   central: max(relstep*abs(sqrt(norm)), absstep)       (src/epsilons.jl:50-53; jacobians.jl:602)
-    const T nrm = (T)sqrt(t);                  // norm(x2)
-    const T xs = fabs(sqrt(nrm));              // abs(sqrt(tmp))
+    const T xs = fabs(sqrt((T)nrm));           // abs(sqrt(tmp))
     const T a = (T)relstep * xs;
-    T e = (a > (T)absstep) ? a : (T)absstep;
+    T e = eps_max<T>(a, (T)absstep);
     if (is_forward) e = e * (T)dir;
     return e;
+}
+
+// the step rule applied to a masked sum of squares t = sum_{color[j] == c} x[j]^2 (every step-size kernel ends in this)
+template <typename T> __device__ __forceinline__ T eps_rule(double t, double relstep, double absstep, double dir, int is_forward)
+{
+    return eps_rule_norm<T>(sqrt(t), relstep, absstep, dir, is_forward);
+}
+
+// The plain Float64 sum of squares overflows for |x| >~ 1.3e154 and loses the squares below ~1e-162, where the reference's norm
+// (LinearAlgebra's scaled 2-norm) is finite / exact.  A colour whose total t is +Inf, or is below 2^-960 while the relative term can
+// still exceed absstep (absstep < relstep * 2^-240), is summed once more as sum (x * 2^k)^2 with k = -600 / +600 -- exact power-of-two
+// scaling -- and its norm is sqrt(that) * 2^-k (eps_rescan_norm_wave).  Returns k, or 0: the plain sum stands (every ordinary
+// magnitude: same bits as before).  Float32 elements are summed in Float64, where neither can happen: always 0.
+__device__ __forceinline__ int eps_rescale_exp(double t, double relstep, double absstep)
+{
+    if constexpr (sizeof(real_t) == 8) {
+        if (t == __builtin_huge_val()) return -600;
+        if (t < 0x1p-960 && absstep < relstep * 0x1p-240) return 600;
+    }
+    (void)t; (void)relstep; (void)absstep;
+    return 0;
 }
 
 // TEST SWITCHES.  A handful of FDJAC_* environment variables select between bit-identical kernel variants / plan builders so that the

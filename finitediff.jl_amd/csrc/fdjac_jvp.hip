@@ -69,7 +69,7 @@ k_jvp_eps(const double *__restrict__ partial, int nparts, double relstep, double
         for (int w = 0; w < kBlock / 64; ++w) t += red[w];
         const real_t tmp = sqrt(fabs((real_t)t));      // the dot product in Float64, the step rule in the element type
         const real_t a = (real_t)relstep * fabs(tmp);
-        real_t e = (a > (real_t)absstep) ? a : (real_t)absstep;   // src/epsilons.jl:26-29,50-53
+        real_t e = eps_max<real_t>(a, (real_t)absstep);   // src/epsilons.jl:26-29,50-53 (NaN propagates)
         if (is_forward) e = e * (real_t)dir;
         eps[0] = e;
     }
@@ -131,7 +131,7 @@ k_jvp_small(const real_t *__restrict__ x, const real_t *__restrict__ v, int64_t 
         for (int w = 0; w < kJvpSmallBlock / 64; ++w) t += red[w];
         const real_t tmp = sqrt(fabs((real_t)t));
         const real_t a = (real_t)relstep * fabs(tmp);
-        real_t e = (a > (real_t)absstep) ? a : (real_t)absstep;   // src/epsilons.jl:26-29,50-53
+        real_t e = eps_max<real_t>(a, (real_t)absstep);   // src/epsilons.jl:26-29,50-53 (NaN propagates)
         if (!central) e = e * (real_t)dir;
         eps[0] = e;
         s_e = e;

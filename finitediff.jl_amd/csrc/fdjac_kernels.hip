@@ -104,11 +104,20 @@ k_eps_partial_reg(const real_t *__restrict__ x, const CT *__restrict__ color, in
         for (int u = 0; u < kRegColors; ++u) stage[u * 64 + lane] = v[u];
     }
     __builtin_amdgcn_wave_barrier();
-    if (lane < NC) {
+    {
         double tot = 0.0;
-        for (int g = 0; g < kEpsGroups; ++g) tot += stage[g * ldp + lane];
-        if (lane < eg.C) {
-            const real_t e = eps_rule<real_t>(tot, eg.relstep, eg.absstep, eg.dir, eg.is_forward);
+        if (lane < NC)
+            for (int g = 0; g < kEpsGroups; ++g) tot += stage[g * ldp + lane];
+        // a colour whose plain sum over- or underflowed: summed once more with a power-of-two scaling by the whole wavefront
+        double nrm = sqrt(tot);
+        const int k = lane < NC && lane < eg.C ? eps_rescale_exp(tot, eg.relstep, eg.absstep) : 0;
+        for (unsigned long long m = __ballot(k != 0); m; m &= m - 1) {
+            const int cc = __builtin_ctzll(m);
+            const double r = eps_rescan_norm_wave<CT, CYC>(x, color, n, cyc_C, cyc_shift, pair, cc, __shfl(k, cc, 64));
+            if (lane == cc) nrm = r;
+        }
+        if (lane < NC && lane < eg.C) {
+            const real_t e = eps_rule_norm<real_t>(nrm, eg.relstep, eg.absstep, eg.dir, eg.is_forward);
             eps[lane] = e;
             if (eps2) eps2[lane] = (real_t)2 * e;           // (central differences handed over as f(+) - f(-), see launch_scale)
         }
@@ -127,7 +136,7 @@ k_eps_flags(const real_t *__restrict__ x, const CT *__restrict__ color, int64_t 
 {
     __shared__ __attribute__((aligned(16))) double s_lds[kFzMaxBlocks + 2 * kEpsGroups + 2];
     const int b = (int)blockIdx.x;
-    if (b < fz.eg.C) { fused_finisher(fz, b, s_lds); return; }
+    if (b < fz.eg.C) { fused_finisher<CT, CYC>(fz, b, s_lds, x, n, color); return; }
     fused_eps_block<NC, true, CT, CYC, NT>(x, n, fz, b - fz.eg.C, reinterpret_cast<double (*)[NC]>(s_lds), color);
 }
 
@@ -183,7 +192,8 @@ k_eps_partial_seg(const real_t *__restrict__ x, const int32_t *__restrict__ perm
 //   central: max(relstep*abs(sqrt(norm)), absstep)       (src/epsilons.jl:50-53; jacobians.jl:602)
 __global__ void __launch_bounds__(kBlock)
 k_eps_finalize(const double *__restrict__ partial, int nparts, int ldp, double relstep,
-               double absstep, double dir, int is_forward, real_t *__restrict__ eps, real_t *__restrict__ eps2)
+               double absstep, double dir, int is_forward, real_t *__restrict__ eps, real_t *__restrict__ eps2,
+               const real_t *__restrict__ x, const int32_t *__restrict__ perm, const int64_t *__restrict__ cptr, int pair)
 {
     const int c = blockIdx.x;
     double acc = 0.0;
@@ -192,12 +202,27 @@ k_eps_finalize(const double *__restrict__ partial, int nparts, int ldp, double r
     acc = wave_sum(acc);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
     __syncthreads();
-    if (threadIdx.x == 0) {
+    if (threadIdx.x < 64) {
         double t = 0.0;
         for (int w = 0; w < kBlock / 64; ++w) t += red[w];
-        const real_t e = eps_rule<real_t>(t, relstep, absstep, dir, is_forward);
-        eps[c] = e;
-        if (eps2) eps2[c] = (real_t)2 * e;                  // (central differences handed over as f(+) - f(-), see launch_scale)
+        double nrm = sqrt(t);
+        const int k = eps_rescale_exp(t, relstep, absstep);
+        if (k != 0) {       // over- or underflow: the colour's list once more, scaled by 2^k (eps_rescale_exp)
+            const double sc = k < 0 ? 0x1p-600 : 0x1p600, unsc = k < 0 ? 0x1p600 : 0x1p-600;
+            double a2 = 0.0;
+            for (int64_t i = cptr[c] + threadIdx.x; i < cptr[c + 1]; i += 64) {
+                const double v = (double)x[perm[i]] * sc;
+                a2 += v * v;
+                if (pair) { const double w = (double)x[perm[i] + 1] * sc; a2 += w * w; }
+            }
+            a2 = wave_sum(a2);
+            nrm = sqrt(__shfl(a2, 0, 64)) * unsc;
+        }
+        if (threadIdx.x == 0) {
+            const real_t e = eps_rule_norm<real_t>(nrm, relstep, absstep, dir, is_forward);
+            eps[c] = e;
+            if (eps2) eps2[c] = (real_t)2 * e;              // (central differences handed over as f(+) - f(-), see launch_scale)
+        }
     }
 }
 
@@ -244,17 +269,24 @@ k_eps_perturb_small(const real_t *__restrict__ x, const CT *__restrict__ color, 
         if (lane == 0) red[wave][c] = t;
     }
     __syncthreads();
-    if ((int)threadIdx.x < NC) {
+    if (wave == 0) {
         double t = 0.0;
+        if (lane < NC) {
 #pragma unroll
-        for (int w = 0; w < kSmallBlock / 64; ++w) t += red[w][threadIdx.x];
-        const real_t nrm = (real_t)sqrt(t);
-        const real_t xs = fabs(sqrt(nrm));
-        const real_t a = (real_t)relstep * xs;
-        real_t e = (a > (real_t)absstep) ? a : (real_t)absstep;
-        if (is_forward) e = e * (real_t)dir;
-        s_eps[threadIdx.x] = e;
-        if ((int)threadIdx.x < C) eps[threadIdx.x] = e;
+            for (int w = 0; w < kSmallBlock / 64; ++w) t += red[w][lane];
+        }
+        double nrm = sqrt(t);
+        const int k = lane < NC && lane < C ? eps_rescale_exp(t, relstep, absstep) : 0;
+        for (unsigned long long m = __ballot(k != 0); m; m &= m - 1) {      // over- or underflow: rescaled once more (eps_rescale_exp)
+            const int cc = __builtin_ctzll(m);
+            const double r = eps_rescan_norm_wave<CT, false>(x, color, n, 0, 0, 0, cc, __shfl(k, cc, 64));
+            if (lane == cc) nrm = r;
+        }
+        if (lane < NC) {
+            const real_t e = eps_rule_norm<real_t>(nrm, relstep, absstep, dir, is_forward);
+            s_eps[lane] = e;
+            if (lane < C) eps[lane] = e;
+        }
     }
     if (PMODE < 0) return;
     __syncthreads();
@@ -1225,7 +1257,7 @@ k_eps_element(const real_t *__restrict__ x, int64_t ncols, double relstep, doubl
         // abs(x_i): of a complex element (complex-valued x) the modulus
         const real_t ax = pair ? (real_t)hypot((double)x[2 * i], (double)x[2 * i + 1]) : (real_t)fabs(x[i]);
         const real_t a = (real_t)relstep * ax;
-        real_t e = (a > (real_t)absstep) ? a : (real_t)absstep;
+        real_t e = eps_max<real_t>(a, (real_t)absstep);
         if (is_forward) e = e * dir;
         eps[i] = e;
     }
@@ -1363,10 +1395,10 @@ int launch_eps_final(fd_plan *p, double relstep, double absstep, double dir)
 }
 
 // (the many-colour path's second stage: one block per colour over the chunk partials)
-int launch_eps_finalize(fd_plan *p, int nparts, int ldp, double relstep, double absstep, double dir)
+int launch_eps_finalize(fd_plan *p, const real_t *x, int nparts, int ldp, double relstep, double absstep, double dir)
 {
     hipLaunchKernelGGL(k_eps_finalize, dim3((unsigned)p->C), dim3(kBlock), 0, p->ctx->stream, p->d_partial, nparts, ldp, relstep,
-                       absstep, dir, p->fdtype == FD_FORWARD ? 1 : 0, p->d_eps, p->d_eps2);
+                       absstep, dir, p->fdtype == FD_FORWARD ? 1 : 0, p->d_eps, p->d_eps2, x, p->d_perm, p->d_cptr, p->cx ? 1 : 0);
     p->eps2_fresh = p->d_eps2 != nullptr;
     FD_HIP_CHECK(hipGetLastError());
     return FD_OK;
@@ -1381,7 +1413,7 @@ static int launch_eps_t(fd_plan *p, const real_t *x, double relstep, double abss
     const int nparts = p->seg_chunks;
     hipLaunchKernelGGL(k_eps_partial_seg, dim3((unsigned)((int64_t)C * nparts)), dim3(kBlock), 0, s,
                        x, p->d_perm, p->d_cptr, (int64_t)C, nparts, p->d_partial, p->cx ? 1 : 0);
-    return launch_eps_finalize(p, nparts, C, relstep, absstep, dir);
+    return launch_eps_finalize(p, x, nparts, C, relstep, absstep, dir);
 }
 
 // the fused small-problem launch (k_eps_perturb_small); pmode -1 = step sizes only

@@ -336,6 +336,16 @@ int fd_plan_row_lists(const fd_plan *plan, const void **row_ptr_dev, const void 
  * once, src/jacobians.jl:540-545); it is ignored for central / complex.  relstep <= 0 selects
  * default_relstep (src/epsilons.jl:133-144); absstep < 0 selects absstep = relstep.  dir is
  * the reference's `dir` (true/+1 or -1; forward only).  Blocks until outs are complete.
+ *
+ * The step rule at the edges (src/epsilons.jl:26-29, 50-53; the norm of src/jacobians.jl:560, 601):
+ *   - max(relstep * abs(sqrt(norm)), absstep) is Julia's max: a NaN on either side propagates.  A colour with a NaN coordinate
+ *     gets a NaN step size and NaN values in its columns; this is no error (no FD_ERR_COMM).
+ *   - The masked norm is a plain Float64 sum of squares.  Where that sum overflows (+Inf: |x| >~ 1.3e154), or falls below
+ *     2^-960 while absstep < relstep * 2^-240, the colour's norm is recomputed as sqrt(sum (x * 2^-+600)^2) * 2^+-600, the
+ *     scaled 2-norm the reference's norm returns there (within a few ulps).  Sharded plans (a communicator or mailbox
+ *     attached) do not rescan: an overflowed colour keeps eps = Inf there.
+ *   - Every colour is evaluated from the caller's x.  The reference un-perturbs x in place (x1 - eps * mask), so after a
+ *     NaN step size its later colours see NaN coordinates; that poisoning is not reproduced.
  */
 int fd_jacobian(fd_plan *plan, fd_f_launch f, void *fctx, const void *x, int x_kind,
                 const void *f_in, int f_in_kind, double relstep, double absstep, double dir,

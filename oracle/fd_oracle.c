@@ -116,16 +116,20 @@ typedef struct {
     int64_t lam, mu;
 } fdo_pattern;
 
+/* v * (b ? 1 : 0) as Julia computes v * Bool: false is a strong zero, copysign(0, v) even for a NaN or infinite v
+   (same bits as v * 0.0 for every finite v) */
+static inline fdo_real bmul(fdo_real v, int b) { return b ? v : copysign((fdo_real)0.0, v); }
+
 /* ---- src/epsilons.jl:26-29, 50-53 ---- */
 static inline fdo_real eps_forward(fdo_real x, fdo_real relstep, fdo_real absstep, fdo_real dir)
 {
     fdo_real a = relstep * fabs(x);
-    return (a > absstep ? a : absstep) * dir;
+    return (a > absstep || a != a ? a : absstep) * dir;     /* Julia's max: a NaN propagates */
 }
 static inline fdo_real eps_central(fdo_real x, fdo_real relstep, fdo_real absstep)
 {
     fdo_real a = relstep * fabs(x);
-    return (a > absstep ? a : absstep);
+    return (a > absstep || a != a ? a : absstep);
 }
 
 /* src/epsilons.jl:133-144 */
@@ -137,13 +141,31 @@ fdo_real fdo_default_relstep(int fdtype)
     return 1.0;
 }
 
-/* LinearAlgebra.norm restated (see header) */
-static fdo_real norm2(const fdo_real *v, int64_t n)
+/* LinearAlgebra.norm restated (see header): the plain sum of squares; when it overflows, or underflows while the relative
+   term of the step rule can still exceed absstep, the scaled norm the reference's norm (BLAS nrm2 / generic_norm2) computes
+   there -- sum (v_i * 2^-+600)^2 in double, scaled back (the Float32 oracle: the plain sum in double, unscaled -- a float's
+   square cannot leave double's range, and a scaling by 2^600 would overflow it).  The thresholds: a total of +Inf, or below 2^-960 (2^-120 in Float32) with absstep < relstep * 2^-240
+   (2^-30).  Every ordinary magnitude keeps the plain sum. */
+static fdo_real norm2(const fdo_real *v, int64_t n, fdo_real relstep, fdo_real absstep)
 {
     fdo_real s = 0.0;
     FDO_PAR_SUM(s)
     for (int64_t i = 0; i < n; ++i) s += v[i] * v[i];
-    return sqrt(s);
+#ifdef FDO_F32
+    const double tiny = 0x1p-120, rel = 0x1p-30;
+#else
+    const double tiny = 0x1p-960, rel = 0x1p-240;
+#endif
+    const int over = s == (fdo_real)INFINITY, under = s < tiny && absstep < relstep * rel;
+    if (!over && !under) return sqrt(s);
+#ifdef FDO_F32
+    const double sc = 1.0;
+#else
+    const double sc = over ? 0x1p-600 : 0x1p600;
+#endif
+    double d = 0.0;
+    for (int64_t i = 0; i < n; ++i) { const double w = (double)v[i] * sc; d += w * w; }
+    return (fdo_real)(sqrt(d) / sc);
 }
 
 static int64_t max_color(const int64_t *colorvec, int64_t n)
@@ -329,17 +351,17 @@ int fdo_jacobian_cached(int fdtype, fdo_f_real f, fdo_f_cplx fc, void *ctx, fdo_
                 x1[color_i - 1] = x1_save;
             } else { /* :558-585 */
                 FDO_PAR
-                for (int64_t i = 0; i < N; ++i) x2[i] = x1[i] * (fdo_real)(colorvec[i] == color_i);
-                fdo_real tmp = norm2(x2, N);
+                for (int64_t i = 0; i < N; ++i) x2[i] = bmul(x1[i], colorvec[i] == color_i);
+                fdo_real tmp = norm2(x2, N, relstep, absstep);
                 fdo_real epsilon = eps_forward(sqrt(tmp), relstep, absstep, dir);
                 FDO_PAR
-                for (int64_t i = 0; i < N; ++i) x1[i] = x1[i] + epsilon * (fdo_real)(colorvec[i] == color_i);
+                for (int64_t i = 0; i < N; ++i) x1[i] = x1[i] + bmul(epsilon, colorvec[i] == color_i);
                 f(ctx, fx1, x1); ++nf;
                 FDO_PAR
                 for (int64_t r = 0; r < M; ++r) fx1[r] = (fx1[r] - vfx[r]) / epsilon;
                 colored_iteration(pat, fx1, colorvec, color_i);
                 FDO_PAR
-                for (int64_t i = 0; i < N; ++i) x1[i] = x1[i] - epsilon * (fdo_real)(colorvec[i] == color_i);
+                for (int64_t i = 0; i < N; ++i) x1[i] = x1[i] - bmul(epsilon, colorvec[i] == color_i);
             }
         }
     } else if (fdtype == FDO_CENTRAL) {
@@ -356,22 +378,22 @@ int fdo_jacobian_cached(int fdtype, fdo_f_real f, fdo_f_cplx fc, void *ctx, fdo_
                 x1[color_i - 1] = x_save;
             } else { /* :599-621 */
                 FDO_PAR
-                for (int64_t i = 0; i < N; ++i) x2[i] = x1[i] * (fdo_real)(colorvec[i] == color_i);
-                fdo_real tmp = norm2(x2, N);
+                for (int64_t i = 0; i < N; ++i) x2[i] = bmul(x1[i], colorvec[i] == color_i);
+                fdo_real tmp = norm2(x2, N, relstep, absstep);
                 fdo_real epsilon = eps_central(sqrt(tmp), relstep, absstep);
                 FDO_PAR
-                for (int64_t i = 0; i < N; ++i) x1[i] = x1[i] + epsilon * (fdo_real)(colorvec[i] == color_i);
+                for (int64_t i = 0; i < N; ++i) x1[i] = x1[i] + bmul(epsilon, colorvec[i] == color_i);
                 FDO_PAR
-                for (int64_t i = 0; i < N; ++i) x[i] = x[i] - epsilon * (fdo_real)(colorvec[i] == color_i);
+                for (int64_t i = 0; i < N; ++i) x[i] = x[i] - bmul(epsilon, colorvec[i] == color_i);
                 f(ctx, fx1, x1); ++nf;
                 f(ctx, fx, x); ++nf;
                 FDO_PAR
                 for (int64_t r = 0; r < M; ++r) fx1[r] = (fx1[r] - fx[r]) / (2 * epsilon);
                 colored_iteration(pat, fx1, colorvec, color_i);
                 FDO_PAR
-                for (int64_t i = 0; i < N; ++i) x1[i] = x1[i] - epsilon * (fdo_real)(colorvec[i] == color_i);
+                for (int64_t i = 0; i < N; ++i) x1[i] = x1[i] - bmul(epsilon, colorvec[i] == color_i);
                 FDO_PAR
-                for (int64_t i = 0; i < N; ++i) x[i] = x[i] + epsilon * (fdo_real)(colorvec[i] == color_i);
+                for (int64_t i = 0; i < N; ++i) x[i] = x[i] + bmul(epsilon, colorvec[i] == color_i);
             }
         }
     } else if (fdtype == FDO_COMPLEX) { /* :623-648 */
@@ -386,12 +408,12 @@ int fdo_jacobian_cached(int fdtype, fdo_f_real f, fdo_f_cplx fc, void *ctx, fdo_
                 cx1[color_i - 1] = x1_save;
             } else {
                 for (int64_t i = 0; i < N; ++i)
-                    cx1[i] = cx1[i] + CMPLX(0.0, epsilon * (fdo_real)(colorvec[i] == color_i));
+                    cx1[i] = cx1[i] + CMPLX(0.0, bmul(epsilon, colorvec[i] == color_i));
                 fc(ctx, cfx, cx1); ++nf;
                 for (int64_t r = 0; r < M; ++r) { cfx[r] = cimag(cfx[r]) / epsilon; vre[r] = creal(cfx[r]); }
                 colored_iteration(pat, vre, colorvec, color_i);
                 for (int64_t i = 0; i < N; ++i)
-                    cx1[i] = cx1[i] - CMPLX(0.0, epsilon * (fdo_real)(colorvec[i] == color_i));
+                    cx1[i] = cx1[i] - CMPLX(0.0, bmul(epsilon, colorvec[i] == color_i));
             }
         }
         free(vre);

@@ -14,12 +14,42 @@ def default_relstep(fdtype):   # src/epsilons.jl:133-144
     return {"forward": np.sqrt(EPS), "central": np.cbrt(EPS), "complex": 1.0}[fdtype]
 
 
+def _bmul(v, mask):              # v * mask as Julia's Bool multiplies: false is a strong zero (copysign(0, v), even for NaN / Inf)
+    if np.iscomplexobj(v):
+        z = np.empty(np.shape(v), np.complex128)
+        z.real, z.imag = np.copysign(0.0, np.real(v)), np.copysign(0.0, np.imag(v))
+        return np.where(mask, v, z)
+    return np.where(mask, v, np.copysign(0.0, v))
+
+
+def _max(a, b):                 # Julia's max: a NaN on either side is the result
+    return a if (a > b or a != a) else b
+
+
 def compute_epsilon(fdtype, x, relstep, absstep, dir=1.0):   # src/epsilons.jl:26-29, 50-53, 104-107
     if fdtype == "forward":
-        return max(relstep * abs(x), absstep) * dir
+        return _max(relstep * abs(x), absstep) * dir
     if fdtype == "central":
-        return max(relstep * abs(x), absstep)
+        return _max(relstep * abs(x), absstep)
     return EPS
+
+
+def norm(x2, relstep, absstep):
+    """LinearAlgebra's norm(x2) (src/jacobians.jl:560, 601): the plain sqrt(dot); where the sum of squares overflows, or
+    underflows while the relative term can still exceed absstep (< 2^-960 with absstep < relstep * 2^-240), the scaled norm
+    sqrt(sum (x * 2^-+600)^2) * 2^+-600 that the reference's scaled 2-norm returns there."""
+    def sumsq(v):               # numpy.linalg.norm's own order: x.dot(x), or re.dot(re) + im.dot(im)
+        if np.iscomplexobj(v):
+            return float(v.real.dot(v.real) + v.imag.dot(v.imag))
+        return float(v.dot(v))
+    x2 = np.asarray(x2)
+    with np.errstate(over="ignore", under="ignore"):
+        s = sumsq(x2)
+        over = s == np.inf
+        if not over and not (s < 2.0 ** -960 and absstep < relstep * 2.0 ** -240):
+            return np.sqrt(s)
+        sc = 2.0 ** -600 if over else 2.0 ** 600
+        return float(np.sqrt(sumsq(x2.astype(np.complex128 if np.iscomplexobj(x2) else np.float64) * sc)) / sc)
 
 
 def jacobian(f, x, colorvec, pattern, fdtype="forward", relstep=None, absstep=None, dir=1.0, f_in=None):
@@ -44,25 +74,25 @@ def jacobian(f, x, colorvec, pattern, fdtype="forward", relstep=None, absstep=No
         fx1 = np.zeros(M)
         for c in range(1, int(colorvec.max()) + 1):             # :547
             mask = (colorvec == c)
-            x2 = x1 * mask                                      # :559
-            eps = compute_epsilon("forward", np.sqrt(np.linalg.norm(x2)), relstep, absstep, dir)   # :560-561
-            x1 = x1 + eps * mask                                # :562
+            x2 = _bmul(x1, mask)                                      # :559
+            eps = compute_epsilon("forward", np.sqrt(norm(x2, relstep, absstep)), relstep, absstep, dir)   # :560-561
+            x1 = x1 + _bmul(eps, mask)                                # :562
             f(fx1, x1)
             ncalls += 1
             d = (fx1 - fx) / eps                                # :565
             for j in np.nonzero(mask)[0]:                       # decompression: J[row, col] = vfx[row]
                 rows = np.nonzero(pattern[:, j])[0]
                 J[rows, j] = d[rows]
-            x1 = x1 - eps * mask                                # :584
+            x1 = x1 - _bmul(eps, mask)                                # :584
     elif fdtype == "central":
         fx, fx1 = np.zeros(M), np.zeros(M)
         xx = x                                                   # the caller's x is perturbed too (:604, :620)
         for c in range(1, int(colorvec.max()) + 1):
             mask = (colorvec == c)
-            x2 = x1 * mask
-            eps = compute_epsilon("central", np.sqrt(np.linalg.norm(x2)), relstep, absstep)
-            x1 = x1 + eps * mask
-            xx = xx - eps * mask
+            x2 = _bmul(x1, mask)
+            eps = compute_epsilon("central", np.sqrt(norm(x2, relstep, absstep)), relstep, absstep)
+            x1 = x1 + _bmul(eps, mask)
+            xx = xx - _bmul(eps, mask)
             f(fx1, x1)
             f(fx, xx)
             ncalls += 2
@@ -70,8 +100,8 @@ def jacobian(f, x, colorvec, pattern, fdtype="forward", relstep=None, absstep=No
             for j in np.nonzero(mask)[0]:
                 rows = np.nonzero(pattern[:, j])[0]
                 J[rows, j] = d[rows]
-            x1 = x1 - eps * mask
-            xx = xx + eps * mask
+            x1 = x1 - _bmul(eps, mask)
+            xx = xx + _bmul(eps, mask)
     else:
         eps = EPS                                                # :624
         cx1 = x1.astype(np.complex128)
@@ -136,11 +166,11 @@ def jacobian_complex_x(f, x, colorvec, pattern=None, fdtype="forward", relstep=N
             x1[i] = save
             continue
         mask = (colorvec == c)
-        x2 = x1 * mask
-        eps = compute_epsilon(fdtype, np.sqrt(np.linalg.norm(x2)), relstep, absstep, dir)
-        x1 = x1 + eps * mask
+        x2 = _bmul(x1, mask)
+        eps = compute_epsilon(fdtype, np.sqrt(norm(x2, relstep, absstep)), relstep, absstep, dir)
+        x1 = x1 + _bmul(eps, mask)
         if fdtype == "central":
-            xx = xx - eps * mask
+            xx = xx - _bmul(eps, mask)
             f(fx1, x1)
             f(fx, xx)
             ncalls += 2
@@ -152,7 +182,7 @@ def jacobian_complex_x(f, x, colorvec, pattern=None, fdtype="forward", relstep=N
         for j in np.nonzero(mask)[0]:
             rows = np.nonzero(pattern[:, j])[0]
             J[rows, j] = d[rows]
-        x1 = x1 - eps * mask
+        x1 = x1 - _bmul(eps, mask)
         if fdtype == "central":
-            xx = xx + eps * mask
+            xx = xx + _bmul(eps, mask)
     return J, ncalls

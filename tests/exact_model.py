@@ -1,0 +1,168 @@
+"""Exact host model of what the storing kernels promise (csrc/fdjac_builtin_f.hip, include/fdjac_device.h): the BITS of the plain
+colour-by-colour evaluation of src/jacobians.jl:537-622, restated in vectorised numpy independently of the library.  Test
+infrastructure only.
+
+  step sizes   the masked sums of squares in the defined order (eps_order.masked_sumsq), then the step rule in the element type:
+               max(relstep * abs(sqrt(norm)), absstep) [* dir] with Julia's NaN-propagating max; a colour whose plain sum overflowed,
+               or underflowed while the relative term can still exceed absstep, takes the scaled norm sqrt(sum (x 2^-+600)^2) 2^+-600
+               (its summation order is not defined: such step sizes are checked against mpmath, not bit for bit)
+  points       colour c: the plus point is x + eps_c on the colour's coordinates and x + copysign(0, eps_c) elsewhere (Julia's
+               eps * false); forward differences subtract f(x), central ones f at x - eps_c mask_c (x - copysign(0, eps_c) elsewhere)
+  values       f in the element type, in the fixture's own operation order (csrc: tridiag_row, stencil5_row), the IEEE difference,
+               the IEEE quotient by eps_c (central: by 2 eps_c)
+  layout       CSC nzval, BandedMatrix data, Tridiagonal dl / d / du; uncoloured columns hold 0
+
+The reference's in-place un-perturbation (x1 - eps mask after every colour) is NOT modelled: every colour starts from x."""
+import numpy as np
+
+import eps_order
+
+F64 = np.float64
+
+
+def default_relstep(fdtype, dtype=F64):
+    e = np.finfo(dtype).eps
+    return float(np.sqrt(np.dtype(dtype).type(e))) if fdtype == "forward" else float(np.cbrt(np.dtype(dtype).type(e)))
+
+
+def rescale_exp(t, relstep, absstep, dtype=F64):
+    """The exponent k of the scaled fallback (csrc/fdjac_internal.h, eps_rescale_exp), or 0: the plain sum stands."""
+    if np.dtype(dtype) != np.dtype(F64):
+        return 0                       # Float32 elements are summed in Float64: neither over- nor underflow can happen
+    if t == np.inf:
+        return -600
+    if t < 2.0 ** -960 and absstep < relstep * 2.0 ** -240:
+        return 600
+    return 0
+
+
+def jl_max(a, b):
+    return a if (a > b or a != a) else b
+
+
+def epsilons(x, colors0, C, fdtype, relstep=None, absstep=None, dir=1.0, dtype=F64):
+    """(eps[C] in the element type, scaled[C]: the colour took the scaled fallback).  colors0: 0-based, < 0 = no colour."""
+    T = np.dtype(dtype).type
+    relstep = default_relstep(fdtype, dtype) if relstep is None else float(relstep)
+    absstep = relstep if absstep is None else float(absstep)
+    x = np.asarray(x, dtype=dtype)
+    colors0 = np.asarray(colors0)
+    with np.errstate(all="ignore"):
+        tot = eps_order.masked_sumsq(x, colors0, C, dtype)
+        out = np.empty(C, dtype=dtype)
+        scaled = np.zeros(C, bool)
+        for c in range(C):
+            k = rescale_exp(tot[c], relstep, absstep, dtype)
+            if k:
+                y = x[colors0 == c].astype(F64) * 2.0 ** k
+                nrm = np.sqrt(np.dot(y, y)) * 2.0 ** -k
+                scaled[c] = True
+            else:
+                nrm = np.sqrt(tot[c])
+            xs = np.abs(np.sqrt(T(nrm)))
+            e = jl_max(T(relstep) * xs, T(absstep))
+            if fdtype == "forward":
+                e = e * T(dir)
+            out[c] = e
+    return out, scaled
+
+
+# ---- the fixtures, in the operation order of csrc (every neighbour outside the domain is 0) ----
+def tridiag_f(x, nl):
+    T = x.dtype.type
+    z = np.zeros(1, x.dtype)
+    xm = np.concatenate([z, x[:-1]])
+    xp = np.concatenate([x[1:], z])
+    v = (xm - T(2) * x) + xp
+    if nl:
+        v = v + (x * x) * xp
+    return v
+
+
+def stencil5_f(x, nx, ny, nl):
+    T = x.dtype.type
+    g = x.reshape(ny, nx)
+    z = np.zeros_like(g)
+    w = z.copy(); w[:, 1:] = g[:, :-1]
+    e = z.copy(); e[:, :-1] = g[:, 1:]
+    s = z.copy(); s[1:, :] = g[:-1, :]
+    n = z.copy(); n[:-1, :] = g[1:, :]
+    v = (((w + e) + s) + n) - T(4) * g
+    if nl:
+        v = v + (g * g) * e
+    return v.reshape(-1)
+
+
+def fixture(family, *prm):
+    """f(x) -> f(x) in x's dtype, for the rational built-in families."""
+    if family in ("tridiag", "tridiag_nl"):
+        return lambda x: tridiag_f(x, family == "tridiag_nl")
+    if family in ("lap5", "lap5_nl"):
+        nx, ny = prm
+        return lambda x: stencil5_f(x, nx, ny, family == "lap5_nl")
+    raise ValueError(family)
+
+
+def colour_values(f, x, colors0, C, eps, fdtype):
+    """D[c][r]: the value the plain evaluation stores for row r in a column of colour c."""
+    x = np.asarray(x)
+    T = x.dtype.type
+    D = np.empty((C, x.size), dtype=x.dtype)
+    with np.errstate(all="ignore"):
+        base = f(x) if fdtype == "forward" else None
+        for c in range(C):
+            e = T(eps[c])
+            z = np.copysign(T(0), e)
+            m = colors0 == c
+            xp = np.where(m, x + e, x + z)
+            if fdtype == "forward":
+                D[c] = (f(xp) - base) / e
+            else:
+                xm = np.where(m, x - e, x - z)
+                D[c] = (f(xp) - f(xm)) / (T(2) * e)
+    return D
+
+
+def to_csc(D, colors0, colptr, rowval):
+    """nzval of a 1-based CSC pattern: entry (r, j) holds D[colour of j][r], 0 for an uncoloured column."""
+    colptr = np.asarray(colptr) - 1
+    rows = np.asarray(rowval) - 1
+    cols = np.repeat(np.arange(colptr.size - 1), np.diff(colptr))
+    c = np.asarray(colors0)[cols]
+    out = np.zeros(rows.size, D.dtype)
+    ok = c >= 0
+    out[ok] = D[c[ok], rows[ok]]
+    return out
+
+
+def to_banded(D, colors0, M, N, l, u):
+    """BandedMatrix data, column-major (l + u + 1) x N: data[u + i - j, j] = J[i, j]; slots outside the matrix hold 0."""
+    out = np.zeros((l + u + 1, N), D.dtype)
+    colors0 = np.asarray(colors0)
+    for b in range(l + u + 1):
+        j = np.arange(N)
+        i = j + b - u
+        ok = (i >= 0) & (i < M) & (colors0 >= 0)
+        out[b, j[ok]] = D[colors0[j[ok]], i[ok]]
+    return out.T.reshape(-1)
+
+
+def to_tridiagonal(D, colors0, N):
+    """Tridiagonal (dl, d, du): dl[j] = J[j + 1, j], d[j] = J[j, j], du[j] = J[j, j + 1]."""
+    colors0 = np.asarray(colors0)
+
+    def take(i, j):
+        out = np.zeros(i.size, D.dtype)
+        ok = colors0[j] >= 0
+        out[ok] = D[colors0[j[ok]], i[ok]]
+        return out
+    j = np.arange(N)
+    return take(j[:-1] + 1, j[:-1]), take(j, j), take(j[:-1], j[:-1] + 1)
+
+
+def same_bits(got, want):
+    """Bit-equal, except that a NaN matches any NaN (payloads are not part of the promise)."""
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.dtype == want.dtype and got.shape == want.shape, (got.dtype, want.dtype, got.shape, want.shape)
+    it = np.uint64 if got.dtype == np.float64 else np.uint32
+    return (got.view(it) == want.view(it)) | (np.isnan(got) & np.isnan(want))

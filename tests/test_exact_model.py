@@ -1,0 +1,236 @@
+"""The exact host model (tests/exact_model.py) tied to the reference: it agrees with the C and numpy oracles on ordinary inputs at the
+oracles' tolerance, its step sizes are within 4 ulps of an mpmath evaluation of max(relstep * sqrt(||x_c||_2), absstep) * dir at the
+edges of the range (overflowing / underflowing sums of squares, subnormals, NaN / Inf coordinates), and the oracles take the same
+edge semantics (NaN propagates through the step rule, the scaled norm where the plain sum leaves the range).  CPU only."""
+import numpy as np
+import pytest
+
+import exact_model as X
+from finitediff_jl_amd import patterns as P
+from oracle import np_oracle
+
+mpmath = pytest.importorskip("mpmath")
+
+
+def _mp_eps(x, colors0, c, fdtype, relstep, absstep, dir, dtype):
+    """max(relstep * sqrt(||x_c||), absstep) [* dir] in 200-bit arithmetic, rounded to the element type -- the norm too, as the
+    reference holds it (tmp = norm(x2) is an element-type value, src/jacobians.jl:560: a subnormal norm keeps a subnormal's bits)."""
+    mp = mpmath.mp
+    mp.prec = 200
+    v = [mpmath.mpf(float(t)) for t in np.asarray(x)[np.asarray(colors0) == c]]
+    if any(mpmath.isnan(t) for t in v):
+        return np.dtype(dtype).type(np.nan)
+    nrm = mpmath.mpf(float(np.dtype(dtype).type(float(mpmath.sqrt(mpmath.fsum([t * t for t in v]))))))
+    a = mpmath.mpf(float(np.dtype(dtype).type(relstep))) * mpmath.sqrt(nrm)
+    e = max(a, mpmath.mpf(float(np.dtype(dtype).type(absstep))))
+    if fdtype == "forward":
+        e = e * dir
+    return np.dtype(dtype).type(float(e))
+
+
+def _ulps(a, b, dtype):
+    it = np.int64 if np.dtype(dtype) == np.float64 else np.int32
+    ia, ib = np.asarray([a], dtype).view(it)[0], np.asarray([b], dtype).view(it)[0]
+    return abs(int(ia) - int(ib))
+
+
+def _edge_vector(case, N, C, rng, dtype):
+    x = (rng.random(N) + 0.5).astype(dtype)
+    c = np.arange(N) % C
+    if case == "huge_1e240":
+        x[c == 1] = 1e240 * (rng.random(int((c == 1).sum())) + 0.5)
+    elif case == "huge_range":
+        k = np.nonzero(c == 0)[0]
+        x[k] = 10.0 ** rng.uniform(154, 300, k.size) * np.where(rng.random(k.size) < 0.5, -1, 1)
+    elif case == "tiny_1e-200":
+        x[c == 2] = 1e-200 * (rng.random(int((c == 2).sum())) + 0.5)
+    elif case == "subnormal":
+        x[c == 1] = 5e-324 * rng.integers(1, 1000, int((c == 1).sum()))
+    elif case == "float32_huge":
+        x[c == 0] = 1e36 * (rng.random(int((c == 0).sum())) + 0.1)      # (squares far past FLT_MAX, the norm inside the range)
+    elif case == "float32_subnormal":
+        x[c == 2] = 1.4e-45 * rng.integers(1, 1000, int((c == 2).sum()))
+    return x.astype(dtype), c
+
+
+EDGE = [("ordinary", np.float64, None), ("huge_1e240", np.float64, None), ("huge_range", np.float64, None),
+        ("tiny_1e-200", np.float64, 0.0), ("subnormal", np.float64, 0.0), ("subnormal", np.float64, None),
+        ("ordinary", np.float32, None), ("float32_huge", np.float32, None), ("float32_subnormal", np.float32, 0.0)]
+
+
+@pytest.mark.parametrize("fdtype", ["forward", "central"])
+@pytest.mark.parametrize("case,dtype,absstep", EDGE)
+@pytest.mark.parametrize("N,C", [(5, 3), (1000, 3), (70_001, 5)])
+def test_model_eps_within_4_ulps_of_mpmath(fdtype, case, dtype, absstep, N, C):
+    rng = np.random.default_rng(N + C)
+    x, c = _edge_vector(case, N, C, rng, dtype)
+    rel = X.default_relstep(fdtype, dtype)
+    for dir in ((1.0, -1.0) if fdtype == "forward" else (1.0,)):
+        eps, scaled = X.epsilons(x, c, C, fdtype, absstep=absstep, dir=dir, dtype=dtype)
+        if case in ("huge_1e240", "huge_range", "tiny_1e-200") and dtype == np.float64 and N > 5:
+            assert scaled.any(), case          # the case reaches the fallback
+        for k in range(C):
+            want = _mp_eps(x, c, k, fdtype, rel, rel if absstep is None else absstep, dir, dtype)
+            assert np.isfinite(eps[k]), (case, k)
+            assert _ulps(eps[k], want, dtype) <= 4, (case, k, eps[k], want)
+
+
+def test_model_eps_nan_and_inf_coordinates():
+    # one NaN, one +Inf and one -Inf coordinate, each in its own colour: NaN propagates (Julia's max), an infinite coordinate gives
+    # an infinite step size; the other colours keep theirs
+    N, C = 1000, 5
+    x = np.random.default_rng(3).random(N) + 0.5
+    c = np.arange(N) % C
+    x[10] = np.nan        # colour 0
+    x[21] = np.inf        # colour 1
+    x[42] = -np.inf       # colour 2
+    clean = x.copy()
+    clean[[10, 21, 42]] = 1.0
+    for fdtype in ("forward", "central"):
+        eps, _ = X.epsilons(x, c, C, fdtype)
+        ref, _ = X.epsilons(clean, c, C, fdtype)
+        assert np.isnan(eps[0]) and eps[1] == np.inf and eps[2] == np.inf
+        assert np.array_equal(eps[3:], ref[3:])
+        for k in range(C):
+            assert np.isnan(np_oracle.compute_epsilon(fdtype, np.sqrt(np_oracle.norm(np.where(c == k, x, 0.0), 1e-8, 1e-8)), 1e-8, 1e-8)) == (k == 0)
+
+
+def test_model_plain_sum_is_the_defined_order():
+    # at ordinary magnitudes the model's step sizes are those of eps_order (the device's defined summation order), bit for bit
+    import eps_order
+    rng = np.random.default_rng(1)
+    for N, C in ((1, 1), (129, 3), (300_001, 9)):
+        x = rng.random(N) - 0.5
+        c = np.arange(N) % C
+        for fdtype in ("forward", "central"):
+            eps, scaled = X.epsilons(x, c, C, fdtype)
+            assert not scaled.any()
+            assert np.array_equal(eps, eps_order.epsilons(x, c, C, fdtype))
+
+
+def _oracle_run(oracle, fam, prm, x, colors, fdtype, colptr, rowval, dtype=np.float64, **kw):
+    return oracle.jacobian(fdtype, oracle.Fixture(fam, *prm, dtype=dtype), x, colors, kind=oracle.PAT_CSC_COMMON, colptr=colptr,
+                           rowval=rowval, **kw)["out"]
+
+
+@pytest.mark.parametrize("fdtype", ["forward", "central"])
+@pytest.mark.parametrize("fam,prm", [("tridiag", (1,)), ("tridiag_nl", (2,)), ("tridiag_nl", (1025,)), ("tridiag", (40_000,)),
+                                     ("lap5", (6, 5)), ("lap5_nl", (64, 40)), ("lap5_nl", (254, 3))])
+def test_model_agrees_with_the_c_oracle(oracle, fdtype, fam, prm):
+    rng = np.random.default_rng(sum(prm))
+    if fam.startswith("tridiag"):
+        N = prm[0]
+        colptr, rowval = P.tridiag_csc(N)
+        colors = P.cyclic_colors(N, min(3, N) if N > 1 else 1)
+    else:
+        N = prm[0] * prm[1]
+        colptr, rowval = P.lap5_csc(*prm)
+        colors = P.lap5_colors(*prm)
+    x = rng.random(N)
+    c0 = colors - 1
+    C = int(colors.max())
+    for dir in ((1.0, -1.0) if fdtype == "forward" else (1.0,)):
+        eps, _ = X.epsilons(x, c0, C, fdtype, dir=dir)
+        D = X.colour_values(X.fixture(fam, *prm), x, c0, C, eps, fdtype)
+        got = X.to_csc(D, c0, colptr, rowval)
+        ref = _oracle_run(oracle, fam, prm, x, colors, fdtype, colptr, rowval, dir=dir)
+        # the oracle's later colours see x drifted by the in-place un-perturbation: the existing tolerance (test_gpu_parity._tol_ok)
+        atol = 16 * np.finfo(np.float64).eps * 8.0 / np.min(np.abs(eps))
+        assert np.all(np.abs(got - ref) <= 1e-6 * np.abs(ref) + atol), (fam, prm, fdtype, np.max(np.abs(got - ref)))
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_model_agrees_with_the_float32_and_float64_oracles_on_storage_layouts(oracle, dtype):
+    # the Banded and Tridiagonal layouts hold the CSC values at their slots
+    N = 1000
+    x = np.random.default_rng(4).random(N).astype(dtype)
+    colors = P.cyclic_colors(N, 3)
+    c0 = colors - 1
+    colptr, rowval = P.tridiag_csc(N)
+    eps, _ = X.epsilons(x, c0, 3, "central", dtype=dtype)
+    D = X.colour_values(X.fixture("tridiag_nl", N), x, c0, 3, eps, "central")
+    csc = X.to_csc(D, c0, colptr, rowval)
+    dense = P.csc_to_dense(N, N, colptr, rowval, csc)
+    band = X.to_banded(D, c0, N, N, 1, 1).reshape(N, 3)
+    dl, d, du = X.to_tridiagonal(D, c0, N)
+    assert np.array_equal(band[:, 1], np.diag(dense)) and np.array_equal(band[1:, 0], np.diag(dense, 1))
+    assert np.array_equal(band[:-1, 2], np.diag(dense, -1)) and band[0, 0] == 0 and band[-1, 2] == 0
+    assert np.array_equal(dl, np.diag(dense, -1)) and np.array_equal(d, np.diag(dense)) and np.array_equal(du, np.diag(dense, 1))
+    ref = _oracle_run(oracle, "tridiag_nl", (N,), x, colors, "central", colptr, rowval, dtype=dtype)
+    tol = (1e-6, 1e-6) if dtype == np.float64 else (1e-3, 1e-2)
+    assert np.all(np.abs(csc.astype(np.float64) - ref) <= tol[0] * np.abs(ref) + tol[1])
+
+
+@pytest.mark.parametrize("fdtype", ["forward", "central"])
+@pytest.mark.parametrize("case,absstep", [("huge_1e240", None), ("huge_range", None), ("tiny_1e-200", 0.0)])
+def test_oracles_take_the_scaled_norm(oracle, fdtype, case, absstep):
+    # before the fallback, the oracles' plain sum of squares overflowed (eps = Inf: every value of the colour NaN) or flushed the
+    # squares (eps = absstep); now both give the model's values within their tolerance.  tridiag (linear): J = -2 / 1 wherever
+    # x + eps does not absorb eps
+    N, C = 3000, 3
+    x, c0 = _edge_vector(case, N, C, np.random.default_rng(9), np.float64)
+    colors = c0 + 1
+    colptr, rowval = P.tridiag_csc(N)
+    eps, scaled = X.epsilons(x, c0, C, fdtype, absstep=absstep)
+    assert scaled.any()
+    D = X.colour_values(X.fixture("tridiag_nl", N), x, c0, C, eps, fdtype)
+    want = X.to_csc(D, c0, colptr, rowval)
+    ref = _oracle_run(oracle, "tridiag_nl", (N,), x, colors, fdtype, colptr, rowval, absstep=absstep)
+    assert np.all(np.isfinite(ref)) == np.all(np.isfinite(want))
+    fin = np.isfinite(want)
+    assert np.all(np.abs(ref[fin] - want[fin]) <= 1e-6 * np.abs(want[fin]) + 1e-6 * np.max(np.abs(want[fin])))
+    A = P.csc_to_dense(N, N, colptr, rowval, np.ones(rowval.size)).astype(bool)
+    rel = X.default_relstep(fdtype)
+    Jn, _ = np_oracle.jacobian(lambda fx, xx: fx.__setitem__(slice(None), X.tridiag_f(xx, True)), x, colors, A, fdtype,
+                               relstep=rel, absstep=rel if absstep is None else absstep)
+    got_n = Jn[rowval - 1, np.repeat(np.arange(N), np.diff(colptr))]
+    assert np.all(np.isfinite(got_n) == np.isfinite(want))
+    assert np.all(np.abs(got_n[fin] - want[fin]) <= 1e-6 * np.abs(want[fin]) + 1e-6 * np.max(np.abs(want[fin])))
+
+
+@pytest.mark.parametrize("fdtype", ["forward", "central"])
+def test_float32_oracles_take_the_scaled_norm_without_overflow(oracle, fdtype):
+    # Float32 elements: the oracles' fallback sums in double WITHOUT scaling (a float's square cannot leave double's range; 2^600
+    # would overflow it).  One colour holds a single tiny coordinate, the rest are 0, absstep = 0: the step sizes stay finite and no
+    # value turns NaN (a step of Inf would poison every later colour through x1 - Inf * mask).
+    N = 30
+    colors = P.cyclic_colors(N, 3)
+    x = (np.random.default_rng(2).random(N) + 0.5).astype(np.float32)
+    x[colors == 2] = 0.0
+    x[4] = np.float32(2.0 ** -61)             # colour 2 (0-based 1): its only non-zero coordinate
+    colptr, rowval = P.tridiag_csc(N)
+    ref = _oracle_run(oracle, "tridiag_nl", (N,), x, colors, fdtype, colptr, rowval, dtype=np.float32, absstep=0.0)
+    assert not np.isnan(ref).any()
+    eps, scaled = X.epsilons(x, colors - 1, 3, fdtype, absstep=0.0, dtype=np.float32)
+    assert np.isfinite(eps).all() and (eps > 0).all()
+    for v, absstep in ((1e30, None), (1e-30, 0.0), (3e38, None), (1.4e-45, 0.0)):
+        y = np.zeros(8, np.float32)
+        y[0] = v
+        rel = 1e-4
+        got = np_oracle.norm(y, rel, rel if absstep is None else absstep)
+        assert got == np.float64(np.float32(v)), (v, got)
+
+
+def test_oracles_nan_coordinate_poisons_only_its_colour(oracle):
+    # Julia's Bool is a strong zero (x * false == 0 even for NaN): a NaN in the LAST colour gives that colour a NaN step and NaN
+    # columns, and leaves the earlier colours' values finite in both oracles (no later colour for the in-place un-perturbation to reach)
+    N, C = 300, 3
+    x = np.random.default_rng(5).random(N) + 0.5
+    x[2] = np.nan                              # colour 3
+    colors = P.cyclic_colors(N, C)
+    colptr, rowval = P.tridiag_csc(N)
+    cols = np.repeat(np.arange(N), np.diff(colptr))
+    A = P.csc_to_dense(N, N, colptr, rowval, np.ones(rowval.size)).astype(bool)
+    rows_nan = np.zeros(N, bool)
+    rows_nan[1:4] = True                       # the rows x[2] enters
+    for fdtype in ("forward", "central"):
+        ref = _oracle_run(oracle, "tridiag_nl", (N,), x, colors, fdtype, colptr, rowval)
+        Jn, _ = np_oracle.jacobian(lambda fx, xx: fx.__setitem__(slice(None), X.tridiag_f(xx, True)), x, colors, A, fdtype)
+        got_n = Jn[rowval - 1, cols]
+        for out in (ref, got_n):
+            last = colors[cols] == C
+            assert np.isnan(out[last]).all()
+            # earlier colours: NaN only in the rows x[2] itself enters (f(x) there is NaN), finite everywhere else
+            other = ~last & ~(rows_nan[rowval - 1] & (fdtype == "forward"))
+            other &= ~rows_nan[rowval - 1]
+            assert np.isfinite(out[other]).all()

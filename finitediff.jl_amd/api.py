@@ -1743,3 +1743,199 @@ def finite_difference_jacobian(f, x, cache_or_fdtype="forward", returntype=np.fl
     finite_difference_jacobian_b(J, f, x, cache_or_fdtype, returntype, f_in, relstep=relstep, absstep=absstep,
                                  colorvec=colorvec, sparsity=sp if sp is not None else "default", dir=dir, ctx=ctx)
     return J
+
+
+# ----------------------------------------------------------------------------------------------
+# Hessian / gradient of a partially separable objective f(x) = sum_r phi_r(x)
+# (src/hessians.jl:202-292, src/gradients.jl:407-446; include/fdjac.h fd_objective_compile / fd_hessian / fd_gradient)
+# ----------------------------------------------------------------------------------------------
+class ObjectiveF:
+    """An objective f(x) = sum_{r<M} phi_r(x) given as SOURCE (fd_objective_compile): `source` defines a functor type `name` with
+        template <class P> __device__ real_t operator()(long long r, const P &X) const     // phi_r at the point X, X(j) = coordinate j
+    -- the source contract of ``JitF``: a row functor written for a Jacobian serves as it is.  `params` = the functor object's bytes.
+    Float64 only.  ``launches``: launches of its kernels so far (2 per Hessian and forward gradient, 1 per central gradient)."""
+
+    def __init__(self, source, name, M, N, params=b"", ctx=None):
+        self.ctx = ctx or Context.default()
+        L = self.L = self.ctx.L
+        self.handle = C.c_void_p()
+        params = bytes(params)
+        buf = C.create_string_buffer(params, len(params)) if params else None
+        rc = L.fd_objective_compile(self.ctx.handle, source.encode(), name.encode(), buf, len(params), int(M), int(N), C.byref(self.handle))
+        self.log = (L.fd_f_compile_log() or b"").decode("utf-8", "replace")
+        _l.check(rc)
+        self.M, self.N = int(M), int(N)
+        self._fin = weakref.finalize(self, L.fd_objective_destroy, self.handle)
+
+    @property
+    def launches(self):
+        n = C.c_int64()
+        _l.check(self.L.fd_objective_counts(self.handle, C.byref(n)))
+        return n.value
+
+
+_HESS_DESTS = {"dense": _l.HESS_DENSE, "csc": _l.HESS_CSC, "banded": _l.HESS_BANDED}
+
+
+def _support_bandwidth(S):
+    """P's half-bandwidth from S alone: the widest row (last column - first column)."""
+    cp, rv = np.asarray(S.colptr, np.int64) - 1, np.asarray(S.rowval, np.int64) - 1
+    if rv.size == 0:
+        return 0
+    cols = np.repeat(np.arange(int(S.n), dtype=np.int64), np.diff(cp))
+    lo = np.full(int(S.m), np.iinfo(np.int64).max)
+    hi = np.full(int(S.m), -1)
+    np.minimum.at(lo, rv, cols)
+    np.maximum.at(hi, rv, cols)
+    used = hi >= 0
+    return int((hi[used] - lo[used]).max())
+
+
+class _ObjectiveCache:
+    """The plan of one support pattern S (fd_hess_plan).  sparsity=None: dense support (every row reads every coordinate; with M = 1
+    the reference's setting) -- M is then the objective's, and the plan is made on first use."""
+
+    def __init__(self, x, sparsity, dest, band, M, ctx):
+        self.n = int(np.prod(x.shape))
+        self.sparsity, self.dest, self.ctx = sparsity, dest, ctx
+        if sparsity is not None and (int(sparsity.n) != self.n):
+            raise ValueError("sparsity has %d columns, x has %d elements" % (int(sparsity.n), self.n))
+        if dest not in _HESS_DESTS:
+            raise ValueError("dest must be one of %s" % sorted(_HESS_DESTS))
+        if dest == "banded" and band is None:
+            band = _support_bandwidth(sparsity) if sparsity is not None else self.n - 1
+        self.band = 0 if band is None else int(band)
+        self.M = int(sparsity.m) if sparsity is not None else (None if M is None else int(M))
+        self._plan = None
+        if self.M is not None:
+            self._make_plan(self.M)
+
+    def _make_plan(self, M):
+        ctx = self.ctx or Context.default()
+        L = ctx.L
+        h = C.c_void_p()
+        if self.sparsity is not None:
+            cp, rv = _i64(self.sparsity.colptr), _i64(self.sparsity.rowval)
+            _l.check(L.fd_hess_plan_create(ctx.handle, M, self.n, cp.ctypes.data, rv.ctypes.data, 8, 1, _HESS_DESTS[self.dest], self.band, C.byref(h)))
+        else:
+            _l.check(L.fd_hess_plan_create(ctx.handle, M, self.n, None, None, 8, 1, _HESS_DESTS[self.dest], self.band, C.byref(h)))
+        self.M, self.ctx, self.L, self.handle = int(M), ctx, L, h
+        self._plan = weakref.finalize(self, L.fd_hess_plan_destroy, h)
+
+    def _plan_for(self, f):
+        if self._plan is None:
+            self._make_plan(f.M)
+        return self.handle
+
+    def info(self, key):
+        if self._plan is None:
+            raise RuntimeError("the plan of a dense-support cache is made on first use (or pass M=)")
+        v = C.c_int64()
+        _l.check(self.L.fd_hess_plan_info(self.handle, int(key), C.byref(v)))
+        return v.value
+
+    def pattern(self):
+        """P = pattern(S^T S) as the plan built it: a host ``SparseMatrixCSC`` (1-based, nzval None)."""
+        nnz = self.info(_l.HESS_INFO_NNZ)
+        cp, rv = np.zeros(self.n + 1, np.int64), np.zeros(max(nnz, 1), np.int64)
+        _l.check(self.L.fd_hess_plan_pattern(self.handle, cp.ctypes.data, rv.ctypes.data))
+        return SparseMatrixCSC(self.n, self.n, cp + 1, rv[:nnz] + 1)
+
+
+class HessianCache(_ObjectiveCache):
+    """HessianCache (src/hessians.jl:1-60) of a partially separable objective on its support pattern `sparsity` (M x N
+    ``SparseMatrixCSC``; None = dense support).  `dest`: "dense" (N x N), "csc" (nzval of ``pattern()``) or "banded" (BandedMatrix
+    data (2 band + 1) x N, band >= P's half-bandwidth, default: P's) -- the storage H is written into; slots outside P hold +0.0."""
+
+    def __init__(self, x, sparsity=None, dest="dense", band=None, M=None, ctx=None):
+        super().__init__(x, sparsity, dest, band, M, ctx)
+
+
+class GradientCache(_ObjectiveCache):
+    """GradientCache (src/gradients.jl:1-100) of a partially separable objective: fdtype "forward" or "central" (the complex step is
+    not supported: FD_ERR_UNSUPPORTED), `sparsity` as for ``HessianCache``."""
+
+    def __init__(self, x, fdtype="forward", sparsity=None, M=None, ctx=None):
+        self.fdtype = _norm_fdtype(fdtype)
+        super().__init__(x, sparsity, "dense", None, M, ctx)
+
+
+def _steps(relstep, absstep):
+    return (-1.0 if relstep is None else float(relstep)), (-1.0 if absstep is None else float(absstep))
+
+
+def _sym_ptr(a, what):
+    """(pointer, kind, keepalive) of a float64 array whose memory order does not matter (a symmetric dense H)."""
+    if _is_torch(a):
+        import torch
+        if a.dtype != torch.float64 or not (a.is_contiguous() or _colmajor_contig(a)):
+            raise TypeError("%s must be a contiguous float64 tensor" % what)
+        return (a.data_ptr(), _l.DEVICE, a) if a.is_cuda else (a.numpy().ctypes.data, _l.HOST, a)
+    if not isinstance(a, np.ndarray) or a.dtype != np.float64 or not (a.flags.c_contiguous or a.flags.f_contiguous):
+        raise TypeError("%s must be a contiguous float64 numpy array or torch tensor" % what)
+    return a.ctypes.data, _l.HOST, a
+
+
+def finite_difference_hessian_b(H, f, x, cache, *, relstep=None, absstep=None):
+    """``FiniteDiff.finite_difference_hessian!(H, f, x, cache; relstep, absstep)`` (src/hessians.jl:202-292) for an ``ObjectiveF``.
+    H: the cache's destination -- a float64 N x N array (dense), a ``SparseMatrixCSC`` of ``cache.pattern()`` or its nzval (csc), a
+    ``BandedMatrix`` or its data (banded).  Host numpy or device torch arrays; x and H both on the device: enqueued on the context's
+    stream (fd_hessian_async), otherwise synchronous.  relstep None: eps^(1/4); absstep None: relstep."""
+    plan = cache._plan_for(f)
+    L = cache.L
+    vals = H.nzval if isinstance(H, SparseMatrixCSC) else (H.data if isinstance(H, BandedMatrix) else H)
+    rs, ab = _steps(relstep, absstep)
+    xp, xk, _kx = _ptr(x, "x")
+    hp, hk, _kh = _sym_ptr(vals, "H") if cache.dest == "dense" else _ptr(vals, "H")
+    n_out = cache.info(_l.HESS_INFO_OUT_LEN)
+    if int(np.prod(vals.shape)) != n_out:
+        raise ValueError("H has %d elements, the %s destination needs %d" % (int(np.prod(vals.shape)), cache.dest, n_out))
+    if xk == _l.DEVICE and hk == _l.DEVICE:
+        _l.check(L.fd_hessian_async(plan, f.handle, xp, rs, ab, hp))
+    else:
+        _l.check(L.fd_hessian(plan, f.handle, xp, xk, rs, ab, hp, hk))
+    return None
+
+
+def finite_difference_hessian(f, x, cache=None, *, relstep=None, absstep=None):
+    """``FiniteDiff.finite_difference_hessian(f, x, cache)``: H allocated in the cache's destination on x's side (host / device)."""
+    cache = cache or HessianCache(x)
+    cache._plan_for(f)
+    n = cache.n
+    if cache.dest == "csc":
+        P = cache.pattern()
+        H = SparseMatrixCSC(n, n, P.colptr, P.rowval, _similar(x, P.rowval.size))
+    elif cache.dest == "banded":
+        w = 2 * cache.band + 1
+        H = BandedMatrix(_similar(x, w * n).reshape(n, w).T if _is_torch(x) else np.zeros((w, n), order="F"), n, cache.band, cache.band)
+    else:
+        H = _similar(x, n * n).reshape(n, n)
+    finite_difference_hessian_b(H, f, x, cache, relstep=relstep, absstep=absstep)
+    return H
+
+
+def finite_difference_gradient_b(df, f, x, cache, *, relstep=None, absstep=None, dir=True):
+    """``FiniteDiff.finite_difference_gradient!(df, f, x, cache; relstep, absstep, dir)`` (src/gradients.jl:407-446) for an
+    ``ObjectiveF``: forward (step times dir) or central differences, host numpy or device torch arrays (both on the device:
+    enqueued on the context's stream)."""
+    plan = cache._plan_for(f)
+    L = cache.L
+    rs, ab = _steps(relstep, absstep)
+    xp, xk, _kx = _ptr(x, "x")
+    dp, dk, _kd = _ptr(df, "df")
+    if int(np.prod(df.shape)) != cache.n:
+        raise ValueError("df has %d elements, x has %d" % (int(np.prod(df.shape)), cache.n))
+    fdt = _l.FDTYPES[cache.fdtype]
+    if xk == _l.DEVICE and dk == _l.DEVICE:
+        _l.check(L.fd_gradient_async(plan, f.handle, xp, fdt, rs, ab, float(dir), dp))
+    else:
+        _l.check(L.fd_gradient(plan, f.handle, xp, xk, fdt, rs, ab, float(dir), dp, dk))
+    return None
+
+
+def finite_difference_gradient(f, x, cache_or_fdtype="forward", *, relstep=None, absstep=None, dir=True):
+    """``FiniteDiff.finite_difference_gradient(f, x, fdtype_or_cache)``: df allocated on x's side."""
+    cache = cache_or_fdtype if isinstance(cache_or_fdtype, GradientCache) else GradientCache(x, cache_or_fdtype)
+    df = _similar(x, cache.n)
+    finite_difference_gradient_b(df, f, x, cache, relstep=relstep, absstep=absstep, dir=dir)
+    return df

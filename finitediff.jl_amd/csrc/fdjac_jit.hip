@@ -52,6 +52,9 @@ struct Hiprtc {
 static Hiprtc g_rtc;
 static std::mutex g_jit_mutex;
 static thread_local std::string t_log;
+// (fdjac_hessian.hip compiles objectives against the same embedded header and reports through the same fd_f_compile_log)
+const char *jit_device_header() { return kDeviceHeader; }
+void jit_set_compile_log(const char *log) { t_log = log ? log : ""; }
 
 static const Hiprtc *hiprtc()
 {

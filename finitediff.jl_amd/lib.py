@@ -19,6 +19,8 @@ P2P_HANDLE_BYTES = 64
 EPS_COMPUTE, EPS_PRECOMPUTED = 0, 1
 TRI_DIAGONALS, TRI_CSC = 0, 1
 FORWARD, CENTRAL, COMPLEX = 0, 1, 2
+HESS_DENSE, HESS_CSC, HESS_BANDED = 0, 1, 2
+HESS_INFO_NNZ, HESS_INFO_BANDWIDTH, HESS_INFO_UPPER, HESS_INFO_LIST_LEN, HESS_INFO_OUT_LEN = range(5)
 HOST, DEVICE = 0, 1
 FDTYPES = {"forward": FORWARD, "central": CENTRAL, "complex": COMPLEX}
 STAGES = ("eps", "perturb", "f", "decompress", "total", "exchange")
@@ -80,6 +82,8 @@ EXPORTS = (
     "fd_banded_solver_create", "fd_banded_solver_destroy", "fd_banded_solver_set_policy", "fd_banded_solver_status", "fd_banded_solve_async",
     "fd_blocktridiag_solver_create", "fd_blocktridiag_solver_destroy", "fd_blocktridiag_solver_set_policy", "fd_blocktridiag_solver_status",
     "fd_blocktridiag_solve_async",
+    "fd_objective_compile", "fd_objective_destroy", "fd_objective_counts", "fd_hess_plan_create", "fd_hess_plan_destroy",
+    "fd_hess_plan_info", "fd_hess_plan_pattern", "fd_hessian_async", "fd_hessian", "fd_gradient_async", "fd_gradient",
 )
 
 
@@ -276,6 +280,17 @@ def load():
     L.fd_tridiag_solve_async.argtypes = [vp, dbl, dbl, pp, vp, vp, vp]
     L.fd_tridiag_solve_interface.argtypes = [vp, dbl, dbl, pp, vp, vp]
     L.fd_tridiag_solve_finish.argtypes = [vp, dbl, dbl, pp, vp, vp, i32, i32, vp]
+    L.fd_objective_compile.argtypes = [vp, C.c_char_p, C.c_char_p, vp, i64, i64, i64, pp]
+    L.fd_objective_destroy.argtypes = [vp]
+    L.fd_objective_counts.argtypes = [vp, C.POINTER(i64)]
+    L.fd_hess_plan_create.argtypes = [vp, i64, i64, vp, vp, i32, i32, i32, i64, pp]
+    L.fd_hess_plan_destroy.argtypes = [vp]
+    L.fd_hess_plan_info.argtypes = [vp, i32, C.POINTER(i64)]
+    L.fd_hess_plan_pattern.argtypes = [vp, vp, vp]
+    L.fd_hessian_async.argtypes = [vp, vp, vp, dbl, dbl, vp]
+    L.fd_hessian.argtypes = [vp, vp, vp, i32, dbl, dbl, vp, i32]
+    L.fd_gradient_async.argtypes = [vp, vp, vp, i32, dbl, dbl, dbl, vp]
+    L.fd_gradient.argtypes = [vp, vp, vp, i32, i32, dbl, dbl, dbl, vp, i32]
     for name in TYPED:   # the Float32 instantiation has the same prototypes (values behind void*, steps stay double)
         getattr(L, "fd32_" + name[3:]).argtypes = getattr(L, name).argtypes
     for name in EXPORTS:

@@ -230,3 +230,32 @@ def banded_to_dense(data, M, N, l, u):
         for i in range(max(0, j - u), min(M, j + l + 1)):
             A[i, j] = data[u + i - j, j]
     return A
+
+
+def hessian_sparsity(S):
+    """The Hessian pattern of f = sum_r phi_r for the rows' support pattern S (a ``SparseMatrixCSC`` M x N: row r of column j stored
+    <=> phi_r reads x_j): P = pattern(S^T S), N x N, symmetric, rows ascending in every column, the diagonal of every column some row
+    touches -- what ``fd_hess_plan_create`` builds on the device side.  Returns a host ``SparseMatrixCSC`` (1-based, nzval None)."""
+    from .api import SparseMatrixCSC
+    M, N = int(S.m), int(S.n)
+    colptr, rowval = np.asarray(S.colptr, np.int64) - 1, np.asarray(S.rowval, np.int64) - 1
+    cols = np.repeat(np.arange(N, dtype=np.int64), np.diff(colptr))
+    # S by rows: the columns of every row, ascending
+    order = np.lexsort((cols, rowval))
+    r_sorted, c_sorted = rowval[order], cols[order]
+    r_ptr = np.zeros(M + 1, np.int64)
+    np.add.at(r_ptr, r_sorted + 1, 1)
+    np.cumsum(r_ptr, out=r_ptr)
+    # every pair (i, j) of columns of one row: entry k of row r is paired with all L_r entries of that row
+    L = np.diff(r_ptr)
+    per = L[r_sorted]                                          # partners of each stored entry
+    first = np.repeat(r_ptr[r_sorted], per)
+    k = np.arange(int(per.sum()), dtype=np.int64) - np.repeat(np.cumsum(per) - per, per)
+    i = np.repeat(c_sorted, per)
+    j = c_sorted[first + k]
+    key = np.unique(j * N + i)                                 # column-major order: by column j, then row i
+    pj, pi = key // N, key % N
+    pcolptr = np.zeros(N + 1, np.int64)
+    np.add.at(pcolptr, pj + 1, 1)
+    np.cumsum(pcolptr, out=pcolptr)
+    return SparseMatrixCSC(N, N, pcolptr + 1, pi + 1)

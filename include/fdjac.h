@@ -734,6 +734,69 @@ int fd_f_compiled_counts(void *fctx, int64_t *launches);
 int fd_f_compiled_row_stores(void *fctx, int64_t *row_stores);
 const char *fd_f_compile_log(void);
 
+/* ---- Hessian and gradient of a partially separable objective ------------------------------------------------------------------------
+ * finite_difference_hessian! (src/hessians.jl:202-292) and finite_difference_gradient! (src/gradients.jl:407-446, the StridedVector
+ * method) for f(x) = sum_{r=0}^{M-1} phi_r(x), where phi_r reads the coordinates of row r of an M x N support pattern S.  Float64 only.
+ *   fd_objective_compile   phi as SOURCE, the contract of fd_f_compile_rows: a functor type with
+ *                              template <class P> __device__ real_t operator()(long long r, const P &X) const
+ *                          compiled with hiprtc against include/fdjac_device.h (-ffp-contract=off, gfx950), cached by content apart from
+ *                          fd_f_compile_rows' modules.  FD_ERR_ARG + fd_f_compile_log() if it does not compile; FD_ERR_UNSUPPORTED
+ *                          without libhiprtc.  fd_objective_counts: launches of its kernels so far.
+ *   fd_hess_plan_create    S as CSC (colptr / rowval, idx_bytes 4 or 8, idx_base 0 or 1, as fd_plan_create_csc; rows of a column are
+ *                          sorted, duplicates dropped); colptr == rowval == NULL: dense support (every row reads every coordinate --
+ *                          M = 1 with dense S is the reference's setting, f = phi_0).  The Hessian's pattern P = pattern(S^T S)
+ *                          (symmetric, both triangles, ascending rows, the diagonal of every column some row touches) and the rows of
+ *                          every upper entry are built on the host by the first call that needs them.  `dest` (enum fd_hess_dest):
+ *                              FD_HESS_DENSE   H = n x n column-major (the reference's H after copytri!(H, 'U'))
+ *                              FD_HESS_CSC     H = nzval of P (fd_hess_plan_pattern hands P out: SparseMatrixCSC(N, N, colptr, rowval, H))
+ *                              FD_HESS_BANDED  H = BandedMatrix data (2 band + 1) x N as fd_plan_create_banded writes it, l = u = band;
+ *                                              band >= P's half-bandwidth, else FD_ERR_ARG -- what fd_banded_solve_async reads
+ *                          Every slot outside P is written as +0.0.  `band` is ignored by the other destinations.
+ *   fd_hessian_async       hcentral differences (relstep <= 0: eps(Float64)^(1/4) = 2^-13; absstep < 0: absstep = relstep), x and H
+ *                          device pointers, enqueued on the context's stream: ONE launch of the rows pass (phi_r(x), plan scratch) and
+ *                          ONE of the entry pass (a lane per upper entry of P, both slots stored).  e_i = max(relstep |x_i|, absstep)
+ *                          serves the diagonal and the off-diagonal entries; i < j always differences (i, j) and mirrors it (the
+ *                          formula is not bit-symmetric; the reference mirrors the upper triangle).  Sums over rows ascend in r.
+ *   fd_gradient_async      fdtype FD_FORWARD (e_j = max(relstep |x_j|, absstep) * dir, relstep <= 0: sqrt(eps)): the rows pass + ONE
+ *                          launch, a lane per column; FD_CENTRAL (dir ignored, relstep <= 0: cbrt(eps)): that launch alone.
+ *                          FD_COMPLEX: FD_ERR_UNSUPPORTED.  A column no row touches has the empty sum +0.0 before the division.
+ *   fd_hessian / fd_gradient   the same from HOST or DEVICE x and outputs (x_kind / out_kind), synchronous.
+ * With M = 1 and dense S every value is the reference's expression bit for bit (for phi made of + - * / sqrt).  With M > 1 the sums
+ * run over the rows of each entry: equal in exact arithmetic, not bit-equal to differencing the whole f; structural zeros are exact.
+ * NaN STEPS: a NaN coordinate x_k (or a NaN absstep) makes e_k NaN, and exactly the entries whose rows read x_k NaN -- H_kk, the H_ik
+ * with k in the support of some row of rows(i) & rows(k), g_k, and every value whose rows' phi_r read x_k -- as in the reference,
+ * where every entry reads f at the poisoned point.
+ * FD_ERR_SHAPE when the objective's and the plan's M / N differ.  One in-flight call per plan. */
+typedef struct fd_objective fd_objective;
+typedef struct fd_hess_plan fd_hess_plan;
+enum fd_hess_dest { FD_HESS_DENSE = 0, FD_HESS_CSC = 1, FD_HESS_BANDED = 2 };
+enum fd_hess_info_key {
+    FD_HESS_INFO_NNZ = 0,             /* nnz(P) */
+    FD_HESS_INFO_BANDWIDTH = 1,       /* P's half-bandwidth max |i - j| */
+    FD_HESS_INFO_UPPER = 2,           /* upper entries (i <= j) of P: the entry pass's lanes */
+    FD_HESS_INFO_LIST_LEN = 3,        /* total length of the entries' row lists */
+    FD_HESS_INFO_OUT_LEN = 4          /* elements of H for the plan's destination */
+};
+/* src/hessians.jl:202-292 / src/gradients.jl:407-446: the objective f = sum_r phi_r */
+int fd_objective_compile(fd_ctx *ctx, const char *source, const char *functor_type, const void *params, int64_t params_bytes,
+                         int64_t M, int64_t N, fd_objective **out);
+int fd_objective_destroy(fd_objective *obj);
+int fd_objective_counts(fd_objective *obj, int64_t *launches);
+/* HessianCache (src/hessians.jl:1-60) on the support pattern S */
+int fd_hess_plan_create(fd_ctx *ctx, int64_t M, int64_t N, const void *colptr, const void *rowval, int idx_bytes, int idx_base,
+                        int dest, int64_t band, fd_hess_plan **out);
+int fd_hess_plan_destroy(fd_hess_plan *plan);
+int fd_hess_plan_info(const fd_hess_plan *plan, int key, int64_t *value);
+/* P as 0-based host arrays: colptr_out[N + 1], rowval_out[nnz(P)] (either may be NULL) */
+int fd_hess_plan_pattern(const fd_hess_plan *plan, int64_t *colptr_out, int64_t *rowval_out);
+/* finite_difference_hessian!(H, f, x, cache; relstep, absstep): src/hessians.jl:202-292 */
+int fd_hessian_async(fd_hess_plan *plan, fd_objective *obj, const void *x, double relstep, double absstep, void *H);
+int fd_hessian(fd_hess_plan *plan, fd_objective *obj, const void *x, int x_kind, double relstep, double absstep, void *H, int out_kind);
+/* finite_difference_gradient!(df, f, x, cache; relstep, absstep, dir): src/gradients.jl:407-446 */
+int fd_gradient_async(fd_hess_plan *plan, fd_objective *obj, const void *x, int fdtype, double relstep, double absstep, double dir, void *df);
+int fd_gradient(fd_hess_plan *plan, fd_objective *obj, const void *x, int x_kind, int fdtype, double relstep, double absstep, double dir,
+                void *df, int out_kind);
+
 /* Device stream-copy ceiling probe: copies `bytes` device-to-device `iters` times with a
    16 B/lane kernel and returns the achieved GB/s (read + write bytes) -- the measured roofline
    the achieved figures are quoted against. */

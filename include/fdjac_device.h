@@ -1560,6 +1560,128 @@ __global__ void __launch_bounds__(256) fd_bbb_store_cols(F f, const T *__restric
     else { X.minus = MODE == 1 ? 1 : 2; vm = f(r, X); }
     *o = (vp - vm) / (MODE == 1 ? 2 * h : h);
 }
+
+/* ---- partially separable OBJECTIVES: Hessian and gradient (fd_objective_compile / fd_hessian / fd_gradient, csrc/fdjac_hessian.hip) --
+ * f(x) = sum_r phi_r(x), phi given as the row functor of fd_csc_store_cols (T f(long long r, const P &X)), S = the rows' support
+ * pattern (M x N CSC: row r of column j stored <=> phi_r reads x_j).  The reference differences the whole f (src/hessians.jl:202-292,
+ * src/gradients.jl:407-446); here every entry is the sum, over the rows that read its coordinates, of the same differences of phi_r:
+ *   step     e_i = max(relstep |x_i|, absstep), Julia's max (a NaN on either side is the result; src/epsilons.jl:74-77)
+ *   H_ii     (sum_{r in rows(i)}            (phi_r(i+) - 2 phi_r(x)) + phi_r(i-)) / (e_i e_i)
+ *   H_ij     (sum_{r in rows(i) & rows(j)} ((phi_r(i+j+) - phi_r(i+j-)) - phi_r(i-j+)) + phi_r(i-j-)) / ((4 e_i) e_j),  i < j
+ *   g_j      forward (sum_{r in rows(j)} (phi_r(j+) - phi_r(x))) / e_j (e_j times dir), central (sum (phi_r(j+) - phi_r(j-))) / (2 e_j)
+ * each sum left to right in ascending r (an empty one is +0.0).  With M = 1 and dense S these are the reference's operations.
+ * Deterministic: one lane per entry / column, no atomics. */
+template <typename T> __device__ inline T fd_hess_step(T xi, T relstep, T absstep)
+{
+    const T a = relstep * fabs(xi);
+    return (a > absstep || a != a) ? a : absstep;       /* max(a, absstep) as Julia's max (eps_max in csrc/fdjac_internal.h) */
+}
+/* the point x with at most two coordinates replaced: x[k] is loaded once and then selected, so the four evaluations of one row share
+   their loads; j overrides i (the diagonal and the gradient pass i == j, vi == vj; the plain point i = j = -1) */
+template <typename T> struct fd_pair_point {
+    typedef T value_type;
+    const T *x;
+    long long i, j;
+    T vi, vj;
+    __device__ T operator()(long long k) const
+    {
+        T v = x[k];
+        v = k == i ? vi : v;
+        v = k == j ? vj : v;
+        return v;
+    }
+};
+/* the Hessian pattern P = pattern(S^T S) by its UPPER entries (i <= j): the diagonals first [0, ndiag), then i < j, each with the
+   ascending rows of rows(i) & rows(j) at rows[lo[e] .. lo[e + 1]).  dest 0: dense N x N column-major; 1: nzval of P (dst[2e] = slot
+   of (i, j), dst[2e + 1] = slot of (j, i)); 2: BandedMatrix data (2 band + 1) x N, l = u = band */
+struct fd_hess_desc {
+    const int *ent_i, *ent_j;
+    const long long *lo;
+    const int *rows;
+    const long long *dst;
+    void *out;
+    long long nent, ndiag, N;
+    int dest, band;
+};
+/* the rows pass: phi_r(x) of every row.  Launch fd_xcd_grid((M + 255) / 256) workgroups of 256 threads. */
+template <typename T, class F>
+__global__ void __launch_bounds__(256) fd_obj_rows(F f, const T *__restrict__ x, T *__restrict__ fx, long long M)
+{
+    const long long nb = (M + 255) / 256, b = fd_xcd_block(blockIdx.x, nb);
+    if (b >= nb) return;
+    const long long r = b * 256 + threadIdx.x;
+    if (r >= M) return;
+    const fd_pair_point<T> X = {x, -1, -1, (T)0, (T)0};
+    fx[r] = f(r, X);
+}
+/* the entry pass: one lane per upper entry of P, both slots stored.  fx = the rows pass's values.  Launch fd_xcd_grid((nent + 255) / 256)
+   workgroups of 256 threads. */
+template <typename T, class F>
+__global__ void __launch_bounds__(256) fd_hess_entries(F f, const T *__restrict__ x, const T *__restrict__ fx, T relstep, T absstep, fd_hess_desc d)
+{
+    const long long nb = (d.nent + 255) / 256, b = fd_xcd_block(blockIdx.x, nb);
+    if (b >= nb) return;
+    const long long e = b * 256 + threadIdx.x;
+    if (e >= d.nent) return;
+    const long long i = d.ent_i[e], j = d.ent_j[e], q0 = d.lo[e], q1 = d.lo[e + 1];
+    const T xi = x[i], ei = fd_hess_step(xi, relstep, absstep), xip = xi + ei, xim = xi - ei;
+    T h;
+    if (e < d.ndiag) {
+        const fd_pair_point<T> Xp = {x, i, i, xip, xip}, Xm = {x, i, i, xim, xim};
+        T s = (T)0;
+        for (long long q = q0; q < q1; ++q) {
+            const long long r = d.rows[q];
+            const T t = (f(r, Xp) - 2 * fx[r]) + f(r, Xm);
+            s = q == q0 ? t : s + t;
+        }
+        h = s / (ei * ei);
+    } else {
+        const T xj = x[j], ej = fd_hess_step(xj, relstep, absstep), xjp = xj + ej, xjm = xj - ej;
+        const fd_pair_point<T> Xpp = {x, i, j, xip, xjp}, Xpm = {x, i, j, xip, xjm}, Xmp = {x, i, j, xim, xjp}, Xmm = {x, i, j, xim, xjm};
+        T s = (T)0;
+        for (long long q = q0; q < q1; ++q) {
+            const long long r = d.rows[q];
+            const T t = ((f(r, Xpp) - f(r, Xpm)) - f(r, Xmp)) + f(r, Xmm);
+            s = q == q0 ? t : s + t;
+        }
+        h = s / ((4 * ei) * ej);
+    }
+    T *o = (T *)d.out;
+    if (d.dest == 1) {
+        o[d.dst[2 * e]] = h;
+        if (i != j) o[d.dst[2 * e + 1]] = h;
+    } else if (d.dest == 2) {
+        const long long w = 2 * (long long)d.band + 1;
+        o[(d.band + i - j) + w * j] = h;
+        if (i != j) o[(d.band + j - i) + w * i] = h;
+    } else {
+        o[i + j * d.N] = h;
+        if (i != j) o[j + i * d.N] = h;
+    }
+}
+/* the gradient pass: one lane per column j over S's column j (colptr / rowval, 0-based).  MODE 0 forward (fx = the rows pass's
+   values), 1 central.  Launch fd_xcd_grid((N + 255) / 256) workgroups of 256 threads. */
+template <typename T, int MODE, class F>
+__global__ void __launch_bounds__(256) fd_grad_cols(F f, const T *__restrict__ x, const T *__restrict__ fx, T relstep, T absstep, T dir,
+                                                    const long long *__restrict__ colptr, const int *__restrict__ rowval, T *__restrict__ df, long long N)
+{
+    const long long nb = (N + 255) / 256, b = fd_xcd_block(blockIdx.x, nb);
+    if (b >= nb) return;
+    const long long j = b * 256 + threadIdx.x;
+    if (j >= N) return;
+    const T xj = x[j];
+    T e = fd_hess_step(xj, relstep, absstep);
+    if (MODE == 0) e = e * dir;
+    const fd_pair_point<T> Xp = {x, j, j, xj + e, xj + e}, Xm = {x, j, j, xj - e, xj - e};
+    const long long q0 = colptr[j], q1 = colptr[j + 1];
+    T s = (T)0;
+    for (long long q = q0; q < q1; ++q) {
+        const long long r = rowval[q];
+        const T t = MODE == 0 ? f(r, Xp) - fx[r] : f(r, Xp) - f(r, Xm);
+        s = q == q0 ? t : s + t;
+    }
+    df[j] = MODE == 0 ? s / e : s / (2 * e);
+}
 #endif /* __HIPCC__ && __cplusplus */
 
 #endif /* FDJAC_DEVICE_H */

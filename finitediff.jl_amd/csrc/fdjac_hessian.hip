@@ -4,80 +4,19 @@
 // The reference makes O(n^2) calls to a scalar f of O(n) cost each.  With the rows' support pattern S (row r of column j stored <=> phi_r
 // reads x_j) every Hessian entry H_ij is a short sum over rows(i) & rows(j) and every gradient entry a sum over rows(j): O(nnz) work in
 // one launch after the rows pass, no colouring, no atomics.  The kernels are templates of include/fdjac_device.h (fd_obj_rows,
-// fd_hess_entries, fd_grad_cols), instantiated for the caller's functor by hiprtc -- the same compilation as fd_f_compile_rows (embedded
-// header, -ffp-contract=off, gfx950, cached by content) with a kernel tail and a module cache of its own.  The plan builds P =
-// pattern(S^T S) and the rows of every upper entry on the host, on the first call that needs them.  Float64 only.
-#include <dlfcn.h>
-#include <hip/hiprtc.h>
-
+// fd_hess_entries, fd_grad_cols), instantiated for the caller's functor by the library's runtime compiler (fdjac_rtc.hip: the one
+// fd_f_compile_rows uses -- embedded header, -ffp-contract=off, gfx950); this file names the kernels and keeps the compiled objectives,
+// cached by content.  The plan builds P = pattern(S^T S) and the rows of every upper entry on the host, on the first call that needs
+// them.  Float64 only.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <limits>
-#include <map>
-#include <mutex>
 #include <new>
-#include <string>
-#include <vector>
 
 #include "fdjac_internal.h"
 
 namespace fdjac {
-
-const char *jit_device_header();               // fdjac_jit.hip
-void jit_set_compile_log(const char *log);
-
-struct ObjRtc {
-    void *handle = nullptr;
-    decltype(&hiprtcCreateProgram) CreateProgram = nullptr;
-    decltype(&hiprtcDestroyProgram) DestroyProgram = nullptr;
-    decltype(&hiprtcCompileProgram) CompileProgram = nullptr;
-    decltype(&hiprtcAddNameExpression) AddNameExpression = nullptr;
-    decltype(&hiprtcGetLoweredName) GetLoweredName = nullptr;
-    decltype(&hiprtcGetProgramLogSize) GetProgramLogSize = nullptr;
-    decltype(&hiprtcGetProgramLog) GetProgramLog = nullptr;
-    decltype(&hiprtcGetCodeSize) GetCodeSize = nullptr;
-    decltype(&hiprtcGetCode) GetCode = nullptr;
-    decltype(&hiprtcGetErrorString) GetErrorString = nullptr;
-};
-static ObjRtc g_orc;
-static std::mutex g_obj_mutex;
-
-// hiprtc bound at run time, as fdjac_jit.hip binds it (call with g_obj_mutex held)
-static const ObjRtc *obj_hiprtc()
-{
-    if (g_orc.handle) return &g_orc;
-    const char *env = getenv("FDJAC_HIPRTC_LIB");
-    const char *names[] = {env && *env ? env : "libhiprtc.so", "libhiprtc.so", "libhiprtc.so.7", "/opt/rocm/lib/libhiprtc.so"};
-    void *h = nullptr;
-    for (const char *n : names)
-        if (!h) h = dlopen(n, RTLD_NOW | RTLD_GLOBAL);
-    if (!h) {
-        set_error("hiprtc not found (tried libhiprtc.so, /opt/rocm/lib; set FDJAC_HIPRTC_LIB): %s", dlerror());
-        return nullptr;
-    }
-    ObjRtc r;
-    r.handle = h;
-#define FD_OSYM(field, name)                                           \
-    r.field = (decltype(r.field))dlsym(h, name);                       \
-    if (!r.field) {                                                    \
-        set_error("hiprtc symbol %s missing", name);                   \
-        return nullptr;                                                \
-    }
-    FD_OSYM(CreateProgram, "hiprtcCreateProgram")
-    FD_OSYM(DestroyProgram, "hiprtcDestroyProgram")
-    FD_OSYM(CompileProgram, "hiprtcCompileProgram")
-    FD_OSYM(AddNameExpression, "hiprtcAddNameExpression")
-    FD_OSYM(GetLoweredName, "hiprtcGetLoweredName")
-    FD_OSYM(GetProgramLogSize, "hiprtcGetProgramLogSize")
-    FD_OSYM(GetProgramLog, "hiprtcGetProgramLog")
-    FD_OSYM(GetCodeSize, "hiprtcGetCodeSize")
-    FD_OSYM(GetCode, "hiprtcGetCode")
-    FD_OSYM(GetErrorString, "hiprtcGetErrorString")
-#undef FD_OSYM
-    g_orc = r;
-    return &g_orc;
-}
 
 // one compiled objective: its three kernels
 struct ObjModule {
@@ -86,24 +25,14 @@ struct ObjModule {
     unsigned sizeof_f = 0;
     int refs = 0;
     std::string key;
+    ~ObjModule() { if (mod) (void)hipModuleUnload(mod); }
 };
-static std::map<std::string, ObjModule *> g_obj_modules;
+static ModuleCache<ObjModule> g_obj_modules;
 
 static const char kObjTail[] = R"FDOBJ(
 typedef FDOBJ_FUNCTOR fdobj_F;
 extern "C" __device__ __attribute__((used)) const unsigned fdobj_sizeof_f = sizeof(fdobj_F);
 )FDOBJ";
-static const char *const kObjOpts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-math-errno"};
-
-static void release_obj_module(ObjModule *m)
-{
-    if (!m) return;
-    std::lock_guard<std::mutex> lock(g_obj_mutex);
-    if (--m->refs > 0) return;
-    g_obj_modules.erase(m->key);
-    if (m->mod) (void)hipModuleUnload(m->mod);
-    delete m;
-}
 
 static int require_device()
 {
@@ -289,103 +218,34 @@ int fd_objective_compile(fd_ctx *ctx, const char *source, const char *functor, c
     *out = nullptr;
     FD_REQUIRE(M >= 1 && N >= 1 && M < ((int64_t)1 << 31) && N < ((int64_t)1 << 31), FD_ERR_ARG, "bad shape (1 <= M, N < 2^31)");
     FD_REQUIRE(params_bytes >= 0 && (params || params_bytes == 0), FD_ERR_ARG, "bad functor parameters");
-    for (const char *c = functor; *c; ++c)
-        FD_REQUIRE((*c >= 'a' && *c <= 'z') || (*c >= 'A' && *c <= 'Z') || (*c >= '0' && *c <= '9') || *c == '_' || *c == ':' || *c == '<' || *c == '>' || *c == ',' ||
-                       *c == ' ',
-                   FD_ERR_ARG, "functor must be a type name");
+    FD_REQUIRE(rtc_is_type_name(functor), FD_ERR_ARG, "functor must be a type name");
     FD_HIP_CHECK(hipSetDevice(ctx->device));
-    jit_set_compile_log("");
-    std::string src = jit_device_header();
-    src += "\ntypedef double real_t;\n#line 1 \"functor\"\n";
-    src += source;
-    src += "\n#define FDOBJ_FUNCTOR ";
-    src += functor;
-    src += "\n";
-    src += kObjTail;
+    rtc_log().clear();
+    const std::string src = rtc_source("double", rtc_functor_text(source), std::string("FDOBJ_FUNCTOR ") + functor, kObjTail);
     const std::string key = std::to_string(ctx->device) + "\n" + src;
-    ObjModule *m = nullptr;
-    {
-        std::lock_guard<std::mutex> lock(g_obj_mutex);
-        auto it = g_obj_modules.find(key);
-        if (it != g_obj_modules.end()) { m = it->second; m->refs += 1; }
-    }
+    ObjModule *m = g_obj_modules.acquire(key);
     if (!m) {
-        const ObjRtc *R = nullptr;
-        {
-            std::lock_guard<std::mutex> lock(g_obj_mutex);
-            R = obj_hiprtc();
-        }
-        if (!R) return FD_ERR_UNSUPPORTED;
-        hiprtcProgram prog = nullptr;
-        hiprtcResult rr = R->CreateProgram(&prog, src.c_str(), "fdjac_objective.hip", 0, nullptr, nullptr);
-        FD_REQUIRE(rr == HIPRTC_SUCCESS, FD_ERR_HIP, "hiprtcCreateProgram failed: %s", R->GetErrorString(rr));
-        const std::string names[4] = {"fd_obj_rows<double, fdobj_F>", "fd_hess_entries<double, fdobj_F>", "fd_grad_cols<double, 0, fdobj_F>",
-                                      "fd_grad_cols<double, 1, fdobj_F>"};
-        for (const std::string &n : names) (void)R->AddNameExpression(prog, n.c_str());
-        rr = R->CompileProgram(prog, 5, kObjOpts);
-        std::string log;
-        size_t ls = 0;
-        if (R->GetProgramLogSize(prog, &ls) == HIPRTC_SUCCESS && ls > 1) {
-            log.resize(ls);
-            (void)R->GetProgramLog(prog, &log[0]);
-        }
-        jit_set_compile_log(log.c_str());
-        if (rr != HIPRTC_SUCCESS) {
-            set_error("compiling the objective failed (%s); the compiler's messages: fd_f_compile_log().  First lines: %.300s", R->GetErrorString(rr), log.c_str());
-            (void)R->DestroyProgram(&prog);
-            return FD_ERR_ARG;
-        }
-        std::string low[4];
-        for (int k = 0; k < 4; ++k) {
-            const char *ln = nullptr;
-            if (R->GetLoweredName(prog, names[k].c_str(), &ln) == HIPRTC_SUCCESS && ln) low[k] = ln;
-        }
-        std::vector<char> code;
-        size_t cs = 0;
-        bool ok = R->GetCodeSize(prog, &cs) == HIPRTC_SUCCESS && cs > 0;
-        if (ok) {
-            code.resize(cs);
-            ok = R->GetCode(prog, code.data()) == HIPRTC_SUCCESS;
-        }
-        (void)R->DestroyProgram(&prog);
-        FD_REQUIRE(ok, FD_ERR_HIP, "hiprtc returned no code object for the objective");
         m = new (std::nothrow) ObjModule();
         FD_REQUIRE(m, FD_ERR_NOMEM, "out of host memory");
-        hipError_t e = hipModuleLoadData(&m->mod, code.data());
-        hipFunction_t *fn[4] = {&m->rows, &m->hess, &m->grad[0], &m->grad[1]};
-        for (int k = 0; k < 4 && e == hipSuccess; ++k) e = low[k].empty() ? hipErrorNotFound : hipModuleGetFunction(fn[k], m->mod, low[k].c_str());
-        if (e == hipSuccess) {
-            hipDeviceptr_t dp = nullptr;
-            size_t bytes = 0;
-            e = hipModuleGetGlobal(&dp, &bytes, m->mod, "fdobj_sizeof_f");
-            if (e == hipSuccess) e = hipMemcpy(&m->sizeof_f, dp, sizeof(unsigned), hipMemcpyDeviceToHost);
-        }
-        if (e != hipSuccess) {
-            set_error("loading the compiled objective failed: %s", hipGetErrorString(e));
-            if (m->mod) (void)hipModuleUnload(m->mod);
-            delete m;
-            (void)hipGetLastError();
-            return FD_ERR_HIP;
-        }
-        std::lock_guard<std::mutex> lock(g_obj_mutex);
-        auto it = g_obj_modules.find(key);
-        if (it != g_obj_modules.end()) {       // (another thread compiled the same text meanwhile: keep theirs)
-            (void)hipModuleUnload(m->mod);
-            delete m;
-            m = it->second;
-        } else {
-            m->key = key;
-            g_obj_modules[key] = m;
-        }
-        m->refs += 1;
+        m->key = key;
+        RtcResult r = rtc_compile(src, "fdjac_objective.hip", std::vector<char>(),
+                                  {{"fd_obj_rows<double, fdobj_F>", true, &m->rows},
+                                   {"fd_hess_entries<double, fdobj_F>", true, &m->hess},
+                                   {"fd_grad_cols<double, 0, fdobj_F>", true, &m->grad[0]},
+                                   {"fd_grad_cols<double, 1, fdobj_F>", true, &m->grad[1]}},
+                                  {}, {{"fdobj_sizeof_f", &m->sizeof_f}});
+        rtc_log() = r.log;
+        m->mod = r.mod;
+        if (r.status != RTC_OK) { delete m; return rtc_error(r, "objective"); }
+        m = g_obj_modules.publish(m);
     }
     if (!((params_bytes == 0 && m->sizeof_f == 1) || (int64_t)m->sizeof_f == params_bytes)) {
         set_error("the functor %s is %u bytes, %lld bytes of parameters were given", functor, m->sizeof_f, (long long)params_bytes);
-        release_obj_module(m);
+        g_obj_modules.release(m);
         return FD_ERR_ARG;
     }
     fd_objective *o = new (std::nothrow) fd_objective();
-    if (!o) { release_obj_module(m); set_error("out of host memory"); return FD_ERR_NOMEM; }
+    if (!o) { g_obj_modules.release(m); set_error("out of host memory"); return FD_ERR_NOMEM; }
     o->ctx = ctx; o->m = m; o->M = M; o->N = N;
     o->params.assign(std::max<size_t>(m->sizeof_f, 16), 0);
     if (params_bytes > 0) memcpy(o->params.data(), params, (size_t)params_bytes);
@@ -399,7 +259,7 @@ int fd_objective_destroy(fd_objective *obj)
     if (!obj) return FD_OK;
     (void)hipSetDevice(obj->ctx->device);
     (void)hipStreamSynchronize(obj->ctx->stream);
-    release_obj_module(obj->m);
+    g_obj_modules.release(obj->m);
     delete obj;
     return FD_OK;
 }

@@ -85,6 +85,9 @@
 #include <cstdlib>
 #include <cstdint>
 #include <cstdio>
+#include <map>
+#include <mutex>
+#include <string>
 #include <vector>
 
 #include "fdjac.h"
@@ -282,6 +285,65 @@ inline const char *test_switch(const char *name)
 struct TimedSpan {
     int stage;
     hipEvent_t a, b;
+};
+
+// ---- runtime compilation (fdjac_rtc.hip): what fdjac_jit.hip and fdjac_hessian.hip compile a caller's text or bitcode with ----------
+enum RtcStatus { RTC_OK = 0, RTC_UNAVAILABLE, RTC_CREATE, RTC_COMPILE, RTC_LINK, RTC_LOAD };
+struct RtcName   { std::string expr; bool required; hipFunction_t *fn; };      // a kernel template's instantiation, found by its lowered name
+struct RtcKernel { const char *name; hipFunction_t *fn; };                     // an extern "C" kernel (required)
+struct RtcGlobal { const char *name; unsigned *value; };                       // an extern "C" device global, read back (required)
+struct RtcResult {
+    RtcStatus status = RTC_OK;
+    hipModule_t mod = nullptr;       // loaded on the current device; nullptr unless status == RTC_OK
+    std::string log, why;            // the compiler's messages (a link failure's reason appended); what failed
+};
+// `src` as a loaded module: compiled for gfx950 (with -fgpu-rdc and linked with `bitcode` unless that is empty), every *fn and *value
+// filled in -- nullptr for an optional name the module lacks, a required one missing is RTC_LOAD.  No module, no function and no
+// sticky HIP error is left behind by a failure.  Takes the binding's mutex: call it with a module cache's mutex held, or with none.
+RtcResult rtc_compile(const std::string &src, const char *program, const std::vector<char> &bitcode, const std::vector<RtcName> &names,
+                      const std::vector<RtcKernel> &kernels = {}, const std::vector<RtcGlobal> &globals = {});
+// the FD_* code of a result, with the error text set: no hiprtc FD_ERR_UNSUPPORTED, compile / link FD_ERR_ARG, create / load FD_ERR_HIP
+int rtc_error(const RtcResult &r, const char *what);
+std::string &rtc_log();                      // the calling thread's fd_f_compile_log()
+bool rtc_is_type_name(const char *s);        // a functor / terms argument: identifier characters, "::", "<, >" and blanks only
+// the translation unit: the embedded include/fdjac_device.h, "typedef <real> real_t;", body, "#define <define>", tail
+std::string rtc_source(const char *real, const std::string &body, const std::string &define, const std::string &tail);
+inline std::string rtc_functor_text(const char *source) { return std::string("#line 1 \"functor\"\n") + source; }
+
+// compiled modules by content (key = device ordinal + '\n' + text [+ bitcode]: a hipModule_t belongs to the device that was current
+// when it was loaded), shared by reference count.  M has key, refs and a destructor that unloads its modules.
+template <class M> struct ModuleCache {
+    std::mutex mutex;
+    std::map<std::string, M *> map;
+    M *acquire(const std::string &key)
+    {
+        std::lock_guard<std::mutex> lock(mutex);
+        auto it = map.find(key);
+        if (it == map.end()) return nullptr;
+        it->second->refs += 1;
+        return it->second;
+    }
+    M *publish(M *m)      // a freshly compiled module with its key set
+    {
+        std::lock_guard<std::mutex> lock(mutex);
+        auto it = map.find(m->key);
+        if (it != map.end()) {       // (another thread compiled the same text meanwhile: keep theirs)
+            delete m;
+            m = it->second;
+        } else {
+            map[m->key] = m;
+        }
+        m->refs += 1;
+        return m;
+    }
+    void release(M *m)
+    {
+        if (!m) return;
+        std::lock_guard<std::mutex> lock(mutex);
+        if (--m->refs > 0) return;
+        map.erase(m->key);
+        delete m;
+    }
 };
 
 }  // namespace fdjac

@@ -8,94 +8,16 @@
 // over as SOURCE: it is compiled here with hiprtc against the embedded include/fdjac_device.h, -ffp-contract=off as the library
 // itself is built (the reference never fuses a*b+c), for the device's gfx950, cached by content for the life of the process.
 //
-// hiprtc is bound at run time (dlopen), like RCCL: libfdjac loads on boxes without it and fd_f_compile_rows says so.
-#include <dlfcn.h>
-#include <hip/hiprtc.h>
-
+// The compilation itself -- the hiprtc binding (bound at run time, like RCCL), the embedded header, lowered names, the bitcode link --
+// is fdjac_rtc.hip's, shared with the objectives of fdjac_hessian.hip; this file says WHICH kernels a functor needs and launches them.
 #include <cstring>
-#include <map>
-#include <mutex>
 #include <new>
-#include <string>
-#include <vector>
 
 #include "fdjac_internal.h"
 
 #ifndef FDJAC_F32   /* element-type independent (the element type is a parameter of the compilation): compiled once */
 
 namespace fdjac {
-
-static const char kDeviceHeader[] =
-#include "fdjac_device_h.inc"
-    ;
-
-struct Hiprtc {
-    void *handle = nullptr;
-    decltype(&hiprtcCreateProgram) CreateProgram = nullptr;
-    decltype(&hiprtcDestroyProgram) DestroyProgram = nullptr;
-    decltype(&hiprtcCompileProgram) CompileProgram = nullptr;
-    decltype(&hiprtcAddNameExpression) AddNameExpression = nullptr;
-    decltype(&hiprtcGetLoweredName) GetLoweredName = nullptr;
-    decltype(&hiprtcGetProgramLogSize) GetProgramLogSize = nullptr;
-    decltype(&hiprtcGetProgramLog) GetProgramLog = nullptr;
-    decltype(&hiprtcGetCodeSize) GetCodeSize = nullptr;
-    decltype(&hiprtcGetCode) GetCode = nullptr;
-    decltype(&hiprtcGetErrorString) GetErrorString = nullptr;
-    // linking a caller's LLVM bitcode in (fd_f_link_rows_bitcode): optional -- an older hiprtc without them serves source functors only
-    decltype(&hiprtcGetBitcodeSize) GetBitcodeSize = nullptr;
-    decltype(&hiprtcGetBitcode) GetBitcode = nullptr;
-    decltype(&hiprtcLinkCreate) LinkCreate = nullptr;
-    decltype(&hiprtcLinkAddData) LinkAddData = nullptr;
-    decltype(&hiprtcLinkComplete) LinkComplete = nullptr;
-    decltype(&hiprtcLinkDestroy) LinkDestroy = nullptr;
-};
-static Hiprtc g_rtc;
-static std::mutex g_jit_mutex;
-static thread_local std::string t_log;
-// (fdjac_hessian.hip compiles objectives against the same embedded header and reports through the same fd_f_compile_log)
-const char *jit_device_header() { return kDeviceHeader; }
-void jit_set_compile_log(const char *log) { t_log = log ? log : ""; }
-
-static const Hiprtc *hiprtc()
-{
-    if (g_rtc.handle) return &g_rtc;
-    const char *env = getenv("FDJAC_HIPRTC_LIB");
-    const char *names[] = {env && *env ? env : "libhiprtc.so", "libhiprtc.so", "libhiprtc.so.7", "/opt/rocm/lib/libhiprtc.so"};
-    void *h = nullptr;
-    for (const char *n : names)
-        if (!h) h = dlopen(n, RTLD_NOW | RTLD_GLOBAL);
-    if (!h) {
-        set_error("hiprtc not found (tried libhiprtc.so, /opt/rocm/lib; set FDJAC_HIPRTC_LIB): %s", dlerror());
-        return nullptr;
-    }
-    Hiprtc r;
-    r.handle = h;
-#define FD_SYM(field, name)                                            \
-    r.field = (decltype(r.field))dlsym(h, name);                       \
-    if (!r.field) {                                                    \
-        set_error("hiprtc symbol %s missing", name);                   \
-        return nullptr;                                                \
-    }
-    FD_SYM(CreateProgram, "hiprtcCreateProgram")
-    FD_SYM(DestroyProgram, "hiprtcDestroyProgram")
-    FD_SYM(CompileProgram, "hiprtcCompileProgram")
-    FD_SYM(AddNameExpression, "hiprtcAddNameExpression")
-    FD_SYM(GetLoweredName, "hiprtcGetLoweredName")
-    FD_SYM(GetProgramLogSize, "hiprtcGetProgramLogSize")
-    FD_SYM(GetProgramLog, "hiprtcGetProgramLog")
-    FD_SYM(GetCodeSize, "hiprtcGetCodeSize")
-    FD_SYM(GetCode, "hiprtcGetCode")
-    FD_SYM(GetErrorString, "hiprtcGetErrorString")
-#undef FD_SYM
-    r.GetBitcodeSize = (decltype(r.GetBitcodeSize))dlsym(h, "hiprtcGetBitcodeSize");
-    r.GetBitcode = (decltype(r.GetBitcode))dlsym(h, "hiprtcGetBitcode");
-    r.LinkCreate = (decltype(r.LinkCreate))dlsym(h, "hiprtcLinkCreate");
-    r.LinkAddData = (decltype(r.LinkAddData))dlsym(h, "hiprtcLinkAddData");
-    r.LinkComplete = (decltype(r.LinkComplete))dlsym(h, "hiprtcLinkComplete");
-    r.LinkDestroy = (decltype(r.LinkDestroy))dlsym(h, "hiprtcLinkDestroy");
-    g_rtc = r;
-    return &g_rtc;
-}
 
 // one compiled translation unit: the plain row launcher and the storing kernels of one functor type / element type
 struct JitModule {
@@ -138,40 +60,28 @@ struct JitModule {
     std::string key;              // device ordinal + '\n' + source: a hipModule_t belongs to the device that was current when it was loaded
     std::string text;             // the source alone (band_function compiles more instantiations from it)
     int device = 0;
-};
-static std::map<std::string, JitModule *> g_modules;
-
-// a compiled program as a loaded module.  bitcode empty: the program's code object; else the program (compiled with -fgpu-rdc) and the
-// caller's bitcode linked into one code object first (hiprtcLink*, LLVM bitcode inputs: the caller's row function is inlined into the
-// kernels like a source functor's call operator)
-static const char *const kJitOpts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-math-errno", "-fgpu-rdc"};
-static hipError_t load_program(const Hiprtc *R, hiprtcProgram prog, const std::vector<char> &bitcode, hipModule_t *mod, std::string *why)
-{
-    if (bitcode.empty()) {
-        size_t cs = 0;
-        std::vector<char> code;
-        if (R->GetCodeSize(prog, &cs) != HIPRTC_SUCCESS || cs == 0) { *why = "hiprtcGetCodeSize failed"; return hipErrorUnknown; }
-        code.resize(cs);
-        if (R->GetCode(prog, code.data()) != HIPRTC_SUCCESS) { *why = "hiprtcGetCode failed"; return hipErrorUnknown; }
-        return hipModuleLoadData(mod, code.data());
+    ~JitModule()
+    {
+        for (auto &kv : extra)
+            if (kv.second.mod) (void)hipModuleUnload(kv.second.mod);
+        if (cplx.mod) (void)hipModuleUnload(cplx.mod);
+        if (cr.mod) (void)hipModuleUnload(cr.mod);
+        if (mod) (void)hipModuleUnload(mod);
     }
-    if (!R->GetBitcode || !R->GetBitcodeSize || !R->LinkCreate || !R->LinkAddData || !R->LinkComplete || !R->LinkDestroy) { *why = "this hiprtc has no link interface"; return hipErrorNotSupported; }
-    size_t bs = 0;
-    if (R->GetBitcodeSize(prog, &bs) != HIPRTC_SUCCESS || bs == 0) { *why = "hiprtcGetBitcodeSize failed"; return hipErrorUnknown; }
-    std::vector<char> glue(bs), user(bitcode);
-    if (R->GetBitcode(prog, glue.data()) != HIPRTC_SUCCESS) { *why = "hiprtcGetBitcode failed"; return hipErrorUnknown; }
-    hiprtcLinkState ls = nullptr;
-    if (R->LinkCreate(0, nullptr, nullptr, &ls) != HIPRTC_SUCCESS) { *why = "hiprtcLinkCreate failed"; return hipErrorUnknown; }
-    hipError_t e = hipErrorUnknown;
-    void *bin = nullptr;
-    size_t sz = 0;
-    hiprtcResult r = R->LinkAddData(ls, HIPRTC_JIT_INPUT_LLVM_BITCODE, glue.data(), glue.size(), "fdjac kernels", 0, nullptr, nullptr);
-    if (r == HIPRTC_SUCCESS) r = R->LinkAddData(ls, HIPRTC_JIT_INPUT_LLVM_BITCODE, user.data(), user.size(), "caller's row function", 0, nullptr, nullptr);
-    if (r == HIPRTC_SUCCESS) r = R->LinkComplete(ls, &bin, &sz);
-    if (r == HIPRTC_SUCCESS && bin && sz) e = hipModuleLoadData(mod, bin);
-    else *why = std::string("linking the caller's bitcode failed (") + R->GetErrorString(r) + "): does it define fdjac_user_row (and fdjac_user_row_c for the complex step) for gfx950?";
-    (void)R->LinkDestroy(ls);
-    return e;
+};
+static ModuleCache<JitModule> g_modules;      // (its mutex also guards the modules' lazily compiled extras)
+
+static const char *const kColourType[2] = {"unsigned char", "int"}, *const kMode[2] = {"0", "1"};      // [colour bytes == 4], [central]
+
+// one more instantiation of the module's functor, compiled on first use (call with g_modules.mutex held).  Silent: a caller declines.
+static bool jit_extra(JitModule *m, const std::string &src, const char *program, const std::vector<RtcName> &names, hipModule_t *mod,
+                      const std::vector<RtcKernel> &kernels = {}, std::string *log = nullptr)
+{
+    if (hipSetDevice(m->device) != hipSuccess) return false;      // (the extra module must live where the functor's first module does)
+    RtcResult r = rtc_compile(src, program, m->bitcode, names, kernels);
+    if (log) *log = r.log;
+    *mod = r.mod;
+    return r.status == RTC_OK;
 }
 
 // fd_band_store_cols for the bandwidths (l, u) of this module's functor: the precompiled pair, or one more small compilation
@@ -181,34 +91,13 @@ static hipFunction_t band_function(JitModule *m, int l, int u, int central)
     if (l == 1 && u == 1) return m->band[0][central];
     if (l == 2 && u == 2) return m->band[1][central];
     if (l < 0 || u < 0 || l + u > 8) return nullptr;                  // (2 (l + u + 1) quotients per lane live in registers)
-    std::lock_guard<std::mutex> lock(g_jit_mutex);
+    std::lock_guard<std::mutex> lock(g_modules.mutex);
     JitModule::BandExtra &x = m->extra[std::make_pair(l, u)];
     if (x.fn[central] || x.failed) return x.fn[central];
-    x.failed = true;                                                  // (until everything below has worked)
-    const Hiprtc *R = hiprtc();
-    if (!R) return nullptr;
-    hiprtcProgram prog = nullptr;
-    if (hipSetDevice(m->device) != hipSuccess) return nullptr;       // (the extra module must live where the functor's first module does)
-    if (R->CreateProgram(&prog, m->text.c_str(), "fdjac_jit_band.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS) return nullptr;
-    std::string names[2];
-    for (int md = 0; md < 2; ++md) {
-        names[md] = "fd_band_store_cols<" + m->real + ", " + (md ? "1" : "0") + ", fdjit_F, " + std::to_string(l) + ", " + std::to_string(u) + ">";
-        (void)R->AddNameExpression(prog, names[md].c_str());
-    }
-    bool ok = R->CompileProgram(prog, m->bitcode.empty() ? 5 : 6, kJitOpts) == HIPRTC_SUCCESS;
-    std::string low[2];
-    for (int md = 0; md < 2 && ok; ++md) {
-        const char *ln = nullptr;
-        if (R->GetLoweredName(prog, names[md].c_str(), &ln) == HIPRTC_SUCCESS && ln) low[md] = ln; else ok = false;
-    }
-    std::string why;
-    if (ok) ok = load_program(R, prog, m->bitcode, &x.mod, &why) == hipSuccess;
-    (void)R->DestroyProgram(&prog);
-    if (!ok) { (void)hipGetLastError(); return nullptr; }
+    std::vector<RtcName> names;
     for (int md = 0; md < 2; ++md)
-        if (hipModuleGetFunction(&x.fn[md], x.mod, low[md].c_str()) != hipSuccess) { x.fn[md] = nullptr; ok = false; }
-    if (!ok) { (void)hipGetLastError(); return nullptr; }
-    x.failed = false;
+        names.push_back({"fd_band_store_cols<" + m->real + ", " + kMode[md] + ", fdjit_F, " + std::to_string(l) + ", " + std::to_string(u) + ">", true, &x.fn[md]});
+    x.failed = !jit_extra(m, m->text, "fdjac_jit_band.hip", names, &x.mod);
     return x.fn[central];
 }
 
@@ -228,85 +117,34 @@ extern "C" __global__ void __launch_bounds__(256) fdjit_rows_cplx(real_t *__rest
 // the complex instantiation of the module's functor (one more compilation, kept with the module); nullptr-safe: m->cplx.ok says whether it exists
 static bool cplx_functions(JitModule *m)
 {
-    std::lock_guard<std::mutex> lock(g_jit_mutex);
+    std::lock_guard<std::mutex> lock(g_modules.mutex);
     JitModule::Cplx &x = m->cplx;
     if (x.tried) return x.ok;
     x.tried = true;
-    const Hiprtc *R = hiprtc();
-    if (!R || hipSetDevice(m->device) != hipSuccess) return false;
-    const std::string src = m->text + kJitTailCplx;
-    hiprtcProgram prog = nullptr;
-    if (R->CreateProgram(&prog, src.c_str(), "fdjac_jit_cplx.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS) return false;
-    const char *ct[2] = {"unsigned char", "int"};
-    std::string names[2], cnames[2];
+    std::vector<RtcName> names;
     for (int cb = 0; cb < 2; ++cb) {
-        names[cb] = "fd_csc_store_cols_cplx<" + m->real + ", " + ct[cb] + ", fdjit_F>";
-        (void)R->AddNameExpression(prog, names[cb].c_str());
-        cnames[cb] = "fd_colrange_store_cols<" + m->real + ", " + ct[cb] + ", 2, fdjit_F>";
-        (void)R->AddNameExpression(prog, cnames[cb].c_str());
+        names.push_back({"fd_csc_store_cols_cplx<" + m->real + ", " + kColourType[cb] + ", fdjit_F>", true, &x.store[cb]});
+        names.push_back({"fd_colrange_store_cols<" + m->real + ", " + kColourType[cb] + ", 2, fdjit_F>", false, &x.colrange[cb]});      // (an optimisation)
     }
-    bool ok = R->CompileProgram(prog, m->bitcode.empty() ? 5 : 6, kJitOpts) == HIPRTC_SUCCESS;
-    size_t ls = 0;
-    if (R->GetProgramLogSize(prog, &ls) == HIPRTC_SUCCESS && ls > 1) { x.log.resize(ls); (void)R->GetProgramLog(prog, &x.log[0]); }
-    std::string low[2], clow[2];
-    for (int cb = 0; cb < 2 && ok; ++cb) {
-        const char *ln = nullptr;
-        if (R->GetLoweredName(prog, names[cb].c_str(), &ln) == HIPRTC_SUCCESS && ln) low[cb] = ln; else ok = false;
-        if (ok && R->GetLoweredName(prog, cnames[cb].c_str(), &ln) == HIPRTC_SUCCESS && ln) clow[cb] = ln;
-    }
-    if (ok) {
-        std::string why;
-        ok = load_program(R, prog, m->bitcode, &x.mod, &why) == hipSuccess;
-        if (!ok) x.log += why;
-    }
-    (void)R->DestroyProgram(&prog);
-    if (!ok) { (void)hipGetLastError(); return false; }
-    ok = hipModuleGetFunction(&x.rows, x.mod, "fdjit_rows_cplx") == hipSuccess;
-    for (int cb = 0; cb < 2 && ok; ++cb) ok = hipModuleGetFunction(&x.store[cb], x.mod, low[cb].c_str()) == hipSuccess;
-    for (int cb = 0; cb < 2 && ok; ++cb)
-        if (clow[cb].empty() || hipModuleGetFunction(&x.colrange[cb], x.mod, clow[cb].c_str()) != hipSuccess) x.colrange[cb] = nullptr;      // (an optimisation)
-    if (!ok) (void)hipGetLastError();
-    x.ok = ok;
-    return ok;
+    x.ok = jit_extra(m, m->text + kJitTailCplx, "fdjac_jit_cplx.hip", names, &x.mod, {{"fdjit_rows_cplx", &x.rows}}, &x.log);
+    return x.ok;
 }
 
 // fd_colrange_store_cols for forward / central differences (one more small compilation, kept with the module)
 static bool colrange_functions(JitModule *m)
 {
-    std::lock_guard<std::mutex> lock(g_jit_mutex);
+    std::lock_guard<std::mutex> lock(g_modules.mutex);
     JitModule::ColRange &x = m->cr;
     if (x.tried) return x.ok;
     x.tried = true;
-    const Hiprtc *R = hiprtc();
-    if (!R || hipSetDevice(m->device) != hipSuccess) return false;
-    hiprtcProgram prog = nullptr;
-    if (R->CreateProgram(&prog, m->text.c_str(), "fdjac_jit_colrange.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS) return false;
-    const char *ct[2] = {"unsigned char", "int"};
-    std::string names[2][2], bnames[2][2];
+    std::vector<RtcName> names;
     for (int cb = 0; cb < 2; ++cb)
         for (int md = 0; md < 2; ++md) {
-            names[cb][md] = "fd_colrange_store_cols<" + m->real + ", " + ct[cb] + ", " + (md ? "1" : "0") + ", fdjit_F>";
-            (void)R->AddNameExpression(prog, names[cb][md].c_str());
-            bnames[cb][md] = "fd_bbb_store_cols<" + m->real + ", " + ct[cb] + ", " + (md ? "1" : "0") + ", fdjit_F>";
-            (void)R->AddNameExpression(prog, bnames[cb][md].c_str());
+            names.push_back({"fd_colrange_store_cols<" + m->real + ", " + kColourType[cb] + ", " + kMode[md] + ", fdjit_F>", true, &x.fn[cb][md]});
+            names.push_back({"fd_bbb_store_cols<" + m->real + ", " + kColourType[cb] + ", " + kMode[md] + ", fdjit_F>", true, &x.bbb[cb][md]});
         }
-    bool ok = R->CompileProgram(prog, m->bitcode.empty() ? 5 : 6, kJitOpts) == HIPRTC_SUCCESS;
-    std::string low[2][2], blow[2][2];
-    for (int cb = 0; cb < 2 && ok; ++cb)
-        for (int md = 0; md < 2 && ok; ++md) {
-            const char *ln = nullptr;
-            if (R->GetLoweredName(prog, names[cb][md].c_str(), &ln) == HIPRTC_SUCCESS && ln) low[cb][md] = ln; else ok = false;
-            if (ok && R->GetLoweredName(prog, bnames[cb][md].c_str(), &ln) == HIPRTC_SUCCESS && ln) blow[cb][md] = ln; else ok = false;
-        }
-    std::string why;
-    if (ok) ok = load_program(R, prog, m->bitcode, &x.mod, &why) == hipSuccess;
-    (void)R->DestroyProgram(&prog);
-    for (int cb = 0; cb < 2 && ok; ++cb)
-        for (int md = 0; md < 2 && ok; ++md)
-            ok = hipModuleGetFunction(&x.fn[cb][md], x.mod, low[cb][md].c_str()) == hipSuccess && hipModuleGetFunction(&x.bbb[cb][md], x.mod, blow[cb][md].c_str()) == hipSuccess;
-    if (!ok) (void)hipGetLastError();
-    x.ok = ok;
-    return ok;
+    x.ok = jit_extra(m, m->text, "fdjac_jit_colrange.hip", names, &x.mod);
+    return x.ok;
 }
 
 }  // namespace fdjac
@@ -354,7 +192,7 @@ static int jit_launch(void *fctx, void *fx, const void *x, int64_t nbatch, int64
     if (is_complex && !cplx_functions(j->m)) {
         set_error("the functor does not compile for the complex step -- write its call operator on `typename P::value_type` (include/fdjac_device.h, "
                   "\"the complex step for row functors\").  Compiler: %.300s", j->m->cplx.log.c_str());
-        t_log = j->m->cplx.log;
+        rtc_log() = j->m->cplx.log;
         return 3;
     }
     long long xs = x_stride, fs = fx_stride, r0 = row_begin, r1 = row_end;      // (complex points: strides and rows in complex elements)
@@ -362,6 +200,23 @@ static int jit_launch(void *fctx, void *fx, const void *x, int64_t nbatch, int64
     const unsigned gx = (unsigned)((row_end - row_begin + 255) / 256);
     if (hipModuleLaunchKernel(is_complex ? j->m->cplx.rows : j->m->rows, gx, (unsigned)nbatch, 1, 256, 1, 1, 0, (hipStream_t)stream, args, nullptr) != hipSuccess) return 4;
     j->launches += 1;
+    return 0;
+}
+
+// forward differences of the column-range / BBB stores: f(x) of all rows ONCE (the plain launcher's kernel into the functor's own buffer)
+// -- the columns of a dense block share their rows, forming f(x) inside the storing launch would double the row evaluations.
+// *base = that buffer, or nullptr when it cannot be allocated (the storing launch then forms f(x) itself)
+static int base_rows(fd_jit_f *j, const void *xq, void *stream, const void **base)
+{
+    *base = nullptr;
+    if (!j->d_base && hipMalloc(&j->d_base, (size_t)j->M * (size_t)j->elem_bytes) != hipSuccess) { (void)hipGetLastError(); j->d_base = nullptr; }
+    if (!j->d_base) return 0;
+    void *fxp = j->d_base;
+    long long xs = 0, fs = 0, r0 = 0, r1 = j->M;
+    void *ra[] = {&fxp, (void *)&xq, (void *)j->params.data(), &xs, &fs, &r0, &r1};
+    if (hipModuleLaunchKernel(j->m->rows, (unsigned)((j->M + 255) / 256), 1, 1, 256, 1, 1, 0, (hipStream_t)stream, ra, nullptr) != hipSuccess) return 4;
+    j->launches += 1;
+    *base = j->d_base;
     return 0;
 }
 
@@ -400,17 +255,7 @@ static int jit_launch_lazy(void *fctx, void *fx, const fd_lazy_points *lp, int64
         const long long slots = bb.N * (bb.bl + bb.bu + 1) * (bb.lam + bb.mu + 1);
         if (slots <= 0 || (slots + 255) / 256 >= ((long long)1 << 31)) return FD_LAZY_DECLINED;
         const void *xq = lp->x, *eq = lp->eps, *base = nullptr;
-        if (!central) {
-            if (!j->d_base && hipMalloc(&j->d_base, (size_t)j->M * (size_t)j->elem_bytes) != hipSuccess) { (void)hipGetLastError(); j->d_base = nullptr; }
-            if (j->d_base) {
-                void *fxp = j->d_base;
-                long long xs = 0, fs = 0, r0 = 0, r1 = j->M;
-                void *ra[] = {&fxp, (void *)&xq, (void *)j->params.data(), &xs, &fs, &r0, &r1};
-                if (hipModuleLaunchKernel(j->m->rows, (unsigned)((j->M + 255) / 256), 1, 1, 256, 1, 1, 0, (hipStream_t)stream, ra, nullptr) != hipSuccess) return 4;
-                j->launches += 1;
-                base = j->d_base;
-            }
-        }
+        if (!central && base_rows(j, xq, stream, &base) != 0) return 4;
         void *args[] = {(void *)j->params.data(), (void *)&xq, (void *)&eq, &bb, (void *)&base};
         if (hipModuleLaunchKernel(j->m->cr.bbb[cbi][central], (unsigned)((slots + 255) / 256), 1, 1, 256, 1, 1, 0, (hipStream_t)stream, args, nullptr) != hipSuccess) return 4;
         j->launches += 1;
@@ -431,19 +276,7 @@ static int jit_launch_lazy(void *fctx, void *fx, const fd_lazy_points *lp, int64
         int c_lo = lp->c_lo, c_hi = lp->c_lo + lp->ncolors;
         const void *xq = lp->x, *eq = lp->eps;
         const void *base = nullptr;
-        if (!lp->is_complex && !central) {
-            // forward differences: f(x) of all rows ONCE (the plain launcher's kernel into the functor's own buffer) -- the columns of
-            // a dense block share their rows, forming f(x) inside the storing launch would double the row evaluations
-            if (!j->d_base && hipMalloc(&j->d_base, (size_t)j->M * (size_t)j->elem_bytes) != hipSuccess) { (void)hipGetLastError(); j->d_base = nullptr; }
-            if (j->d_base) {
-                void *fxp = j->d_base;
-                long long xs = 0, fs = 0, r0 = 0, r1 = j->M;
-                void *ra[] = {&fxp, (void *)&xq, (void *)j->params.data(), &xs, &fs, &r0, &r1};
-                if (hipModuleLaunchKernel(j->m->rows, (unsigned)((j->M + 255) / 256), 1, 1, 256, 1, 1, 0, (hipStream_t)stream, ra, nullptr) != hipSuccess) return 4;
-                j->launches += 1;
-                base = j->d_base;
-            }
-        }
+        if (!lp->is_complex && !central && base_rows(j, xq, stream, &base) != 0) return 4;
         void *args[] = {(void *)j->params.data(), (void *)&xq, (void *)&eq, &c_lo, &c_hi, &cr, (void *)&base};
         const long long nw = (cr.col_end - cr.col_begin + 7) / 8;
         if (hipModuleLaunchKernel(fn, (unsigned)(8 * ((nw + 7) / 8)), 1, 1, 256, 1, 1, 0, (hipStream_t)stream, args, nullptr) != hipSuccess) return 4;
@@ -519,27 +352,11 @@ static int jit_launch_lazy(void *fctx, void *fx, const fd_lazy_points *lp, int64
     return 0;
 }
 
-static void release_module(JitModule *m)
-{
-    if (!m) return;
-    std::lock_guard<std::mutex> lock(g_jit_mutex);
-    if (--m->refs > 0) return;
-    g_modules.erase(m->key);
-    for (auto &kv : m->extra)
-        if (kv.second.mod) (void)hipModuleUnload(kv.second.mod);
-    if (m->cplx.mod) (void)hipModuleUnload(m->cplx.mod);
-    if (m->cr.mod) (void)hipModuleUnload(m->cr.mod);
-    if (m->mod) (void)hipModuleUnload(m->mod);
-    delete m;
-}
-
 }  // namespace fdjac
 
 using namespace fdjac;
 
 extern "C" {
-
-const char *fd_f_compile_log(void) { return t_log.c_str(); }
 
 // the shared back half of fd_f_compile_rows / fd_f_link_rows_bitcode: `src` is the complete translation unit (device header, element
 // type, the functor -- source text, or the shim around the caller's bitcode --, the kernels), `bitcode` the caller's LLVM bitcode or empty
@@ -550,154 +367,54 @@ static int jit_build(fd_ctx *ctx, const std::string &src, const std::vector<char
     const bool sep = sep_lists != nullptr;      // fd_f_compile_terms: FDJIT_FUNCTOR is fd_sep_rows<terms>, sep_lists = {row_ptr, row_col} on the device
     // (modules are per DEVICE: a second context on another GPU compiling the same text must not get device 0's functions)
     const std::string key = std::to_string(ctx->device) + "\n" + src + std::string(bitcode.begin(), bitcode.end());
-    JitModule *m = nullptr;
-    {
-        std::lock_guard<std::mutex> lock(g_jit_mutex);
-        auto it = g_modules.find(key);
-        if (it != g_modules.end()) { m = it->second; m->refs += 1; }
-    }
+    JitModule *m = g_modules.acquire(key);
     if (!m) {
-        const Hiprtc *R = nullptr;
-        {
-            std::lock_guard<std::mutex> lock(g_jit_mutex);
-            R = hiprtc();
-        }
-        if (!R) return FD_ERR_UNSUPPORTED;
-        hiprtcProgram prog = nullptr;
-        hiprtcResult rr = R->CreateProgram(&prog, src.c_str(), "fdjac_jit.hip", 0, nullptr, nullptr);
-        FD_REQUIRE(rr == HIPRTC_SUCCESS, FD_ERR_HIP, "hiprtcCreateProgram failed: %s", R->GetErrorString(rr));
-        // the kernels of include/fdjac_device.h instantiated for this functor, found by their lowered names
-        std::string names[2][2][2];
-        const char *ct[2] = {"unsigned char", "int"};
-        for (int w = 0; w < 2; ++w)
-            for (int cb = 0; cb < 2; ++cb)
-                for (int md = 0; md < 2; ++md) {
-                    names[w][cb][md] = std::string(w ? "fd_csc_store_cols_win<" : "fd_csc_store_cols<") + real + ", " + ct[cb] + ", " + (md ? "1" : "0") + ", fdjit_F>";
-                    (void)R->AddNameExpression(prog, names[w][cb][md].c_str());
-                }
-        std::string bnames[2][2];
-        for (int wi = 0; wi < 2; ++wi)
-            for (int md = 0; md < 2; ++md) {
-                bnames[wi][md] = std::string("fd_band_store_cols<") + real + ", " + (md ? "1" : "0") + ", fdjit_F, " + (wi ? "2, 2>" : "1, 1>");
-                (void)R->AddNameExpression(prog, bnames[wi][md].c_str());
-            }
-        std::string rnames[2][2], enames[2][2];
-        if (sep)
-            for (int cb = 0; cb < 2; ++cb)
-                for (int md = 0; md < 2; ++md) {
-                    rnames[cb][md] = std::string("fd_csc_store_rows<") + real + ", " + ct[cb] + ", " + (md ? "1" : "0") + ", fdjit_F>";
-                    (void)R->AddNameExpression(prog, rnames[cb][md].c_str());
-                    enames[cb][md] = std::string("fd_csc_store_ents<") + real + ", " + ct[cb] + ", " + (md ? "1" : "0") + ", fdjit_F>";
-                    (void)R->AddNameExpression(prog, enames[cb][md].c_str());
-                }
-        rr = R->CompileProgram(prog, bitcode.empty() ? 5 : 6, kJitOpts);
-        size_t ls = 0;
-        if (R->GetProgramLogSize(prog, &ls) == HIPRTC_SUCCESS && ls > 1) {
-            t_log.resize(ls);
-            (void)R->GetProgramLog(prog, &t_log[0]);
-        }
-        if (rr != HIPRTC_SUCCESS) {
-            set_error("compiling the functor failed (%s); the compiler's messages: fd_f_compile_log().  First lines: %.300s", R->GetErrorString(rr), t_log.c_str());
-            (void)R->DestroyProgram(&prog);
-            return FD_ERR_ARG;
-        }
-        std::string low[2][2][2];
-        for (int w = 0; w < 2; ++w)
-            for (int cb = 0; cb < 2; ++cb)
-                for (int md = 0; md < 2; ++md) {
-                    const char *ln = nullptr;
-                    if (R->GetLoweredName(prog, names[w][cb][md].c_str(), &ln) == HIPRTC_SUCCESS && ln) low[w][cb][md] = ln;
-                }
-        std::string blow[2][2];
-        for (int wi = 0; wi < 2; ++wi)
-            for (int md = 0; md < 2; ++md) {
-                const char *ln = nullptr;
-                if (R->GetLoweredName(prog, bnames[wi][md].c_str(), &ln) == HIPRTC_SUCCESS && ln) blow[wi][md] = ln;
-            }
-        std::string rlow[2][2], elow[2][2];
-        if (sep)
-            for (int cb = 0; cb < 2; ++cb)
-                for (int md = 0; md < 2; ++md) {
-                    const char *ln = nullptr;
-                    if (R->GetLoweredName(prog, rnames[cb][md].c_str(), &ln) == HIPRTC_SUCCESS && ln) rlow[cb][md] = ln;
-                    if (R->GetLoweredName(prog, enames[cb][md].c_str(), &ln) == HIPRTC_SUCCESS && ln) elow[cb][md] = ln;
-                }
         m = new (std::nothrow) JitModule();
-        if (!m) { (void)R->DestroyProgram(&prog); FD_REQUIRE(false, FD_ERR_NOMEM, "out of host memory"); }
-        std::string why;
-        hipError_t e = load_program(R, prog, bitcode, &m->mod, &why);
-        (void)R->DestroyProgram(&prog);
-        if (e != hipSuccess && !why.empty()) {
-            set_error("%s", why.c_str());
-            t_log += why;
-            delete m;
-            (void)hipGetLastError();
-            return FD_ERR_ARG;
-        }
-        if (e == hipSuccess) e = hipModuleGetFunction(&m->rows, m->mod, "fdjit_rows");
-        for (int cb = 0; cb < 2 && e == hipSuccess; ++cb)
-            for (int md = 0; md < 2 && e == hipSuccess; ++md) {
-                e = low[0][cb][md].empty() ? hipErrorNotFound : hipModuleGetFunction(&m->store[cb][md], m->mod, low[0][cb][md].c_str());
-                if (e == hipSuccess && !low[1][cb][md].empty() && hipModuleGetFunction(&m->store_win[cb][md], m->mod, low[1][cb][md].c_str()) != hipSuccess)
-                    m->store_win[cb][md] = nullptr;       // (the windowed form is an optimisation: the plain one serves)
-            }
-        for (int wi = 0; wi < 2 && e == hipSuccess; ++wi)
+        FD_REQUIRE(m, FD_ERR_NOMEM, "out of host memory");
+        m->key = key;
+        m->text = src;
+        m->bitcode = bitcode;
+        m->device = ctx->device;
+        m->real = real;
+        // the kernels of include/fdjac_device.h instantiated for this functor; all but the plain column store are optimisations
+        std::vector<RtcName> names;
+        const std::string tail = std::string(", fdjit_F>"), head = std::string("<") + real + ", ";
+        for (int w = 0; w < 2; ++w)
+            for (int cb = 0; cb < 2; ++cb)
+                for (int md = 0; md < 2; ++md)
+                    names.push_back({(w ? "fd_csc_store_cols_win" : "fd_csc_store_cols") + head + kColourType[cb] + ", " + kMode[md] + tail, w == 0,
+                                     w ? &m->store_win[cb][md] : &m->store[cb][md]});
+        for (int wi = 0; wi < 2; ++wi)
             for (int md = 0; md < 2; ++md)
-                if (blow[wi][md].empty() || hipModuleGetFunction(&m->band[wi][md], m->mod, blow[wi][md].c_str()) != hipSuccess) m->band[wi][md] = nullptr;      // (an optimisation)
-        for (int cb = 0; cb < 2 && e == hipSuccess && sep; ++cb)
-            for (int md = 0; md < 2; ++md)
-            {
-                if (rlow[cb][md].empty() || hipModuleGetFunction(&m->store_rows[cb][md], m->mod, rlow[cb][md].c_str()) != hipSuccess) m->store_rows[cb][md] = nullptr;      // (an optimisation)
-                if (elow[cb][md].empty() || hipModuleGetFunction(&m->store_ents[cb][md], m->mod, elow[cb][md].c_str()) != hipSuccess) m->store_ents[cb][md] = nullptr;
+                names.push_back({"fd_band_store_cols" + head + kMode[md] + ", fdjit_F, " + (wi ? "2, 2>" : "1, 1>"), false, &m->band[wi][md]});
+        for (int cb = 0; cb < 2 && sep; ++cb)
+            for (int md = 0; md < 2; ++md) {
+                names.push_back({"fd_csc_store_rows" + head + kColourType[cb] + ", " + kMode[md] + tail, false, &m->store_rows[cb][md]});
+                names.push_back({"fd_csc_store_ents" + head + kColourType[cb] + ", " + kMode[md] + tail, false, &m->store_ents[cb][md]});
             }
-        if (e == hipSuccess) {
-            hipDeviceptr_t dp = nullptr;
-            size_t bytes = 0;
-            e = hipModuleGetGlobal(&dp, &bytes, m->mod, "fdjit_sizeof_f");
-            if (e == hipSuccess) e = hipMemcpy(&m->sizeof_f, dp, sizeof(unsigned), hipMemcpyDeviceToHost);
-            if (e == hipSuccess) e = hipModuleGetGlobal(&dp, &bytes, m->mod, "fdjit_lists_offset");
-            if (e == hipSuccess) e = hipMemcpy(&m->lists_offset, dp, sizeof(unsigned), hipMemcpyDeviceToHost);
-            if (e == hipSuccess) e = hipModuleGetGlobal(&dp, &bytes, m->mod, "fdjit_terms_bytes");
-            if (e == hipSuccess) e = hipMemcpy(&m->terms_bytes, dp, sizeof(unsigned), hipMemcpyDeviceToHost);
-        }
-        if (e != hipSuccess) {
-            set_error("loading the compiled functor failed: %s", hipGetErrorString(e));
-            if (m->mod) (void)hipModuleUnload(m->mod);
-            delete m;
-            return FD_ERR_HIP;
-        }
-        (void)hipGetLastError();
-        std::lock_guard<std::mutex> lock(g_jit_mutex);
-        auto it = g_modules.find(key);
-        if (it != g_modules.end()) {       // (another thread compiled the same text meanwhile: keep theirs)
-            (void)hipModuleUnload(m->mod);
-            delete m;
-            m = it->second;
-        } else {
-            m->key = key;
-            m->text = src;
-            m->bitcode = bitcode;
-            m->device = ctx->device;
-            m->real = real;
-            g_modules[key] = m;
-        }
-        m->refs += 1;
+        // (hiprtc runs outside the cache's mutex: two threads may compile the same text, the second one's module is dropped)
+        RtcResult r = rtc_compile(src, "fdjac_jit.hip", bitcode, names, {{"fdjit_rows", &m->rows}},
+                                  {{"fdjit_sizeof_f", &m->sizeof_f}, {"fdjit_lists_offset", &m->lists_offset}, {"fdjit_terms_bytes", &m->terms_bytes}});
+        rtc_log() = r.log;
+        m->mod = r.mod;
+        if (r.status != RTC_OK) { delete m; return rtc_error(r, "functor"); }
+        m = g_modules.publish(m);
     }
     // an empty functor has sizeof 1; otherwise the caller's bytes ARE the functor object (a separable functor: the TERMS object, the
     // library appends the list pointers where fd_sep_rows keeps them)
     const unsigned want_bytes = sep ? m->terms_bytes : m->sizeof_f;
     if (sep && (m->lists_offset == 0 || m->lists_offset + 2 * sizeof(void *) > m->sizeof_f)) {
         set_error("internal: fd_sep_rows layout not reported by the compiled module");
-        release_module(m);
+        g_modules.release(m);
         return FD_ERR_HIP;
     }
     if (!((params_bytes == 0 && want_bytes == 1) || (int64_t)want_bytes == params_bytes)) {
         set_error("the functor %s is %u bytes, %lld bytes of parameters were given", functor, want_bytes, (long long)params_bytes);
-        release_module(m);
+        g_modules.release(m);
         return FD_ERR_ARG;
     }
     fd_jit_f *j = new (std::nothrow) fd_jit_f();
-    if (!j) { release_module(m); set_error("out of host memory"); return FD_ERR_NOMEM; }
+    if (!j) { g_modules.release(m); set_error("out of host memory"); return FD_ERR_NOMEM; }
     j->ctx = ctx; j->m = m; j->elem_bytes = elem_bytes; j->M = M; j->N = N;
     j->params.assign(std::max<size_t>(m->sizeof_f, 16), 0);
     if (params_bytes > 0) memcpy(j->params.data(), params, (size_t)params_bytes);
@@ -726,23 +443,11 @@ int fd_f_compile_rows(fd_ctx *ctx, const char *source, const char *functor, cons
     FD_REQUIRE(elem_bytes == 8 || elem_bytes == 4, FD_ERR_ARG, "elem_bytes must be 8 (Float64) or 4 (Float32)");
     FD_REQUIRE(M >= 1 && N >= 1, FD_ERR_ARG, "bad shape");
     FD_REQUIRE(params_bytes >= 0 && (params || params_bytes == 0), FD_ERR_ARG, "bad functor parameters");
-    for (const char *c = functor; *c; ++c)
-        FD_REQUIRE((*c >= 'a' && *c <= 'z') || (*c >= 'A' && *c <= 'Z') || (*c >= '0' && *c <= '9') || *c == '_' || *c == ':' || *c == '<' || *c == '>' || *c == ',' ||
-                       *c == ' ',
-                   FD_ERR_ARG, "functor must be a type name");
+    FD_REQUIRE(rtc_is_type_name(functor), FD_ERR_ARG, "functor must be a type name");
     FD_HIP_CHECK(hipSetDevice(ctx->device));
-    t_log.clear();
+    rtc_log().clear();
     const char *real = elem_bytes == 8 ? "double" : "float";
-    std::string src;      // (hiprtc declares the HIP runtime itself: no include)
-    src += kDeviceHeader;
-    src += "\ntypedef ";
-    src += real;
-    src += " real_t;\n#line 1 \"functor\"\n";
-    src += source;
-    src += "\n#define FDJIT_FUNCTOR ";
-    src += functor;
-    src += "\n";
-    src += kJitTail;
+    const std::string src = rtc_source(real, rtc_functor_text(source), std::string("FDJIT_FUNCTOR ") + functor, kJitTail);
     return jit_build(ctx, src, std::vector<char>(), real, functor, params, params_bytes, M, N, elem_bytes, fn_out, lazy_out, lazy_caps_out, fctx_out);
 }
 
@@ -756,25 +461,13 @@ int fd_f_compile_terms(fd_ctx *ctx, const char *source, const char *terms, const
     FD_REQUIRE(elem_bytes == 8 || elem_bytes == 4, FD_ERR_ARG, "elem_bytes must be 8 (Float64) or 4 (Float32)");
     FD_REQUIRE(M >= 1 && N >= 1 && M < ((int64_t)1 << 31), FD_ERR_ARG, "bad shape");
     FD_REQUIRE(params_bytes >= 0 && (params || params_bytes == 0), FD_ERR_ARG, "bad functor parameters");
-    for (const char *c = terms; *c; ++c)
-        FD_REQUIRE((*c >= 'a' && *c <= 'z') || (*c >= 'A' && *c <= 'Z') || (*c >= '0' && *c <= '9') || *c == '_' || *c == ':' || *c == '<' || *c == '>' || *c == ',' ||
-                       *c == ' ',
-                   FD_ERR_ARG, "terms_type must be a type name");
+    FD_REQUIRE(rtc_is_type_name(terms), FD_ERR_ARG, "terms_type must be a type name");
     FD_HIP_CHECK(hipSetDevice(ctx->device));
-    t_log.clear();
+    rtc_log().clear();
     const char *real = elem_bytes == 8 ? "double" : "float";
-    std::string src;
-    src += kDeviceHeader;
-    src += "\ntypedef ";
-    src += real;
-    src += " real_t;\n#line 1 \"functor\"\n";
-    src += source;
-    src += "\n#define FDJIT_FUNCTOR fd_sep_rows<";
-    src += terms;
-    src += " >\n";
-    src += kJitTail;
     const void *lists[2] = {row_ptr_dev, row_col_dev};
     const std::string name = std::string("fd_sep_rows<") + terms + " >";
+    const std::string src = rtc_source(real, rtc_functor_text(source), "FDJIT_FUNCTOR " + name, kJitTail);
     return jit_build(ctx, src, std::vector<char>(), real, name.c_str(), params, params_bytes, M, N, elem_bytes, fn_out, lazy_out, lazy_caps_out, fctx_out, lists,
                      (unsigned long long)plan_serial);
 }
@@ -855,18 +548,11 @@ int fd_f_link_rows_bitcode(fd_ctx *ctx, const void *bitcode, int64_t bitcode_byt
     FD_REQUIRE(M >= 1 && N >= 1, FD_ERR_ARG, "bad shape");
     FD_REQUIRE(params_bytes >= 0 && params_bytes <= 4096 && (params || params_bytes == 0), FD_ERR_ARG, "bad parameters (at most 4096 bytes: they travel as a kernel argument)");
     FD_HIP_CHECK(hipSetDevice(ctx->device));
-    t_log.clear();
+    rtc_log().clear();
     const char *real = elem_bytes == 8 ? "double" : "float";
     const int64_t np = params_bytes > 0 ? params_bytes : 1;
-    std::string src;
-    src += kDeviceHeader;
-    src += "\ntypedef ";
-    src += real;
-    src += " real_t;\n#define FDJIT_NPARAMS " + std::to_string((long long)np) + "\n";
-    src += kExternHead;
-    src += "\n#define FDJIT_FUNCTOR fd_extern_F\n";
-    src += kJitTail;
-    src += kExternTail;
+    const std::string src = rtc_source(real, "#define FDJIT_NPARAMS " + std::to_string((long long)np) + "\n" + kExternHead, "FDJIT_FUNCTOR fd_extern_F",
+                                       std::string(kJitTail) + kExternTail);
     const std::vector<char> bc((const char *)bitcode, (const char *)bitcode + bitcode_bytes);
     // (an empty parameter block is one byte of padding: the functor object cannot be empty)
     const unsigned char zero = 0;
@@ -879,7 +565,7 @@ int fd_f_compiled_destroy(void *fctx)
     if (!j) return FD_OK;
     (void)hipSetDevice(j->ctx->device);
     (void)hipStreamSynchronize(j->ctx->stream);
-    release_module(j->m);
+    g_modules.release(j->m);
     if (j->d_base) (void)hipFree(j->d_base);
     delete j;
     return FD_OK;

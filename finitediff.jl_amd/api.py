@@ -1697,6 +1697,51 @@ def matrix_colors(A):
     raise TypeError("matrix_colors: unsupported matrix type %r" % type(A).__name__)
 
 
+def _device_pattern_args(colptr, rowval, N, extra=()):
+    import torch
+    for t, what in ((colptr, "colptr"), (rowval, "rowval")) + tuple(extra):
+        if not (_is_torch(t) and t.is_cuda and t.is_contiguous() and t.dtype in (torch.int32, torch.int64)):
+            raise TypeError("%s must be a contiguous int32 / int64 CUDA tensor" % what)
+    if colptr.dtype != rowval.dtype:
+        raise TypeError("colptr and rowval must have the same integer type")
+    if colptr.numel() != N + 1:
+        raise ValueError("DimensionMismatch: length(colptr) != N + 1")
+    return rowval if rowval.numel() else rowval.new_zeros(1)      # (a pattern without entries: the C ABI still wants an address)
+
+
+def matrix_colors_device(M, N, colptr, rowval, idx_base=1, ctx=None, color_dtype=None):
+    """fd_color_columns_device: colour the columns of a CSC pattern that lives on the device -- `colptr`, `rowval` are torch
+    CUDA tensors (int32 or int64, `idx_base`-based).  Returns `(colorvec, ncolors)`: `colorvec` a CUDA tensor of `color_dtype`
+    (torch.int32 by default, or torch.int64) with colours 1..ncolors that goes straight into `make_plan_csc_device`.
+    Jones-Plassmann under a fixed priority: the result is the greedy colouring in order of descending priority, the same bits
+    on every call (include/fdjac.h).  For exact bands and stencils the closed forms (`matrix_colors` of a Tridiagonal /
+    BandedMatrix, `patterns.cyclic_colors`) use fewer colours."""
+    import torch
+    ctx = ctx or Context.default()
+    color_dtype = color_dtype or torch.int32
+    if color_dtype not in (torch.int32, torch.int64):
+        raise TypeError("color_dtype must be torch.int32 or torch.int64")
+    rowval = _device_pattern_args(colptr, rowval, int(N))
+    out = torch.empty(int(N), dtype=color_dtype, device=colptr.device)
+    nc = C.c_int64()
+    _l.check(ctx.L.fd_color_columns_device(ctx.handle, int(M), int(N), colptr.data_ptr(), rowval.data_ptr(), colptr.element_size(),
+                                           int(idx_base), out.data_ptr(), out.element_size(), C.byref(nc)))
+    return out, int(nc.value)
+
+
+def check_colors_device(M, N, colptr, rowval, colorvec, idx_base=1, ctx=None):
+    """fd_color_check_device: the number of rows in which two columns of the same non-zero colour meet (0: `colorvec` is a
+    valid colouring of the pattern).  All three arrays are torch CUDA tensors (int32 or int64)."""
+    ctx = ctx or Context.default()
+    rowval = _device_pattern_args(colptr, rowval, int(N), ((colorvec, "colorvec"),))
+    if colorvec.numel() != N:
+        raise ValueError("DimensionMismatch: length(colorvec) != length(x)")
+    bad = C.c_int64()
+    _l.check(ctx.L.fd_color_check_device(ctx.handle, int(M), int(N), colptr.data_ptr(), rowval.data_ptr(), colptr.element_size(),
+                                         int(idx_base), colorvec.data_ptr(), colorvec.element_size(), C.byref(bad)))
+    return int(bad.value)
+
+
 def finite_difference_jacobian(f, x, cache_or_fdtype="forward", returntype=np.float64, f_in=None, *, M=None,
                                relstep=None, absstep=None, colorvec=None, sparsity=None, jac_prototype=None,
                                dir=True, ctx=None):

@@ -272,7 +272,9 @@ __device__ __forceinline__ int eps_rescale_exp(double t, double relstep, double 
 //   FDJAC_SMALL (fused single-workgroup launches of small problems), FDJAC_LAZY_DIFF / FDJAC_LAZY_STORE (hand-over forms of the lazy
 //   launchers), FDJAC_EPS_CYCLIC (the step-size reduction's computed colours), FDJAC_BAND_DESC (computed tile
 //   descriptors), FDJAC_PLAN_DEVICE (host vs device plan builder), FDJAC_WINDOW / FDJAC_WINDOW2D / FDJAC_SORTED / FDJAC_WIN_TILE /
-//   FDJAC_WIN_PERIODIC / FDJAC_TILE_ORDER (which decompression kernel a hand-over plan compiles to).
+//   FDJAC_WIN_PERIODIC / FDJAC_TILE_ORDER (which decompression kernel a hand-over plan compiles to), FDJAC_COLOR_BATCH (rounds per
+//   read-back of the device colouring, 1..8) / FDJAC_COLOR_TAIL (0: no one-workgroup tail) / FDJAC_COLOR_STATS (1: one line of
+//   round and launch counts on stderr per fd_color_columns_device call).
 // They are read through this ONE function, and only in a process that opted in with FDJAC_TEST_SWITCHES=1 (tests/conftest.py sets it):
 // a production process ignores them altogether -- there every choice is the plan builder's.  (Operational variables are not gated:
 // FDJAC_RCCL_LIB, FDJAC_HIPRTC_LIB, FDJAC_P2P_TIMEOUT_MS, FDJAC_PLAN_THREADS, FDJAC_PLAN_TIMING.)

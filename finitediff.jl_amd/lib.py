@@ -70,7 +70,7 @@ EXPORTS = (
     "fd_stream_copy_gbps", "fd_plan_set_lazy_f", "fd_builtin_f_lazy", "fd_plan_set_lazy_caps", "fd_builtin_f_lazy_caps",
     "fd_jvp_plan_create", "fd_jvp_plan_destroy", "fd_jvp", "fd_jvp_async", "fd_jvp_get_epsilon",
     "fd_jvp_plan_set_lazy_f", "fd_builtin_f_lazy_jvp", "fd_jvp_plan_set_lazy_caps", "fd_builtin_f_lazy_jvp_caps",
-    "fd_color_columns_greedy", "fd_color_banded",
+    "fd_color_columns_greedy", "fd_color_banded", "fd_color_columns_device", "fd_color_check_device",
     "fd_comm_unique_id", "fd_comm_create", "fd_comm_destroy", "fd_comm_info", "fd_comm_library", "fd_comm_allgather",
     "fd_comm_gatherv", "fd_comm_allreduce_sum", "fd_comm_broadcast", "fd_comm_halo_exchange", "fd_comm_enable_p2p", "fd_comm_p2p_status", "fd_comm_disable_p2p", "fd_f_compile_rows", "fd_f_link_rows_bitcode", "fd_f_compiled_destroy", "fd_f_compiled_counts", "fd_f_compile_log", "fd_f_compile_terms", "fd_f_compiled_row_stores", "fd_plan_row_lists",
     "fd_p2p_create", "fd_p2p_create_loopback", "fd_p2p_loopback_fill", "fd_p2p_loopback_fill_fused", "fd_p2p_local_handle", "fd_p2p_connect", "fd_p2p_destroy", "fd_p2p_info", "fd_p2p_status", "fd_p2p_allgather",
@@ -217,6 +217,8 @@ def load():
     L.fd_jvp_get_epsilon.argtypes = [vp, C.POINTER(dbl)]
     L.fd_color_columns_greedy.argtypes = [i64, i64, vp, vp, i32, i32, C.POINTER(i64), C.POINTER(i64)]
     L.fd_color_banded.argtypes = [i64, i64, i64, C.POINTER(i64), C.POINTER(i64)]
+    L.fd_color_columns_device.argtypes = [vp, i64, i64, vp, vp, i32, i32, vp, i32, C.POINTER(i64)]
+    L.fd_color_check_device.argtypes = [vp, i64, i64, vp, vp, i32, i32, vp, i32, C.POINTER(i64)]
     L.fd_plan_set_lazy_f.argtypes = [vp, F_LAUNCH_LAZY]
     L.fd_builtin_f_lazy.argtypes = [vp, C.POINTER(F_LAUNCH_LAZY)]
     L.fd_plan_set_lazy_caps.argtypes = [vp, i32]

@@ -492,6 +492,30 @@ int fd_color_columns_greedy(int64_t M, int64_t N, const void *colptr, const void
                             int idx_base, int64_t *colorvec_out, int64_t *ncolors_out);
 /* Closed-form colouring of a band: colorvec[j] = mod1(j, l+u+1) (valid for any matrix inside the band). */
 int fd_color_banded(int64_t N, int64_t l, int64_t u, int64_t *colorvec_out, int64_t *ncolors_out);
+/* Jones-Plassmann colouring of the same graph ON THE DEVICE, for a pattern that already lives there (the arrays
+   fd_plan_create_csc_device takes: idx_bytes 4 or 8, idx_base 0 or 1; colptr / rowval are only read).  Nothing crosses PCIe
+   but a few counters.  The contract: every column j has the priority
+       prio(j) = fmix64(j + 0x9E3779B97F4A7C15 mod 2^64),   j 0-based,
+       fmix64(x): x ^= x >> 33; x *= 0xFF51AFD7ED558CCD; x ^= x >> 33; x *= 0xC4CEB9FE1A85EC53; x ^= x >> 33   (mod 2^64)
+   -- a bijection, so there are no ties -- and takes the smallest colour (1-based) that no conflicting column of HIGHER
+   priority uses.  The result equals the sequential greedy colouring taken in order of descending priority: a function of the
+   pattern alone, bit for bit the same on every call, whatever the grid, the number of rounds or the order in which columns
+   finish (tests/color_model.py restates it in numpy).  A column without entries gets colour 1.
+   colorvec_dev_out[N] (device; color_bytes 4 or 8) receives colours 1..C -- what fd_plan_create_csc_device accepts next;
+   *ncolors_out = C (may be NULL).  Enqueued on the context's stream; synchronous on return; the workspace (about 8 bytes per
+   stored entry + 20 per column + 8 per row) is allocated inside the call and freed before it returns.
+   On unstructured patterns the number of colours is that of the host greedy; on exact bands and stencils a random order costs
+   colours (tridiagonal: 5 against 3, 5-point: 11 against 7): prefer fd_color_banded / the closed forms there.  The cost grows
+   with the longest row: a row of d columns is a clique, needs d colours and d dependency levels under any greedy order; up to
+   4096 uncoloured columns the levels run inside ONE launch, beyond that every level is a launch.
+   FD_ERR_ARG (NULL, widths, base), FD_ERR_SHAPE (rowval outside 1..M, colptr not monotone: found on the device), FD_ERR_NOMEM. */
+int fd_color_columns_device(fd_ctx *ctx, int64_t M, int64_t N, const void *colptr_dev, const void *rowval_dev, int idx_bytes,
+                            int idx_base, void *colorvec_dev_out, int color_bytes, int64_t *ncolors_out);
+/* The number of rows in which two columns of the same non-zero colour meet (0 <=> a valid colouring; colours <= 0 =
+   uncoloured are ignored): a plan does not care whether its colouring is valid, and a caller whose pattern and colours live
+   on the device has no other way to find out.  colorvec_dev[N] is a device array (color_bytes 4 or 8).  Synchronous. */
+int fd_color_check_device(fd_ctx *ctx, int64_t M, int64_t N, const void *colptr_dev, const void *rowval_dev, int idx_bytes,
+                          int idx_base, const void *colorvec_dev, int color_bytes, int64_t *bad_rows_out);
 
 /* ---- multi-GPU (one process per GPU): the exchange steps behind the C ABI -------------------------------------------
  * The reference is single-process; these have no counterpart there.  A plan with a column window

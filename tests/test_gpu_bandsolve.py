@@ -1,33 +1,22 @@
 """The consumer for wider bands (round 6): fd_banded_solve_async -- (alpha I + beta J) y = b for a banded J (l, u <= 4) in the storage
 the banded plans write, block cyclic reduction on the device -- against SciPy's banded LU, and end to end behind a Jacobian the library
-has just computed."""
+has just computed.
+
+With gamma = 0.05 these systems couple unknowns over 8 to 29 rows (above 1e-11): from about the fourth reduction level up (k_bcr_top
+included) the blocks A', C' are below the tolerance -- tests/test_gpu_solve_longrange.py covers those levels."""
 import numpy as np
 import pytest
 import scipy.linalg
 
 import finitediff_jl_amd as fd
 from finitediff_jl_amd import patterns as P
+import solver_inputs as SI
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 
-def _band(N, l, u, rng, dominant=True):
-    """BandedMatrix data (l+u+1) x N column-major: data[u + i - j, j] = A[i, j]; slots outside the matrix hold 0."""
-    w = l + u + 1
-    data = rng.standard_normal((w, N))
-    for j in range(N):
-        for k in range(w):
-            i = j - u + k
-            if i < 0 or i >= N:
-                data[k, j] = 0.0
-    return data
-
-
-def _scipy_solve(data, N, l, u, alpha, beta, b):
-    ab = beta * data.copy()
-    ab[u, :] += alpha          # row u of the (l+u+1) x N band holds the diagonal (scipy's layout is BandedMatrices' layout)
-    return scipy.linalg.solve_banded((l, u), ab, b)
+_band, _scipy_solve = SI.band, SI.band_scipy_solve      # (tests/solver_inputs.py: shared with the CPU test of their reach)
 
 
 def _csc_values(data, N, l, u):
@@ -46,7 +35,7 @@ def test_banded_solve_matches_scipy(dtype, layout, N, l, u):
     rng = np.random.default_rng(N + 10 * l + u)
     data = _band(N, l, u, rng)
     b = rng.standard_normal(N)
-    gamma = 0.05                                   # W = I - gamma J: diagonally dominant for |J| ~ 1
+    gamma = SI.BAND_GAMMA                          # W = I - gamma J: diagonally dominant for |J| ~ 1
     data_t = data.astype(dtype)
     b_t = b.astype(dtype)
     ref = _scipy_solve(data_t.astype(np.float64), N, l, u, 1.0, -gamma, b_t.astype(np.float64))

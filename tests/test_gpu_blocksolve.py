@@ -1,6 +1,9 @@
 """The consumer for block-banded Jacobians (round 6): fd_blocktridiag_solve_async -- (alpha I + beta J) y = b for a block-tridiagonal J
 of dense b x b blocks in BlockBandedMatrix data, block cyclic reduction on the device -- against SciPy's sparse LU, and end to end
-behind the block-coupled Jacobian of BASELINE's config 5."""
+behind the block-coupled Jacobian of BASELINE's config 5.
+
+With gamma = 0.2 / (3 b) these systems couple unknowns over about 5 blocks (above 1e-11): from about the third reduction level up the
+coupling blocks are below the tolerance -- tests/test_gpu_solve_longrange.py covers those levels."""
 import numpy as np
 import pytest
 import scipy.sparse
@@ -8,6 +11,7 @@ import scipy.sparse.linalg
 
 import finitediff_jl_amd as fd
 from finitediff_jl_amd import patterns as P
+import solver_inputs as SI
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -34,11 +38,8 @@ def _sparse_from_data(lay, data, alpha, beta):
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 @pytest.mark.parametrize("nb,b", [(1, 32), (2, 32), (3, 8), (7, 32), (100, 32), (1000, 32), (333, 16), (64, 5), (4097, 4), (50, 1)])
 def test_block_tridiagonal_solve_matches_scipy(dtype, nb, b):
-    rng = np.random.default_rng(nb + b)
     lay = P.BlockBandedLayout([b] * nb, 1, 1)
-    data = rng.standard_normal(lay.data_len).astype(dtype)
-    rhs = rng.standard_normal(nb * b).astype(dtype)
-    gamma = 0.2 / (3 * b)                                  # I - gamma J: rows of ~3b entries of size ~1 stay diagonally dominant
+    data, rhs, gamma = SI.block_system(nb, b, lay.data_len, dtype)      # (tests/solver_inputs.py: shared with the CPU test of their reach)
     A = _sparse_from_data(lay, data.astype(np.float64), 1.0, -gamma)
     ref = scipy.sparse.linalg.spsolve(A, rhs.astype(np.float64))
     Jd = torch.as_tensor(data, device="cuda")

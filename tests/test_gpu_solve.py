@@ -4,7 +4,11 @@
 whole and sharded by column ranges (the shards run one after the other on the one GPU; the packet exchange of the
 multi-GPU solve is replaced by writing the packets into one tensor -- the single-rank communicator test covers the RCCL
 call itself), and end to end: coloured Jacobian on the device -> solve, nothing copied in between
-(test/downstream/ordinarydiffeq_tridiagonal_solve.jl:18-30: a Rosenbrock step with a Tridiagonal jac_prototype)."""
+(test/downstream/ordinarydiffeq_tridiagonal_solve.jl:18-30: a Rosenbrock step with a Tridiagonal jac_prototype).
+
+The random strongly dominant systems here couple unknowns over about 9 rows (above 1e-11): the reduced systems from the second level
+up are numerically diagonal, so these tests check the level-0 / level-1 arithmetic and the indexing of the upper levels, not their
+couplings -- tests/test_gpu_solve_longrange.py does that."""
 import numpy as np
 import pytest
 from scipy.linalg import solve_banded
@@ -12,6 +16,7 @@ from scipy.linalg import solve_banded
 import finitediff_jl_amd as fd
 from finitediff_jl_amd import patterns as P
 from finitediff_jl_amd import sharded as S
+import solver_inputs as SI
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -21,24 +26,7 @@ def _dev(a, dtype=torch.float64):
     return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype, device="cuda")
 
 
-def _system(N, seed, dominance=0.2):
-    rng = np.random.default_rng(seed)
-    dl, du = rng.random(max(N - 1, 0)) - 0.5, rng.random(max(N - 1, 0)) - 0.5
-    d = rng.random(N) - 0.5
-    # alpha*I + beta*J strictly diagonally dominant: |alpha + beta d_i| >= |beta|(|dl| + |du|) + dominance
-    beta = -0.7
-    alpha = 0.7 * (0.5 + 1.0) + dominance + 0.5
-    b = rng.random(N) - 0.5
-    return dl, d, du, b, alpha, beta
-
-
-def _reference(dl, d, du, b, alpha, beta):
-    N = d.size
-    ab = np.zeros((3, N))
-    ab[0, 1:] = beta * du
-    ab[1, :] = alpha + beta * d
-    ab[2, :-1] = beta * dl
-    return solve_banded((1, 1), ab, b)
+_system, _reference = SI.tridiag_system, SI.tridiag_reference      # (tests/solver_inputs.py: shared with the CPU test of their reach)
 
 
 def _csc_nzval(dl, d, du):
@@ -71,7 +59,8 @@ def _csc_nzval_fast(dl, d, du):
 @pytest.mark.parametrize("N", [1, 2, 3, 7, 8, 9, 63, 64, 65, 511, 512, 513, 2047, 2048, 2049, 2113, 4095, 4096, 4097, 16385, 32769,
                                100003, 262143, 262144, 262145, 10 ** 6, 3 * 10 ** 6 + 1])
 def test_tridiagonal_solve_matches_scipy(layout, N):
-    # sizes around every tile / level boundary (tiles of 2048 rows, a factor of 8 per level, <= 512 rows at the top)
+    # sizes around every tile / level boundary (tiles of 2048 rows, a factor of 8 per level, <= 512 rows at the top): with couplings that
+    # vanish beyond ~9 rows this checks that the indexing there yields no NaN / misplaced row, not the values the upper levels compute
     dl, d, du, b, alpha, beta = _system(N, 100 + N)
     want = _reference(dl, d, du, b, alpha, beta)
     y = torch.full((N,), float("nan"), dtype=torch.float64, device="cuda")
@@ -159,7 +148,7 @@ def test_sharded_solve_equals_global_solve(layout, N, W):
 
 @pytest.mark.parametrize("seed", range(16))
 def test_solver_randomised(seed):
-    # random sizes (around every tile / level boundary by chance), layouts, shifts and rank counts with UNEVEN cuts: whole and sharded
+    # random sizes (near a tile / level boundary only by chance), layouts, shifts and rank counts with UNEVEN cuts: whole and sharded
     # solves against SciPy's banded solve; the sharded pieces go through the two-levels-per-launch schedule whenever a rank's rows allow
     rng = np.random.default_rng(5000 + seed)
     N = int(rng.choice([rng.integers(1, 70), rng.integers(500, 5000), rng.integers(4000, 70000), rng.integers(250000, 600000)]))

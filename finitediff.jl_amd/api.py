@@ -584,6 +584,90 @@ class BandedSolver:
         return v.value
 
 
+class CscSolver:
+    """fd_csc_solver: the sparse consumer.  For a square J in ``SparseMatrixCSC`` storage -- the nzval a CSC plan has just written, left
+    on the device -- ``matvec`` enqueues y = (alpha*I + beta*J) v (or its transpose) and ``solve`` enqueues y = (alpha*I + beta*J)^-1 b by
+    Jacobi-preconditioned BiCGStab whose scalars never leave the device.  ``pattern`` is a ``SparseMatrixCSC`` / ``DevicePatternCSC`` or
+    ``(colptr, rowval, N)`` with numpy arrays or CUDA tensors of int32 / int64 (``idx_base``-based).  A solve that does not converge
+    within ``max_iterations`` (``status()`` flags bit 0) or breaks down (bit 1) fills y with NaN unless ``set_policy(True)``."""
+
+    def __init__(self, pattern, ctx=None, dtype=np.float64, idx_base=1):
+        self.ctx = ctx or Context.default()
+        self.dtype = np.dtype(dtype)
+        self.Lt = _l.typed(self.ctx.L, self.dtype)
+        if isinstance(pattern, (SparseMatrixCSC, DevicePatternCSC)):
+            if pattern.m != pattern.n:
+                raise ValueError("the sparse solver takes a square pattern")
+            colptr, rowval, N = pattern.colptr, pattern.rowval, pattern.n
+            idx_base = getattr(pattern, "idx_base", 1)
+        else:
+            colptr, rowval, N = pattern
+        dev = _is_torch(colptr) and colptr.is_cuda
+        if dev:
+            if not (_is_torch(rowval) and rowval.is_cuda) or rowval.dtype != colptr.dtype or colptr.element_size() not in (4, 8):
+                raise TypeError("colptr and rowval must be CUDA tensors of one integer type (int32 or int64)")
+            colptr, rowval = colptr.contiguous(), rowval.contiguous()
+            ib, pc, pr = colptr.element_size(), colptr.data_ptr(), rowval.data_ptr()
+        else:
+            colptr = np.ascontiguousarray(colptr.numpy() if _is_torch(colptr) else colptr)
+            rowval = np.ascontiguousarray(rowval.numpy() if _is_torch(rowval) else rowval)
+            if colptr.dtype not in (np.int32, np.int64) or rowval.dtype != colptr.dtype:
+                raise TypeError("colptr and rowval must be int32 or int64 arrays of one type")
+            ib, pc, pr = colptr.dtype.itemsize, colptr.ctypes.data, rowval.ctypes.data
+        if colptr.shape[0] != int(N) + 1:
+            raise ValueError("colptr must hold N + 1 entries")
+        h = C.c_void_p()
+        _l.check(self.Lt.fd_csc_solver_create(self.ctx.handle, int(N), pc, pr or None, ib, int(idx_base), _l.DEVICE if dev else _l.HOST, C.byref(h)))
+        self.handle, self.N = h, int(N)
+        self._fin = weakref.finalize(self, self.Lt.fd_csc_solver_destroy, h)
+
+    def _dev(self, a, what):
+        p, k, _keep = _ptr(a, what, self.dtype)
+        if k != _l.DEVICE:
+            raise ValueError("the solver takes device arrays")
+        return p
+
+    def _vals(self, J):
+        return self._dev(J.nzval if isinstance(J, (SparseMatrixCSC, DevicePatternCSC)) else J, "J")
+
+    def matvec(self, J, v, y, alpha=0.0, beta=1.0, transpose=False):
+        """Enqueue y = (alpha*I + beta*J) v, or its transpose, on the context's stream (fd_csc_matvec_async)."""
+        _l.check(self.Lt.fd_csc_matvec_async(self.handle, float(alpha), float(beta), self._vals(J), self._dev(v, "v"), self._dev(y, "y"),
+                                             1 if transpose else 0))
+
+    def solve(self, J, b, y, alpha=1.0, beta=-1.0):
+        """Enqueue y = (alpha*I + beta*J)^-1 b on the context's stream (fd_csc_solve_async)."""
+        _l.check(self.Lt.fd_csc_solve_async(self.handle, float(alpha), float(beta), self._vals(J), self._dev(b, "b"), self._dev(y, "y")))
+
+    def set_options(self, rtol=1e-10, max_iterations=500):
+        _l.check(self.Lt.fd_csc_solver_set_options(self.handle, float(rtol), int(max_iterations)))
+
+    def set_policy(self, keep_unconverged):
+        _l.check(self.Lt.fd_csc_solver_set_policy(self.handle, 1 if keep_unconverged else 0))
+
+    def status(self):
+        """Synchronises.  {"flags": bit 0 not converged | bit 1 breakdown, "iterations", "resid": ||r||_2 of the recurrence, "bnorm"}."""
+        f, it, r, bn = C.c_int(), C.c_int64(), C.c_double(), C.c_double()
+        _l.check(self.Lt.fd_csc_solver_status(self.handle, C.byref(f), C.byref(it), C.byref(r), C.byref(bn)))
+        return {"flags": f.value, "iterations": it.value, "resid": r.value, "bnorm": bn.value}
+
+    def row_lists(self):
+        """The solver's lists as int32 CUDA tensors (copies): row_ptr, row_col, row_slot, diag_slot; and the number of long rows."""
+        import torch
+        ps = [C.c_void_p() for _ in range(4)]
+        nnz, nlong = C.c_int64(), C.c_int64()
+        _l.check(self.Lt.fd_csc_solver_row_lists(self.handle, *[C.byref(p) for p in ps], C.byref(nnz), C.byref(nlong)))
+        out = []
+        for p, n in zip(ps, (self.N + 1, nnz.value, nnz.value, self.N)):
+            if n == 0:
+                out.append(torch.empty(0, dtype=torch.int32, device="cuda:%d" % self.ctx.device))
+                continue
+            view = _DevView(p.value, n, False)
+            view.__cuda_array_interface__["typestr"] = "<i4"
+            out.append(torch.as_tensor(view, device="cuda:%d" % self.ctx.device).clone())
+        return out + [nlong.value]
+
+
 class BlockTridiagSolver:
     """fd_blocktridiag_solver: (alpha*I + beta*J) y = b on the device for a block-tridiagonal J of ``nblk`` dense ``b x b`` blocks
     (b <= 32) in ``BlockBandedMatrix`` data (block bandwidths (1, 1), uniform block sizes) -- the storage a block-banded plan fills

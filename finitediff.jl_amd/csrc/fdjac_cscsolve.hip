@@ -1,0 +1,810 @@
+// The SPARSE consumer ("sparse solve in the Newton/Rosenbrock step"): for a square J in SparseMatrixCSC storage,
+// on the nzval a CSC plan has just written,
+//     y = (alpha I + beta J) v,   y = (alpha I + beta J)^T v,   and   (alpha I + beta J) y = b   by Jacobi-preconditioned BiCGStab.
+// DESIGN.md 4.9 has the contract; tests/csc_solve_model.py restates every summation order below in numpy and the GPU tests compare bits.
+//
+// CREATE (device): colptr / rowval are converted to 0-based Int32 and validated; every entry finds its column by a binary search in
+// colptr and joins its row (counts by integer atomics, an exclusive scan, a fill pass whose order depends on the atomics' arrival);
+// every row's segment is then SORTED by slot -- storage order is column order, so the lists equal a host counting sort's whatever
+// the arrival order was.  Rows of more than kCsLong entries go on a list of their own.  A row order per tile of 256 rows (descending
+// length, ties by row) deals lanes to rows of similar length.
+//
+// ORDERS.  Row r of at most kCsLong entries: acc = 0; acc += nzval[slot_k] * v[col_k] for k ascending; y_r = alpha v_r + beta acc.
+// A longer row is summed by ONE workgroup: thread t adds the entries k = t, t + 256, ... in that order, then block_sum().
+// block_sum(): in every wavefront x += shfl_down(x, 32), 16, 8, 4, 2, 1; then ((w0 + w1) + w2) + w3.
+// A dot over N elements: tiles of kCsVecTile (vector kernels: thread t adds elements t, t + 256, t + 512, t + 768 of its tile) or of 256
+// (product kernels: element t), block_sum() per tile, and the LAST-ARRIVING workgroup (an integer ticket) adds the tiles' sums: thread t
+// adds sums t, t + 256, ... in order, then block_sum().  No floating-point atomics; every order is a function of N alone.  All
+// arithmetic is Float64 for either element type, and nothing is contracted into an FMA.
+#include "fdjac_internal.h"
+#include "fdjac_device.h"
+#include <cmath>
+#include <cstring>
+#include <new>
+
+namespace fdjac {
+
+constexpr int kCsLong = 32;            // rows of more entries than this are summed by a workgroup each
+constexpr int kCsVecTile = 1024;       // elements per workgroup of the vector kernels
+constexpr int kCsWinHalo = 1920;       // the LDS window of v (the tile's 256 rows + the reach on either side) is used up to this reach
+constexpr int kCsBatchDefault = 8;     // iterations enqueued per record read back
+enum { CS_BAD_COLPTR = 1, CS_BAD_ROW = 2, CS_BAD_ORDER = 4 };
+// scalars of a solve, in device memory: doubles ...
+enum { S_RHO = 0, S_RHO_OLD, S_ALPHA, S_OMEGA, S_BNORM2, S_TOL2, S_RNORM2, S_SNORM2, S_NSCAL };
+// ... and words
+enum { W_DONE = 0, W_EARLY, W_FLAGS, W_ITERS, W_TICKET, W_FINAL, W_NWORDS = 8 };
+
+struct CsRecord { int done, early, flags, iters; };       // what the host reads per batch (the first four words)
+
+struct CsPat {                         // the pattern as the kernels see it
+    int N, nnz, nlong, reach, window;
+    const int *colptr, *rowval, *row_ptr, *row_col, *row_slot, *order, *long_rows, *diag;
+};
+
+__device__ __forceinline__ int64_t cs_load(const void *p, int bytes, int64_t i)
+{
+    return bytes == 8 ? ((const int64_t *)p)[i] : (int64_t)((const int32_t *)p)[i];
+}
+__device__ __forceinline__ bool cs_bad_pivot(double x) { return !(fabs(x) > 0.0 && fabs(x) < __builtin_huge_val()); }
+__device__ __forceinline__ int cs_word(const int *w, int i) { return __hip_atomic_load(w + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// ---- create ------------------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(kBlock) k_cs_colptr(const void *__restrict__ colptr, int ib, int base, int64_t N, int64_t nnz,
+                                                      int *__restrict__ cptr, unsigned *err)
+{
+    bool bad = false;
+    for (int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x; j <= N; j += (int64_t)gridDim.x * kBlock) {
+        const int64_t a = cs_load(colptr, ib, j) - base;
+        if (j < N) bad = bad || a > cs_load(colptr, ib, j + 1) - base;
+        bad = bad || a < 0 || a > nnz || (j == 0 && a != 0) || (j == N && a != nnz);
+        cptr[j] = (int)(a < 0 ? 0 : (a > nnz ? nnz : a));
+    }
+    if (bad) atomicOr(err, (unsigned)CS_BAD_COLPTR);
+}
+
+// one lane per entry: its row (validated, 0-based), its column (binary search in the monotone cptr), rows strictly ascending within
+// the column, the row's count, the diagonal's slot and the pattern's reach
+__global__ void __launch_bounds__(kBlock) k_cs_entries(const void *__restrict__ rowval, int ib, int base, const int *__restrict__ cptr,
+                                                       int64_t N, int64_t nnz, int *__restrict__ erow, int *__restrict__ ecol,
+                                                       int *__restrict__ rcnt, int *__restrict__ diag, int *reach, unsigned *err)
+{
+    for (int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x; q < nnz; q += (int64_t)gridDim.x * kBlock) {
+        const int64_t r = cs_load(rowval, ib, q) - base;
+        const bool ok = r >= 0 && r < N;
+        int64_t lo = 0, hi = N;      // cptr[lo] <= q < cptr[hi]
+        while (hi - lo > 1) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (cptr[mid] <= q) lo = mid; else hi = mid;
+        }
+        erow[q] = ok ? (int)r : 0;
+        ecol[q] = (int)lo;
+        if (!ok) { atomicOr(err, (unsigned)CS_BAD_ROW); continue; }
+        if (q > cptr[lo] && cs_load(rowval, ib, q - 1) - base >= r) atomicOr(err, (unsigned)CS_BAD_ORDER);
+        atomicAdd(&rcnt[r], 1);
+        if (r == lo) diag[lo] = (int)q;
+        const int d = (int)(r > lo ? r - lo : lo - r);
+        if (d > 0) atomicMax(reach, d);
+    }
+}
+
+constexpr int kCsScanPer = 8, kCsScanTile = kBlock * kCsScanPer;
+__device__ __forceinline__ int cs_block_exscan(int v, int *s_w, int &total)
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int inc = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int t = __shfl_up(inc, off, 64);
+        if (lane >= off) inc += t;
+    }
+    __syncthreads();
+    if (lane == 63) s_w[w] = inc;
+    __syncthreads();
+    int before = 0;
+    total = 0;
+#pragma unroll
+    for (int i = 0; i < kBlock / 64; ++i) {
+        if (i < w) before += s_w[i];
+        total += s_w[i];
+    }
+    return before + inc - v;
+}
+__global__ void __launch_bounds__(kBlock) k_cs_scan_sums(const int *__restrict__ in, int64_t n, int *__restrict__ bsum)
+{
+    __shared__ int s_w[kBlock / 64];
+    const int64_t i0 = (int64_t)blockIdx.x * kCsScanTile + (int64_t)threadIdx.x * kCsScanPer;
+    int s = 0;
+#pragma unroll
+    for (int k = 0; k < kCsScanPer; ++k) s += i0 + k < n ? in[i0 + k] : 0;
+    int total;
+    (void)cs_block_exscan(s, s_w, total);
+    if (threadIdx.x == 0) bsum[blockIdx.x] = total;
+}
+__global__ void __launch_bounds__(kBlock) k_cs_scan_top(int *__restrict__ bsum, int64_t nb)      // in place; bsum[nb] = the total
+{
+    __shared__ int s_w[kBlock / 64];
+    int carry = 0;
+    for (int64_t b0 = 0; b0 < nb; b0 += kBlock) {
+        const int64_t i = b0 + threadIdx.x;
+        const int v = i < nb ? bsum[i] : 0;
+        int total;
+        const int ex = cs_block_exscan(v, s_w, total);
+        if (i < nb) bsum[i] = carry + ex;
+        carry += total;
+    }
+    if (threadIdx.x == 0) bsum[nb] = carry;
+}
+__global__ void __launch_bounds__(kBlock) k_cs_scan_apply(const int *__restrict__ in, int64_t n, const int *__restrict__ bsum, int64_t nb,
+                                                          int *__restrict__ out)
+{
+    __shared__ int s_w[kBlock / 64];
+    const int64_t i0 = (int64_t)blockIdx.x * kCsScanTile + (int64_t)threadIdx.x * kCsScanPer;
+    int v[kCsScanPer], s = 0;
+#pragma unroll
+    for (int k = 0; k < kCsScanPer; ++k) {
+        v[k] = i0 + k < n ? in[i0 + k] : 0;
+        s += v[k];
+    }
+    int total;
+    int run = bsum[blockIdx.x] + cs_block_exscan(s, s_w, total);
+#pragma unroll
+    for (int k = 0; k < kCsScanPer; ++k) {
+        if (i0 + k < n) out[i0 + k] = run;
+        run += v[k];
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) out[n] = bsum[nb];
+}
+
+// the fill pass: slot q joins its row at the position an atomic cursor hands out (any order: the segments are sorted next)
+__global__ void __launch_bounds__(kBlock) k_cs_fill(const int *__restrict__ erow, int64_t nnz, const int *__restrict__ rptr,
+                                                    int *__restrict__ cursor, int *__restrict__ rslot)
+{
+    for (int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x; q < nnz; q += (int64_t)gridDim.x * kBlock) {
+        const int r = erow[q];
+        rslot[rptr[r] + atomicAdd(&cursor[r], 1)] = (int)q;
+    }
+}
+// short rows: one lane ranks every slot of its row among the row's (slots are distinct; at most kCsLong^2 compares, no private array),
+// parks the sorted slots in the row's segment of rcol, then writes slots and columns; long rows are counted
+__global__ void __launch_bounds__(kBlock) k_cs_sort_short(const int *__restrict__ rptr, int64_t N, int *rslot, const int *__restrict__ ecol,
+                                                          int *rcol, int *nlong)
+{
+    const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (r >= N) return;
+    const int a = rptr[r], n = rptr[r + 1] - a;
+    if (n > kCsLong) { atomicAdd(nlong, 1); return; }
+    for (int k = 0; k < n; ++k) {
+        const int v = rslot[a + k];
+        int rank = 0;
+        for (int i = 0; i < n; ++i) rank += rslot[a + i] < v ? 1 : 0;
+        rcol[a + rank] = v;
+    }
+    for (int k = 0; k < n; ++k) {
+        const int v = rcol[a + k];
+        rslot[a + k] = v;
+        rcol[a + k] = ecol[v];
+    }
+}
+__global__ void __launch_bounds__(kBlock) k_cs_list_long(const int *__restrict__ rptr, int64_t N, int *__restrict__ list, int *cnt)
+{
+    const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (r < N && rptr[r + 1] - rptr[r] > kCsLong) list[atomicAdd(cnt, 1)] = (int)r;
+}
+// long rows: one workgroup per row ranks every slot among the row's (slots are distinct) into tmp, then copies back
+__global__ void __launch_bounds__(kBlock) k_cs_sort_long(const int *__restrict__ rptr, const int *__restrict__ list, int *__restrict__ rslot,
+                                                         int *__restrict__ tmp, const int *__restrict__ ecol, int *__restrict__ rcol)
+{
+    const int r = list[blockIdx.x], a = rptr[r], n = rptr[r + 1] - a;
+    for (int k = threadIdx.x; k < n; k += kBlock) {
+        const int v = rslot[a + k];
+        int rank = 0;
+        for (int i = 0; i < n; ++i) rank += rslot[a + i] < v ? 1 : 0;
+        tmp[a + rank] = v;
+    }
+    __threadfence_block();
+    __syncthreads();
+    for (int k = threadIdx.x; k < n; k += kBlock) {
+        const int v = tmp[a + k];
+        rslot[a + k] = v;
+        rcol[a + k] = ecol[v];
+    }
+}
+// the lanes' rows: within every tile of 256 rows, descending length (capped at kCsLong + 1), ties by ascending row
+__global__ void __launch_bounds__(kBlock) k_cs_order(const int *__restrict__ rptr, int64_t N, int *__restrict__ order)
+{
+    __shared__ int s_len[kBlock];
+    const int64_t r0 = (int64_t)blockIdx.x * kBlock, r = r0 + threadIdx.x;
+    int len = -1;
+    if (r < N) { len = rptr[r + 1] - rptr[r]; if (len > kCsLong) len = kCsLong + 1; }
+    s_len[threadIdx.x] = len;
+    __syncthreads();
+    int rank = 0;
+    for (int u = 0; u < kBlock; ++u) {
+        const int lu = s_len[u];
+        rank += (lu > len || (lu == len && u < (int)threadIdx.x)) ? 1 : 0;
+    }
+    order[r0 + rank] = r < N ? (int)r : -1;
+}
+
+// ---- sums ----------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double cs_block_sum(double x, double *s_w)      // the result is valid in thread 0
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) x = x + __shfl_down(x, off, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = x;
+    __syncthreads();
+    return ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
+}
+// ND dots of one kernel: this workgroup's sums go to part[d * nb + block]; the last workgroup to arrive (ticket) adds every dot's
+// partial sums in order and returns true in all its threads with the totals in out[] (valid in thread 0)
+template <int ND>
+__device__ __forceinline__ bool cs_finish(const double (&mine)[ND], double *part, int *words, double (&out)[ND], double *s_w)
+{
+    __shared__ int s_last;
+    const int nb = gridDim.x;
+    for (int d = 0; d < ND; ++d) {
+        const double t = cs_block_sum(mine[d], s_w);
+        if (threadIdx.x == 0) part[(size_t)d * nb + blockIdx.x] = t;
+    }
+    if (threadIdx.x == 0) {
+        __threadfence();
+        const int old = __hip_atomic_fetch_add(words + W_TICKET, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        s_last = old == nb - 1;
+        if (s_last) __hip_atomic_store(words + W_TICKET, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    if (!s_last) return false;
+    __threadfence();
+    for (int d = 0; d < ND; ++d) {
+        double acc = 0.0;
+        for (int k = threadIdx.x; k < nb; k += kBlock)
+            acc += __hip_atomic_load(part + (size_t)d * nb + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        out[d] = cs_block_sum(acc, s_w);
+    }
+    return true;
+}
+
+// ---- products --------------------------------------------------------------------------------------------------------------------------
+// long rows first: workgroup i sums row long_rows[i] and writes y there; the row kernel then takes those values from y
+template <typename TV>
+__global__ void __launch_bounds__(kBlock) k_cs_long(CsPat P, double alpha, double beta, const real_t *__restrict__ nz,
+                                                    const TV *__restrict__ v, TV *__restrict__ y, const int *words)
+{
+    __shared__ double s_w[kBlock / 64];
+    if (words && cs_word(words, W_DONE)) return;
+    const int r = P.long_rows[blockIdx.x], a = P.row_ptr[r], n = P.row_ptr[r + 1] - a;
+    double acc = 0.0;
+    for (int k = threadIdx.x; k < n; k += kBlock) acc += (double)nz[P.row_slot[a + k]] * (double)v[P.row_col[a + k]];
+    const double t = cs_block_sum(acc, s_w);
+    if (threadIdx.x == 0) y[r] = (TV)(alpha * (double)v[r] + beta * t);
+}
+
+// rows: a tile of 256 rows per workgroup, lane i takes row order[tile * 256 + i]; when the pattern's reach is at most kCsWinHalo, v
+// goes through an LDS window of the tile's rows and `reach` elements on either side (anything outside it is read from memory: the
+// bits do not depend on the window); a wider pattern reads v from memory; the results cross LDS once so that y is
+// written -- and the dots are summed -- in row order.  MODE 0: y only.  1: + dot(c, y) -> alpha (the first product of an
+// iteration).  2: + dot(y, c), dot(y, y) -> omega (the second).
+template <typename TV, int MODE>
+__global__ void __launch_bounds__(kBlock) k_cs_rows(CsPat P, double alpha, double beta, const real_t *__restrict__ nz, const TV *__restrict__ v,
+                                                    TV *__restrict__ y, const double *__restrict__ c, double *scal, int *words, double *part)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
+    __shared__ double s_out[kBlock];
+    __shared__ double s_w[kBlock / 64];
+    if (MODE != 0 && (cs_word(words, W_DONE) || (MODE == 2 && cs_word(words, W_EARLY)))) return;
+    TV *s_v = (TV *)s_raw;
+    const int ntile = (P.N + kBlock - 1) / kBlock;
+    const int tile = MODE == 0 ? (int)fd_xcd_block(blockIdx.x, ntile) : (int)blockIdx.x;
+    if (tile >= ntile) return;
+    const int r0 = tile * kBlock;
+    int w0 = 0, w1 = 0;
+    if (P.window) {
+        const int h = P.reach;
+        w0 = r0 - h > 0 ? r0 - h : 0;
+        w1 = r0 + kBlock + h < P.N ? r0 + kBlock + h : P.N;
+        for (int i = w0 + threadIdx.x; i < w1; i += kBlock) s_v[i - w0] = v[i];
+        __syncthreads();
+    }
+    const int r = P.order[r0 + threadIdx.x];
+    if (r >= 0) {
+        const int a = P.row_ptr[r], n = P.row_ptr[r + 1] - a;
+        if (n <= kCsLong) {
+            double acc = 0.0;
+            for (int k0 = 0; k0 < n; k0 += 8) {      // eight entries' gathers requested before the first is used
+                double pa[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pv[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    if (k0 + k < n) {
+                        const int col = P.row_col[a + k0 + k];
+                        pa[k] = (double)nz[P.row_slot[a + k0 + k]];
+                        pv[k] = (col >= w0 && col < w1) ? (double)s_v[col - w0] : (double)v[col];
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < 8; ++k) if (k0 + k < n) acc += pa[k] * pv[k];
+            }
+            const double vr = (r >= w0 && r < w1) ? (double)s_v[r - w0] : (double)v[r];
+            s_out[r - r0] = alpha * vr + beta * acc;
+        } else {
+            s_out[r - r0] = (double)y[r];         // k_cs_long has written it
+        }
+    }
+    __syncthreads();
+    const int row = r0 + threadIdx.x;
+    double yr = 0.0;
+    if (row < P.N) {
+        yr = s_out[threadIdx.x];
+        y[row] = (TV)yr;
+    }
+    if (MODE == 1) {
+        double mine[1] = {row < P.N ? c[row] * yr : 0.0}, tot[1];
+        if (cs_finish<1>(mine, part, words, tot, s_w) && threadIdx.x == 0) {
+            if (cs_bad_pivot(tot[0])) { atomicOr(words + W_FLAGS, 2); __hip_atomic_store(words + W_DONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+            else scal[S_ALPHA] = scal[S_RHO] / tot[0];
+        }
+    } else if (MODE == 2) {
+        double mine[2] = {row < P.N ? yr * c[row] : 0.0, row < P.N ? yr * yr : 0.0}, tot[2];
+        if (cs_finish<2>(mine, part, words, tot, s_w) && threadIdx.x == 0) {
+            if (cs_bad_pivot(tot[1])) { atomicOr(words + W_FLAGS, 2); __hip_atomic_store(words + W_DONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+            else scal[S_OMEGA] = tot[0] / tot[1];
+        }
+    }
+}
+
+// the transposed product on the CSC arrays as they are: one lane per column, storage order
+__global__ void __launch_bounds__(kBlock) k_cs_cols(CsPat P, double alpha, double beta, const real_t *__restrict__ nz, const real_t *__restrict__ v,
+                                                    real_t *__restrict__ y)
+{
+    const int nb = (P.N + kBlock - 1) / kBlock, b = (int)fd_xcd_block(blockIdx.x, nb);
+    const int j = b * kBlock + threadIdx.x;
+    if (b >= nb || j >= P.N) return;
+    double acc = 0.0;
+    for (int q = P.colptr[j]; q < P.colptr[j + 1]; ++q) acc += (double)nz[q] * (double)v[P.rowval[q]];
+    y[j] = (real_t)(alpha * (double)v[j] + beta * acc);
+}
+
+// ---- BiCGStab ------------------------------------------------------------------------------------------------------------------------
+struct CsVecs { double *r, *rhat, *p, *v, *s, *t, *ph, *sh, *y, *d; };
+
+// the start: d = alpha + beta J_ii, r = rhat = b, p = v = y = 0, rho = ||b||^2
+__global__ void __launch_bounds__(kBlock) k_cs_init(CsPat P, CsVecs V, double alpha, double beta, const real_t *__restrict__ nz,
+                                                    const real_t *__restrict__ b, double rtol, double *scal, int *words, double *part)
+{
+    __shared__ double s_w[kBlock / 64];
+    const int i0 = blockIdx.x * kCsVecTile + threadIdx.x;
+    double mine[1] = {0.0}, tot[1];
+    bool bad = false;
+    for (int k = 0; k < kCsVecTile / kBlock; ++k) {
+        const int i = i0 + k * kBlock;
+        if (i >= P.N) continue;
+        const int q = P.diag[i];
+        const double d = q >= 0 ? alpha + beta * (double)nz[q] : alpha, bi = (double)b[i];
+        bad = bad || cs_bad_pivot(d);
+        V.d[i] = d; V.r[i] = bi; V.rhat[i] = bi; V.p[i] = 0.0; V.v[i] = 0.0; V.y[i] = 0.0;
+        mine[0] += bi * bi;
+    }
+    if (bad) atomicOr(words + W_FLAGS, 2);
+    if (cs_finish<1>(mine, part, words, tot, s_w) && threadIdx.x == 0) {
+        scal[S_RHO] = tot[0]; scal[S_RHO_OLD] = 1.0; scal[S_ALPHA] = 1.0; scal[S_OMEGA] = 1.0;
+        scal[S_BNORM2] = tot[0]; scal[S_RNORM2] = tot[0]; scal[S_SNORM2] = 0.0;
+        scal[S_TOL2] = (rtol * rtol) * tot[0];
+        int done = 0;
+        if (tot[0] == 0.0) done = 1;                                              // b = 0: y = 0, no iteration
+        else if (cs_word(words, W_FLAGS) & 2) done = 1;                           // a Jacobi diagonal that is zero or not finite
+        else if (cs_bad_pivot(tot[0])) { atomicOr(words + W_FLAGS, 2); done = 1; }   // rho
+        if (done) __hip_atomic_store(words + W_DONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+// p = r + beta (p - omega v), ph = p / d
+__global__ void __launch_bounds__(kBlock) k_cs_p(int N, CsVecs V, const double *scal, const int *words)
+{
+    if (cs_word(words, W_DONE)) return;
+    const double bk = (scal[S_RHO] / scal[S_RHO_OLD]) * (scal[S_ALPHA] / scal[S_OMEGA]), om = scal[S_OMEGA];
+    const int i0 = blockIdx.x * kCsVecTile + threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < kCsVecTile / kBlock; ++k) {
+        const int i = i0 + k * kBlock;
+        if (i >= N) continue;
+        const double p = V.r[i] + bk * (V.p[i] - om * V.v[i]);
+        V.p[i] = p;
+        V.ph[i] = p / V.d[i];
+    }
+}
+// s = r - alpha v, sh = s / d, ||s||^2; ||s||^2 <= tol^2 ends the iteration early (W_EARLY)
+__global__ void __launch_bounds__(kBlock) k_cs_s(int N, CsVecs V, double *scal, int *words, double *part)
+{
+    __shared__ double s_w[kBlock / 64];
+    if (cs_word(words, W_DONE)) return;
+    const double al = scal[S_ALPHA];
+    const int i0 = blockIdx.x * kCsVecTile + threadIdx.x;
+    double mine[1] = {0.0}, tot[1];
+#pragma unroll
+    for (int k = 0; k < kCsVecTile / kBlock; ++k) {
+        const int i = i0 + k * kBlock;
+        if (i >= N) continue;
+        const double s = V.r[i] - al * V.v[i];
+        V.s[i] = s;
+        V.sh[i] = s / V.d[i];
+        mine[0] += s * s;
+    }
+    if (cs_finish<1>(mine, part, words, tot, s_w) && threadIdx.x == 0) {
+        scal[S_SNORM2] = tot[0];
+        if (tot[0] <= scal[S_TOL2]) __hip_atomic_store(words + W_EARLY, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+// y += alpha ph + omega sh, r = s - omega t, ||r||^2 and the next rho = rhat . r  (early: y += alpha ph, the residual is s)
+__global__ void __launch_bounds__(kBlock) k_cs_update(int N, CsVecs V, double *scal, int *words, double *part)
+{
+    __shared__ double s_w[kBlock / 64];
+    if (cs_word(words, W_DONE)) return;
+    const int early = cs_word(words, W_EARLY);
+    const double al = scal[S_ALPHA], om = scal[S_OMEGA];
+    const int i0 = blockIdx.x * kCsVecTile + threadIdx.x;
+    double mine[2] = {0.0, 0.0}, tot[2];
+#pragma unroll
+    for (int k = 0; k < kCsVecTile / kBlock; ++k) {
+        const int i = i0 + k * kBlock;
+        if (i >= N) continue;
+        if (early) {
+            V.y[i] = V.y[i] + al * V.ph[i];
+        } else {
+            V.y[i] = (V.y[i] + al * V.ph[i]) + om * V.sh[i];
+            const double r = V.s[i] - om * V.t[i];
+            V.r[i] = r;
+            mine[0] += r * r;
+            mine[1] += V.rhat[i] * r;
+        }
+    }
+    if (cs_finish<2>(mine, part, words, tot, s_w) && threadIdx.x == 0) {
+        int done = 0;
+        if (early) {
+            scal[S_RNORM2] = scal[S_SNORM2];
+            done = 1;
+        } else {
+            scal[S_RNORM2] = tot[0];
+            if (tot[0] <= scal[S_TOL2]) done = 1;
+            else {
+                scal[S_RHO_OLD] = scal[S_RHO];
+                scal[S_RHO] = tot[1];
+                if (cs_bad_pivot(tot[1])) { atomicOr(words + W_FLAGS, 2); done = 1; }
+            }
+        }
+        words[W_ITERS] = words[W_ITERS] + 1;
+        if (done) __hip_atomic_store(words + W_DONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+// the end: bit 0 when the iterations ran out; y, or NaN after a failure unless the caller keeps the last iterate
+__global__ void __launch_bounds__(kBlock) k_cs_final(int N, const double *__restrict__ yacc, real_t *__restrict__ y, int *words, int keep)
+{
+    const int flags = (cs_word(words, W_FLAGS) & 2) | (cs_word(words, W_DONE) ? 0 : 1);
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i == 0) words[W_FINAL] = flags;
+    if (i >= N) return;
+    y[i] = (real_t)((flags && !keep) ? __longlong_as_double(0x7FF8000000000000ll) : yacc[i]);
+}
+
+}  // namespace fdjac
+
+struct fd_csc_solver {
+    fd_ctx *ctx = nullptr;
+    int64_t N = 0, nnz = 0;
+    int nlong = 0, reach = 0, window = 1, batch = fdjac::kCsBatchDefault;
+    int *d_colptr = nullptr, *d_rowval = nullptr, *d_row_ptr = nullptr, *d_row_col = nullptr, *d_row_slot = nullptr, *d_order = nullptr,
+        *d_long = nullptr, *d_diag = nullptr;
+    double *d_vec = nullptr;           // ten vectors of N doubles
+    double *d_part = nullptr;          // the tiles' sums: 2 x ceil(N / 256)
+    double *d_scal = nullptr;
+    int *d_words = nullptr;
+    fdjac::CsRecord *h_rec = nullptr;  // pinned: one record per batch in flight (two)
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    double rtol = 1e-10;
+    int max_iterations = 500, keep = 0;
+    bool solved = false;
+};
+
+using namespace fdjac;
+
+static void csc_solver_free(fd_csc_solver *s)
+{
+    void *ptrs[] = {s->d_colptr, s->d_rowval, s->d_row_ptr, s->d_row_col, s->d_row_slot, s->d_order, s->d_long, s->d_diag,
+                    s->d_vec, s->d_part, s->d_scal, s->d_words};
+    for (void *p : ptrs) if (p) (void)hipFree(p);
+    if (s->h_rec) (void)hipHostFree(s->h_rec);
+    for (hipEvent_t e : s->ev) if (e) (void)hipEventDestroy(e);
+    delete s;
+}
+
+static CsPat csc_pat(const fd_csc_solver *s)
+{
+    CsPat P;
+    P.N = (int)s->N; P.nnz = (int)s->nnz; P.nlong = s->nlong; P.reach = s->reach; P.window = s->window;
+    P.colptr = s->d_colptr; P.rowval = s->d_rowval; P.row_ptr = s->d_row_ptr; P.row_col = s->d_row_col; P.row_slot = s->d_row_slot;
+    P.order = s->d_order; P.long_rows = s->d_long; P.diag = s->d_diag;
+    return P;
+}
+static size_t csc_win_bytes(const fd_csc_solver *s, size_t elem)
+{
+    if (!s->window) return 0;
+    return (size_t)(kBlock + 2 * s->reach) * elem;
+}
+static unsigned csc_grid(int64_t n, int per) { const int64_t g = (n + per - 1) / per; return (unsigned)(g < 1 ? 1 : (g > 65536 ? 65536 : g)); }
+
+static int csc_exscan(hipStream_t st, const int *in, int64_t n, int *out, int *bsum)
+{
+    const int64_t nb = (n + kCsScanTile - 1) / kCsScanTile;
+    hipLaunchKernelGGL(k_cs_scan_sums, dim3((unsigned)nb), dim3(kBlock), 0, st, in, n, bsum);
+    hipLaunchKernelGGL(k_cs_scan_top, dim3(1), dim3(kBlock), 0, st, bsum, nb);
+    hipLaunchKernelGGL(k_cs_scan_apply, dim3((unsigned)nb), dim3(kBlock), 0, st, in, n, (const int *)bsum, nb, out);
+    FD_HIP_CHECK(hipGetLastError());
+    return FD_OK;
+}
+
+int fd_csc_solver_create(fd_ctx *ctx, int64_t N, const void *colptr, const void *rowval, int idx_bytes, int idx_base, int idx_kind,
+                         fd_csc_solver **out)
+{
+    FD_REQUIRE(out != nullptr, FD_ERR_ARG, "NULL argument");
+    *out = nullptr;
+    if (!ctx) {      // (no context can exist without a device: say which of the two is the matter)
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { (void)hipGetLastError(); FD_REQUIRE(false, FD_ERR_NODEVICE, "no HIP device"); }
+        FD_REQUIRE(false, FD_ERR_ARG, "ctx is NULL");
+    }
+    FD_REQUIRE(colptr != nullptr, FD_ERR_ARG, "colptr is NULL");
+    FD_REQUIRE(N >= 1 && N < ((int64_t)1 << 31) - 4096, FD_ERR_ARG, "N = %lld", (long long)N);
+    FD_REQUIRE(idx_bytes == 4 || idx_bytes == 8, FD_ERR_ARG, "idx_bytes = %d (4 or 8)", idx_bytes);
+    FD_REQUIRE(idx_base == 0 || idx_base == 1, FD_ERR_ARG, "idx_base = %d (0 or 1)", idx_base);
+    FD_REQUIRE(idx_kind == FD_HOST || idx_kind == FD_DEVICE, FD_ERR_ARG, "idx_kind = %d", idx_kind);
+    FD_HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    // nnz from the two ends of colptr
+    int64_t ends[2] = {0, 0};
+    for (int k = 0; k < 2; ++k) {
+        const char *src = (const char *)colptr + (size_t)(k ? N : 0) * idx_bytes;
+        int64_t v64 = 0; int32_t v32 = 0;
+        void *dst = idx_bytes == 8 ? (void *)&v64 : (void *)&v32;
+        if (idx_kind == FD_DEVICE) { FD_HIP_CHECK(hipStreamSynchronize(st)); FD_HIP_CHECK(hipMemcpy(dst, src, idx_bytes, hipMemcpyDeviceToHost)); }
+        else std::memcpy(dst, src, idx_bytes);
+        ends[k] = idx_bytes == 8 ? v64 : (int64_t)v32;
+    }
+    const int64_t nnz = ends[1] - ends[0];
+    FD_REQUIRE(ends[0] == idx_base, FD_ERR_SHAPE, "colptr[first] = %lld, expected the index base %d", (long long)ends[0], idx_base);
+    FD_REQUIRE(nnz >= 0 && nnz < ((int64_t)1 << 31) - 4096, FD_ERR_SHAPE, "colptr[last] - colptr[first] = %lld entries (0 <= nnz < 2^31)", (long long)nnz);
+    FD_REQUIRE(nnz == 0 || rowval != nullptr, FD_ERR_ARG, "rowval is NULL");
+
+    fd_csc_solver *s = new (std::nothrow) fd_csc_solver();
+    FD_REQUIRE(s != nullptr, FD_ERR_NOMEM, "out of host memory");
+    s->ctx = ctx; s->N = N; s->nnz = nnz;
+    if (const char *v = test_switch("FDJAC_CSC_WINDOW")) s->window = atoi(v) != 0;
+    if (const char *v = test_switch("FDJAC_CSC_BATCH")) { const int b = atoi(v); if (b >= 1 && b <= 64) s->batch = b; }
+    const int64_t npad = (N + kBlock - 1) / kBlock * kBlock, nz1 = nnz > 0 ? nnz : 1;
+    const int64_t nscan = (N + kCsScanTile - 1) / kCsScanTile + 2;
+    const int64_t npart = 2 * ((N + kBlock - 1) / kBlock);
+    void *raw_cp = nullptr, *raw_rv = nullptr;
+    int *ecol = nullptr, *rcnt = nullptr, *bsum = nullptr, *tmp = nullptr, *misc = nullptr;
+    int rc = FD_OK;
+    unsigned err = 0;
+    int host_misc[4] = {0, 0, 0, 0};      // err, reach, nlong, long cursor
+    auto fail = [&](int code) {
+        void *t[] = {raw_cp, raw_rv, ecol, rcnt, bsum, tmp, misc};
+        (void)hipStreamSynchronize(st);
+        for (void *p : t) if (p) (void)hipFree(p);
+        if (code != FD_OK) csc_solver_free(s);
+        return code;
+    };
+#define CS_TRY(expr)                                                                                              \
+    do {                                                                                                          \
+        hipError_t _e = (expr);                                                                                   \
+        if (_e != hipSuccess) {                                                                                   \
+            set_error("csc solver: %s failed: %s", #expr, hipGetErrorString(_e));                                 \
+            return fail(_e == hipErrorOutOfMemory ? FD_ERR_NOMEM : FD_ERR_HIP);                                   \
+        }                                                                                                         \
+    } while (0)
+    CS_TRY(hipMalloc((void **)&s->d_colptr, sizeof(int) * (size_t)(N + 1)));
+    CS_TRY(hipMalloc((void **)&s->d_rowval, sizeof(int) * (size_t)nz1));
+    CS_TRY(hipMalloc((void **)&s->d_row_ptr, sizeof(int) * (size_t)(N + 1)));
+    CS_TRY(hipMalloc((void **)&s->d_row_col, sizeof(int) * (size_t)nz1));
+    CS_TRY(hipMalloc((void **)&s->d_row_slot, sizeof(int) * (size_t)nz1));
+    CS_TRY(hipMalloc((void **)&s->d_order, sizeof(int) * (size_t)npad));
+    CS_TRY(hipMalloc((void **)&s->d_diag, sizeof(int) * (size_t)N));
+    CS_TRY(hipMalloc((void **)&ecol, sizeof(int) * (size_t)nz1));
+    CS_TRY(hipMalloc((void **)&rcnt, sizeof(int) * (size_t)N));
+    CS_TRY(hipMalloc((void **)&bsum, sizeof(int) * (size_t)nscan));
+    CS_TRY(hipMalloc((void **)&misc, sizeof(int) * 4));
+    const void *cp = colptr, *rv = rowval;
+    if (idx_kind == FD_HOST) {
+        CS_TRY(hipMalloc(&raw_cp, (size_t)idx_bytes * (size_t)(N + 1)));
+        CS_TRY(hipMemcpyAsync(raw_cp, colptr, (size_t)idx_bytes * (size_t)(N + 1), hipMemcpyHostToDevice, st));
+        cp = raw_cp;
+        if (nnz > 0) {
+            CS_TRY(hipMalloc(&raw_rv, (size_t)idx_bytes * (size_t)nnz));
+            CS_TRY(hipMemcpyAsync(raw_rv, rowval, (size_t)idx_bytes * (size_t)nnz, hipMemcpyHostToDevice, st));
+            rv = raw_rv;
+        }
+    }
+    CS_TRY(hipMemsetAsync(misc, 0, sizeof(int) * 4, st));
+    CS_TRY(hipMemsetAsync(rcnt, 0, sizeof(int) * (size_t)N, st));
+    CS_TRY(hipMemsetAsync(s->d_diag, 0xFF, sizeof(int) * (size_t)N, st));
+    hipLaunchKernelGGL(k_cs_colptr, dim3(csc_grid(N + 1, kBlock)), dim3(kBlock), 0, st, cp, idx_bytes, idx_base, N, nnz, s->d_colptr, (unsigned *)misc);
+    CS_TRY(hipGetLastError());
+    CS_TRY(hipMemcpyAsync(host_misc, misc, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
+    CS_TRY(hipStreamSynchronize(st));
+    err = (unsigned)host_misc[0];
+    if (err & CS_BAD_COLPTR) { set_error("csc solver: colptr is not a monotone sequence from the index base to nnz + base"); return fail(FD_ERR_SHAPE); }
+    if (nnz > 0) {
+        hipLaunchKernelGGL(k_cs_entries, dim3(csc_grid(nnz, kBlock)), dim3(kBlock), 0, st, rv, idx_bytes, idx_base, (const int *)s->d_colptr, N, nnz,
+                           s->d_rowval, ecol, rcnt, s->d_diag, misc + 1, (unsigned *)misc);
+        CS_TRY(hipGetLastError());
+    }
+    CS_TRY(hipMemcpyAsync(host_misc, misc, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
+    CS_TRY(hipStreamSynchronize(st));
+    err = (unsigned)host_misc[0];
+    if (err & CS_BAD_ROW) { set_error("csc solver: rowval holds a row outside the %lld x %lld matrix", (long long)N, (long long)N); return fail(FD_ERR_SHAPE); }
+    if (err & CS_BAD_ORDER) { set_error("csc solver: the rows of a column are not strictly ascending"); return fail(FD_ERR_SHAPE); }
+    s->reach = host_misc[1];
+    // the LDS window of v only when the measured reach allows it: every column a tile's rows can name then lies inside the window;
+    // a wider pattern would stage 2 * kCsWinHalo elements per tile to serve the near-diagonal gathers alone
+    if (s->reach > kCsWinHalo) s->window = 0;
+    rc = csc_exscan(st, rcnt, N, s->d_row_ptr, bsum);
+    if (rc != FD_OK) return fail(rc);
+    CS_TRY(hipMemsetAsync(rcnt, 0, sizeof(int) * (size_t)N, st));
+    if (nnz > 0) {
+        hipLaunchKernelGGL(k_cs_fill, dim3(csc_grid(nnz, kBlock)), dim3(kBlock), 0, st, (const int *)s->d_rowval, nnz, (const int *)s->d_row_ptr, rcnt, s->d_row_slot);
+        CS_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_cs_sort_short, dim3((unsigned)((N + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, (const int *)s->d_row_ptr, N, s->d_row_slot,
+                       (const int *)ecol, s->d_row_col, misc + 2);
+    hipLaunchKernelGGL(k_cs_order, dim3((unsigned)((N + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, (const int *)s->d_row_ptr, N, s->d_order);
+    CS_TRY(hipGetLastError());
+    CS_TRY(hipMemcpyAsync(host_misc, misc, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
+    CS_TRY(hipStreamSynchronize(st));
+    s->nlong = host_misc[2];
+    if (s->nlong > 0) {
+        CS_TRY(hipMalloc((void **)&s->d_long, sizeof(int) * (size_t)s->nlong));
+        CS_TRY(hipMalloc((void **)&tmp, sizeof(int) * (size_t)nz1));
+        hipLaunchKernelGGL(k_cs_list_long, dim3((unsigned)((N + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, (const int *)s->d_row_ptr, N, s->d_long, misc + 3);
+        hipLaunchKernelGGL(k_cs_sort_long, dim3((unsigned)s->nlong), dim3(kBlock), 0, st, (const int *)s->d_row_ptr, (const int *)s->d_long, s->d_row_slot, tmp,
+                           (const int *)ecol, s->d_row_col);
+        CS_TRY(hipGetLastError());
+    }
+    CS_TRY(hipMalloc((void **)&s->d_vec, sizeof(double) * 10 * (size_t)N));
+    CS_TRY(hipMalloc((void **)&s->d_part, sizeof(double) * (size_t)npart));
+    CS_TRY(hipMalloc((void **)&s->d_scal, sizeof(double) * S_NSCAL));
+    CS_TRY(hipMalloc((void **)&s->d_words, sizeof(int) * W_NWORDS));
+    CS_TRY(hipHostMalloc((void **)&s->h_rec, sizeof(CsRecord) * 2, hipHostMallocDefault));
+    CS_TRY(hipEventCreateWithFlags(&s->ev[0], hipEventDisableTiming));
+    CS_TRY(hipEventCreateWithFlags(&s->ev[1], hipEventDisableTiming));
+    CS_TRY(hipMemsetAsync(s->d_scal, 0, sizeof(double) * S_NSCAL, st));
+    CS_TRY(hipMemsetAsync(s->d_words, 0, sizeof(int) * W_NWORDS, st));
+    CS_TRY(hipStreamSynchronize(st));
+#undef CS_TRY
+    (void)fail(FD_OK);
+    *out = s;
+    return FD_OK;
+}
+
+int fd_csc_solver_destroy(fd_csc_solver *s)
+{
+    if (!s) return FD_OK;
+    (void)hipSetDevice(s->ctx->device);
+    (void)hipStreamSynchronize(s->ctx->stream);
+    csc_solver_free(s);
+    return FD_OK;
+}
+
+int fd_csc_solver_set_options(fd_csc_solver *s, double rtol, int max_iterations)
+{
+    FD_REQUIRE(s != nullptr, FD_ERR_ARG, "solver is NULL");
+    FD_REQUIRE(rtol >= 0.0 && rtol < 1.0, FD_ERR_ARG, "rtol = %g (0 <= rtol < 1)", rtol);
+    FD_REQUIRE(max_iterations >= 1, FD_ERR_ARG, "max_iterations = %d", max_iterations);
+    s->rtol = rtol; s->max_iterations = max_iterations;
+    return FD_OK;
+}
+
+int fd_csc_solver_set_policy(fd_csc_solver *s, int keep_unconverged)
+{
+    FD_REQUIRE(s != nullptr, FD_ERR_ARG, "solver is NULL");
+    s->keep = keep_unconverged ? 1 : 0;
+    return FD_OK;
+}
+
+// the solver's lists, for the tests and for callers that want the pattern by rows: device pointers that live as long as the solver
+int fd_csc_solver_row_lists(fd_csc_solver *s, const void **row_ptr, const void **row_col, const void **row_slot, const void **diag_slot,
+                            int64_t *nnz_out, int64_t *long_rows_out)
+{
+    FD_REQUIRE(s != nullptr, FD_ERR_ARG, "solver is NULL");
+    if (row_ptr) *row_ptr = s->d_row_ptr;
+    if (row_col) *row_col = s->d_row_col;
+    if (row_slot) *row_slot = s->d_row_slot;
+    if (diag_slot) *diag_slot = s->d_diag;
+    if (nnz_out) *nnz_out = s->nnz;
+    if (long_rows_out) *long_rows_out = s->nlong;
+    return FD_OK;
+}
+
+template <typename TV, int MODE>
+static void csc_product(fd_csc_solver *s, double alpha, double beta, const real_t *nz, const TV *v, TV *y, const double *c, bool guarded)
+{
+    hipStream_t st = s->ctx->stream;
+    const CsPat P = csc_pat(s);
+    const int ntile = (int)((s->N + kBlock - 1) / kBlock);
+    if (s->nlong > 0)
+        hipLaunchKernelGGL((k_cs_long<TV>), dim3((unsigned)s->nlong), dim3(kBlock), 0, st, P, alpha, beta, nz, v, y, guarded ? (const int *)s->d_words : (const int *)nullptr);
+    hipLaunchKernelGGL((k_cs_rows<TV, MODE>), dim3(MODE == 0 ? fd_xcd_grid(ntile) : (unsigned)ntile), dim3(kBlock), csc_win_bytes(s, sizeof(TV)), st, P, alpha, beta,
+                       nz, v, y, c, s->d_scal, s->d_words, s->d_part);
+}
+
+int fd_csc_matvec_async(fd_csc_solver *s, double alpha, double beta, const void *nzval, const void *v, void *y, int transpose)
+{
+    FD_REQUIRE(s && v && y && (nzval || s->nnz == 0), FD_ERR_ARG, "NULL argument");
+    FD_REQUIRE(v != y, FD_ERR_ARG, "y must not be v");
+    FD_HIP_CHECK(hipSetDevice(s->ctx->device));
+    if (transpose) {
+        const int nb = (int)((s->N + kBlock - 1) / kBlock);
+        hipLaunchKernelGGL(k_cs_cols, dim3(fd_xcd_grid(nb)), dim3(kBlock), 0, s->ctx->stream, csc_pat(s), alpha, beta, (const real_t *)nzval, (const real_t *)v, (real_t *)y);
+    } else {
+        csc_product<real_t, 0>(s, alpha, beta, (const real_t *)nzval, (const real_t *)v, (real_t *)y, nullptr, false);
+    }
+    FD_HIP_CHECK(hipGetLastError());
+    return FD_OK;
+}
+
+int fd_csc_solve_async(fd_csc_solver *s, double alpha, double beta, const void *nzval, const void *b, void *y)
+{
+    FD_REQUIRE(s && b && y && (nzval || s->nnz == 0), FD_ERR_ARG, "NULL argument");
+    FD_HIP_CHECK(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    const int N = (int)s->N;
+    const real_t *nz = (const real_t *)nzval;
+    CsVecs V;
+    double **vp[] = {&V.r, &V.rhat, &V.p, &V.v, &V.s, &V.t, &V.ph, &V.sh, &V.y, &V.d};
+    for (int k = 0; k < 10; ++k) *vp[k] = s->d_vec + (size_t)k * (size_t)N;
+    const CsPat P = csc_pat(s);
+    const unsigned gv = (unsigned)((N + kCsVecTile - 1) / kCsVecTile);
+    FD_HIP_CHECK(hipMemsetAsync(s->d_words, 0, sizeof(int) * W_NWORDS, st));
+    hipLaunchKernelGGL(k_cs_init, dim3(gv), dim3(kBlock), 0, st, P, V, alpha, beta, nz, (const real_t *)b, s->rtol, s->d_scal, s->d_words, s->d_part);
+    // the iterations, in batches; the record of batch k is read while batch k + 1 is already enqueued (its kernels leave at once
+    // when the solve is done), so the device never waits for the host
+    int enq = 0, nb = 0;
+    bool stop = false;
+    while (!stop) {
+        const int todo = s->max_iterations - enq < s->batch ? s->max_iterations - enq : s->batch;
+        for (int it = 0; it < todo; ++it) {
+            hipLaunchKernelGGL(k_cs_p, dim3(gv), dim3(kBlock), 0, st, N, V, (const double *)s->d_scal, (const int *)s->d_words);
+            csc_product<double, 1>(s, alpha, beta, nz, V.ph, V.v, V.rhat, true);
+            hipLaunchKernelGGL(k_cs_s, dim3(gv), dim3(kBlock), 0, st, N, V, s->d_scal, s->d_words, s->d_part);
+            csc_product<double, 2>(s, alpha, beta, nz, V.sh, V.t, V.s, true);
+            hipLaunchKernelGGL(k_cs_update, dim3(gv), dim3(kBlock), 0, st, N, V, s->d_scal, s->d_words, s->d_part);
+        }
+        enq += todo;
+        FD_HIP_CHECK(hipGetLastError());
+        FD_HIP_CHECK(hipMemcpyAsync(&s->h_rec[nb & 1], s->d_words, sizeof(CsRecord), hipMemcpyDeviceToHost, st));
+        FD_HIP_CHECK(hipEventRecord(s->ev[nb & 1], st));
+        if (nb >= 1) {
+            FD_HIP_CHECK(hipEventSynchronize(s->ev[(nb - 1) & 1]));
+            stop = s->h_rec[(nb - 1) & 1].done != 0;
+        }
+        ++nb;
+        if (enq >= s->max_iterations) stop = true;
+    }
+    hipLaunchKernelGGL(k_cs_final, dim3((unsigned)((N + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, N, (const double *)V.y, (real_t *)y, s->d_words, s->keep);
+    FD_HIP_CHECK(hipGetLastError());
+    s->solved = true;
+    return FD_OK;
+}
+
+int fd_csc_solver_status(fd_csc_solver *s, int *flags_out, int64_t *iterations_out, double *resid_out, double *bnorm_out)
+{
+    FD_REQUIRE(s != nullptr, FD_ERR_ARG, "solver is NULL");
+    FD_HIP_CHECK(hipSetDevice(s->ctx->device));
+    FD_HIP_CHECK(hipStreamSynchronize(s->ctx->stream));
+    int w[W_NWORDS];
+    double sc[S_NSCAL];
+    FD_HIP_CHECK(hipMemcpy(w, s->d_words, sizeof w, hipMemcpyDeviceToHost));
+    FD_HIP_CHECK(hipMemcpy(sc, s->d_scal, sizeof sc, hipMemcpyDeviceToHost));
+    if (flags_out) *flags_out = s->solved ? w[W_FINAL] : 0;
+    if (iterations_out) *iterations_out = w[W_ITERS];
+    if (resid_out) *resid_out = std::sqrt(sc[S_RNORM2]);
+    if (bnorm_out) *bnorm_out = std::sqrt(sc[S_BNORM2]);
+    return FD_OK;
+}

@@ -10,3 +10,4 @@
 #include "fdjac_solve.hip"
 #include "fdjac_bandsolve.hip"
 #include "fdjac_blocksolve.hip"
+#include "fdjac_cscsolve.hip"

@@ -695,6 +695,40 @@ int fd_banded_solver_set_policy(fd_banded_solver *solver, int trust_non_dominant
 int fd_banded_solver_status(fd_banded_solver *solver, int *flags_out);
 int fd_banded_solve_async(fd_banded_solver *solver, double alpha, double beta, const void *J, const void *b, void *y);
 
+/* ---- the SPARSE consumer: (alpha*I + beta*J) v, its transpose, and (alpha*I + beta*J) y = b for a square J in SparseMatrixCSC storage --
+ * The pattern is that of a fd_plan_create_csc / fd_plan_create_csc_device plan that holds every column: colptr (N + 1) and rowval (nnz),
+ * Int32 or Int64 (idx_bytes 4 / 8), base 0 or 1, on the host or on the device (idx_kind FD_HOST / FD_DEVICE: a device pattern is
+ * converted on the device).  N >= 1, nnz < 2^31, rows strictly ascending within a column: the pattern is validated on the device and a
+ * bad one is FD_ERR_SHAPE with a message.  nzval, v, b and y are DEVICE arrays of the library's element type; all arithmetic is Float64.
+ * The solver depends on no fd_plan and keeps its own lists (the pattern by rows, sorted by column; the diagonal's slots).
+ *   fd_csc_matvec_async   y = (alpha*I + beta*J) v (transpose = 0, row-wise, no atomics) or its transpose (column-wise on the CSC arrays
+ *                         as they are); y must not be v.  The summation orders are defined: the same bits every call.
+ *   fd_csc_solve_async    Jacobi-preconditioned BiCGStab (right-preconditioned, M = diag(alpha + beta*J_ii), y0 = 0, shadow residual b)
+ *                         until ||r||_2 <= rtol * ||b||_2 (fd_csc_solver_set_options: rtol, default 1e-10; max_iterations, default 500).
+ *                         Every scalar stays on the device; the iterations are enqueued in batches and the call waits only for one
+ *                         16-byte record per batch, one batch behind the device.  b = 0: y = 0, no iteration.  y may be b.
+ *   fd_csc_solver_status  synchronises; flags bit 0: not converged within max_iterations; bit 1: breakdown (rho, rhat.v, t.t or a Jacobi
+ *                         diagonal zero or not finite); the iterations of the last solve, its last recurrence residual norm and ||b||_2.
+ *                         After either failure y is NaN, unless fd_csc_solver_set_policy(solver, 1): then y is the last iterate and the
+ *                         bits are raised all the same.  A matrix that is not diagonally dominant is NOT refused.
+ *   fd_csc_solver_row_lists  DIAGNOSTIC ONLY (what the tests compare with a host counting sort): device pointers, owned by the solver, to its
+ *                         Int32 0-based lists row_ptr (N + 1), row_col and row_slot (nnz; the entry's index in nzval) in ascending column
+ *                         order per row, diag_slot (N; -1: not stored), the number of entries and of rows longer than 32 entries.  Any
+ *                         out pointer may be NULL.  The layout is the solver's own and may change with it: do not build on it.
+ * Everything is enqueued on the context's stream; fd_csc_solver_create and fd_csc_solver_status synchronise it.  Without a device
+ * fd_csc_solver_create is FD_ERR_NODEVICE. */
+typedef struct fd_csc_solver fd_csc_solver;
+int fd_csc_solver_create(fd_ctx *ctx, int64_t N, const void *colptr, const void *rowval, int idx_bytes, int idx_base, int idx_kind,
+                         fd_csc_solver **out);
+int fd_csc_solver_destroy(fd_csc_solver *solver);
+int fd_csc_matvec_async(fd_csc_solver *solver, double alpha, double beta, const void *nzval, const void *v, void *y, int transpose);
+int fd_csc_solver_set_options(fd_csc_solver *solver, double rtol, int max_iterations);
+int fd_csc_solver_set_policy(fd_csc_solver *solver, int keep_unconverged);
+int fd_csc_solve_async(fd_csc_solver *solver, double alpha, double beta, const void *nzval, const void *b, void *y);
+int fd_csc_solver_status(fd_csc_solver *solver, int *flags_out, int64_t *iterations_out, double *resid_out, double *bnorm_out);
+int fd_csc_solver_row_lists(fd_csc_solver *solver, const void **row_ptr, const void **row_col, const void **row_slot, const void **diag_slot,
+                            int64_t *nnz_out, int64_t *long_rows_out);
+
 /* ---- the consumer for block-banded Jacobians: (alpha*I + beta*J) y = b for a BLOCK-TRIDIAGONAL J (round 6) ---------------------------
  * J = nblk x nblk dense blocks of block_size x block_size (<= 32), block bandwidths (1, 1), in BlockBandedMatrix data as a
  * fd_plan_create_blockbanded plan of uniform block sizes fills it (block column J's in-band blocks stacked into one column-major
@@ -896,6 +930,17 @@ int fd32_banded_solver_destroy(fd32_banded_solver *solver);
 int fd32_banded_solver_set_policy(fd32_banded_solver *solver, int trust_non_dominant);
 int fd32_banded_solver_status(fd32_banded_solver *solver, int *flags_out);
 int fd32_banded_solve_async(fd32_banded_solver *solver, double alpha, double beta, const void *J, const void *b, void *y);
+typedef struct fd32_csc_solver fd32_csc_solver;
+int fd32_csc_solver_create(fd_ctx *ctx, int64_t N, const void *colptr, const void *rowval, int idx_bytes, int idx_base, int idx_kind,
+                         fd32_csc_solver **out);
+int fd32_csc_solver_destroy(fd32_csc_solver *solver);
+int fd32_csc_matvec_async(fd32_csc_solver *solver, double alpha, double beta, const void *nzval, const void *v, void *y, int transpose);
+int fd32_csc_solver_set_options(fd32_csc_solver *solver, double rtol, int max_iterations);
+int fd32_csc_solver_set_policy(fd32_csc_solver *solver, int keep_unconverged);
+int fd32_csc_solve_async(fd32_csc_solver *solver, double alpha, double beta, const void *nzval, const void *b, void *y);
+int fd32_csc_solver_status(fd32_csc_solver *solver, int *flags_out, int64_t *iterations_out, double *resid_out, double *bnorm_out);
+int fd32_csc_solver_row_lists(fd32_csc_solver *solver, const void **row_ptr, const void **row_col, const void **row_slot, const void **diag_slot,
+                            int64_t *nnz_out, int64_t *long_rows_out);
 typedef struct fd32_tridiag_solver fd32_tridiag_solver;
 int fd32_tridiag_solver_create(fd_ctx *ctx, int64_t N, int64_t row_begin, int64_t row_end, int layout,
                                fd32_tridiag_solver **out);

@@ -587,7 +587,8 @@ class BandedSolver:
 class CscSolver:
     """fd_csc_solver: the sparse consumer.  For a square J in ``SparseMatrixCSC`` storage -- the nzval a CSC plan has just written, left
     on the device -- ``matvec`` enqueues y = (alpha*I + beta*J) v (or its transpose) and ``solve`` enqueues y = (alpha*I + beta*J)^-1 b by
-    Jacobi-preconditioned BiCGStab whose scalars never leave the device.  ``pattern`` is a ``SparseMatrixCSC`` / ``DevicePatternCSC`` or
+    BiCGStab whose scalars never leave the device, preconditioned by the diagonal or (``set_preconditioner``) by the inverses of the
+    diagonal blocks.  ``pattern`` is a ``SparseMatrixCSC`` / ``DevicePatternCSC`` or
     ``(colptr, rowval, N)`` with numpy arrays or CUDA tensors of int32 / int64 (``idx_base``-based).  A solve that does not converge
     within ``max_iterations`` (``status()`` flags bit 0) or breaks down (bit 1) fills y with NaN unless ``set_policy(True)``."""
 
@@ -650,6 +651,26 @@ class CscSolver:
         f, it, r, bn = C.c_int(), C.c_int64(), C.c_double(), C.c_double()
         _l.check(self.Lt.fd_csc_solver_status(self.handle, C.byref(f), C.byref(it), C.byref(r), C.byref(bn)))
         return {"flags": f.value, "iterations": it.value, "resid": r.value, "bnorm": bn.value}
+
+    def set_preconditioner(self, kind="jacobi", block_size=None):
+        """``"jacobi"`` (the default: the diagonal) or ``"block_jacobi"`` with ``block_size`` in 2..32: the inverses of the diagonal blocks
+        alpha*I + beta*J[k*bs:(k+1)*bs, k*bs:(k+1)*bs], gathered and inverted by every solve (fd_csc_solver_set_preconditioner)."""
+        kinds = {"jacobi": 0, "block_jacobi": 1}
+        if kind not in kinds:
+            raise ValueError("kind must be 'jacobi' or 'block_jacobi'")
+        if kind == "block_jacobi" and block_size is None:
+            raise ValueError("block_jacobi needs a block_size (2..32)")
+        _l.check(self.Lt.fd_csc_solver_set_preconditioner(self.handle, kinds[kind], int(block_size or 0)))
+
+    def block_inverses(self):
+        """Synchronises.  The inverses of the last block-Jacobi solve as a float64 CUDA tensor (a copy) of shape (block_size, N): element
+        [c, i] is Minv[i - b0, c] of the block that starts at b0 = (i // block_size) * block_size."""
+        import torch
+        p, nb, bs = C.c_void_p(), C.c_int64(), C.c_int()
+        _l.check(self.Lt.fd_csc_solver_block_inverses(self.handle, C.byref(p), C.byref(nb), C.byref(bs)))
+        self.ctx.synchronize()
+        view = _DevView(p.value, bs.value * self.N, False)
+        return torch.as_tensor(view, device="cuda:%d" % self.ctx.device).clone().reshape(bs.value, self.N)
 
     def row_lists(self):
         """The solver's lists as int32 CUDA tensors (copies): row_ptr, row_col, row_slot, diag_slot; and the number of long rows."""

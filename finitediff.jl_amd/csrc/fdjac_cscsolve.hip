@@ -16,6 +16,20 @@
 // (product kernels: element t), block_sum() per tile, and the LAST-ARRIVING workgroup (an integer ticket) adds the tiles' sums: thread t
 // adds sums t, t + 256, ... in order, then block_sum().  No floating-point atomics; every order is a function of N alone.  All
 // arithmetic is Float64 for either element type, and nothing is contracted into an FMA.
+//
+// BLOCK JACOBI (fd_csc_solver_set_preconditioner, kind 1).  M = diag(B_k), B_k = alpha I + beta J[rows of k, columns of k] over the
+// uniform ranges [k bs, min((k + 1) bs, N)), bs in 2..32, applied on the right where p / d and s / d stand.  Once per solve
+// k_cs_binv gathers every B_k from colptr / rowval / nzval into LDS beside an identity and inverts it by Gauss-Jordan with partial
+// pivoting (one wavefront per block, lane l = column l of [B | I]).  Step j = 0 .. n - 1 of a block of n rows:
+//   pivot row  best = j; for i = j + 1 .. n - 1: if |a_ij| > |a_best,j| then best = i   (strictly greater: the lowest row wins a tie;
+//              a NaN never replaces and a NaN a_jj is never replaced);  piv = a_best,j; zero or not finite: breakdown (flag bit 1, done);
+//   swap rows j and best;  every row i != j: f_i = a_ij / piv, a_il = a_il - f_i * a_jl (one multiply, one subtraction);  then row j:
+//   a_jl = a_jl / piv.  (Two rows that are equal bit for bit therefore leave an exact zero row, and a zero pivot, behind.)
+// Minv is kept as bs planes of N doubles: plane c holds column c of every block's inverse at its global row (a short last block
+// leaves zeros in the planes it does not have).  k_cs_bapply: out_i = sum_c plane_c[i] * x[first row of i's block + c], c ascending
+// from +0.0, one multiply and one add per term; the block's x values go through LDS.  The vector kernels then skip the division
+// (their PC = 1 instances), so an iteration is 7 launches (+ 2 with long rows) instead of 5; kind 0 runs the PC = 0 instances, which
+// are the code of before.  tests/csc_block_model.py restates all of it.
 #include "fdjac_internal.h"
 #include "fdjac_device.h"
 #include <cmath>
@@ -28,6 +42,8 @@ constexpr int kCsLong = 32;            // rows of more entries than this are sum
 constexpr int kCsVecTile = 1024;       // elements per workgroup of the vector kernels
 constexpr int kCsWinHalo = 1920;       // the LDS window of v (the tile's 256 rows + the reach on either side) is used up to this reach
 constexpr int kCsBatchDefault = 8;     // iterations enqueued per record read back
+constexpr int kCsBsMax = 32;           // the largest block of the block-Jacobi preconditioner
+constexpr int kCsBinvWaves = 2;        // blocks (one wavefront each) per workgroup of k_cs_binv: 2 x (32 x 65 + 32) doubles = 33 KiB at bs = 32
 enum { CS_BAD_COLPTR = 1, CS_BAD_ROW = 2, CS_BAD_ORDER = 4 };
 // scalars of a solve, in device memory: doubles ...
 enum { S_RHO = 0, S_RHO_OLD, S_ALPHA, S_OMEGA, S_BNORM2, S_TOL2, S_RNORM2, S_SNORM2, S_NSCAL };
@@ -367,7 +383,8 @@ __global__ void __launch_bounds__(kBlock) k_cs_cols(CsPat P, double alpha, doubl
 // ---- BiCGStab ------------------------------------------------------------------------------------------------------------------------
 struct CsVecs { double *r, *rhat, *p, *v, *s, *t, *ph, *sh, *y, *d; };
 
-// the start: d = alpha + beta J_ii, r = rhat = b, p = v = y = 0, rho = ||b||^2
+// the start: d = alpha + beta J_ii, r = rhat = b, p = v = y = 0, rho = ||b||^2  (PC = 1, block Jacobi: no d; k_cs_binv follows)
+template <int PC>
 __global__ void __launch_bounds__(kBlock) k_cs_init(CsPat P, CsVecs V, double alpha, double beta, const real_t *__restrict__ nz,
                                                     const real_t *__restrict__ b, double rtol, double *scal, int *words, double *part)
 {
@@ -378,10 +395,14 @@ __global__ void __launch_bounds__(kBlock) k_cs_init(CsPat P, CsVecs V, double al
     for (int k = 0; k < kCsVecTile / kBlock; ++k) {
         const int i = i0 + k * kBlock;
         if (i >= P.N) continue;
-        const int q = P.diag[i];
-        const double d = q >= 0 ? alpha + beta * (double)nz[q] : alpha, bi = (double)b[i];
-        bad = bad || cs_bad_pivot(d);
-        V.d[i] = d; V.r[i] = bi; V.rhat[i] = bi; V.p[i] = 0.0; V.v[i] = 0.0; V.y[i] = 0.0;
+        const double bi = (double)b[i];
+        if (PC == 0) {
+            const int q = P.diag[i];
+            const double d = q >= 0 ? alpha + beta * (double)nz[q] : alpha;
+            bad = bad || cs_bad_pivot(d);
+            V.d[i] = d;
+        }
+        V.r[i] = bi; V.rhat[i] = bi; V.p[i] = 0.0; V.v[i] = 0.0; V.y[i] = 0.0;
         mine[0] += bi * bi;
     }
     if (bad) atomicOr(words + W_FLAGS, 2);
@@ -396,7 +417,8 @@ __global__ void __launch_bounds__(kBlock) k_cs_init(CsPat P, CsVecs V, double al
         if (done) __hip_atomic_store(words + W_DONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
-// p = r + beta (p - omega v), ph = p / d
+// p = r + beta (p - omega v), ph = p / d  (PC = 1: ph is k_cs_bapply's)
+template <int PC>
 __global__ void __launch_bounds__(kBlock) k_cs_p(int N, CsVecs V, const double *scal, const int *words)
 {
     if (cs_word(words, W_DONE)) return;
@@ -408,10 +430,11 @@ __global__ void __launch_bounds__(kBlock) k_cs_p(int N, CsVecs V, const double *
         if (i >= N) continue;
         const double p = V.r[i] + bk * (V.p[i] - om * V.v[i]);
         V.p[i] = p;
-        V.ph[i] = p / V.d[i];
+        if (PC == 0) V.ph[i] = p / V.d[i];
     }
 }
-// s = r - alpha v, sh = s / d, ||s||^2; ||s||^2 <= tol^2 ends the iteration early (W_EARLY)
+// s = r - alpha v, sh = s / d, ||s||^2; ||s||^2 <= tol^2 ends the iteration early (W_EARLY)  (PC = 1: sh is k_cs_bapply's)
+template <int PC>
 __global__ void __launch_bounds__(kBlock) k_cs_s(int N, CsVecs V, double *scal, int *words, double *part)
 {
     __shared__ double s_w[kBlock / 64];
@@ -425,7 +448,7 @@ __global__ void __launch_bounds__(kBlock) k_cs_s(int N, CsVecs V, double *scal, 
         if (i >= N) continue;
         const double s = V.r[i] - al * V.v[i];
         V.s[i] = s;
-        V.sh[i] = s / V.d[i];
+        if (PC == 0) V.sh[i] = s / V.d[i];
         mine[0] += s * s;
     }
     if (cs_finish<1>(mine, part, words, tot, s_w) && threadIdx.x == 0) {
@@ -474,6 +497,95 @@ __global__ void __launch_bounds__(kBlock) k_cs_update(int N, CsVecs V, double *s
         if (done) __hip_atomic_store(words + W_DONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
+// ---- block Jacobi ----------------------------------------------------------------------------------------------------------------------
+// gather and invert: wavefront w of the workgroup takes block blockIdx.x * kCsBinvWaves + w; its tile is bs rows of [B | I] with a row
+// stride of 2 bs + 1 doubles (odd: a column read does not stay in one bank); lane l < bs owns column l of B, lane bs + c column c of
+// the companion; lane i < n also forms row i's factor f_i of every step.  A lane writes only its own column and column j is dead from
+// step j on (it is neither swapped nor updated: nothing reads it again), so a step needs two barriers: behind the factors and behind the
+// update.  Every loop runs to bs and every barrier is met by all threads whatever the block's length n (0: a wavefront without a block).
+__global__ void __launch_bounds__(kCsBinvWaves * 64) k_cs_binv(CsPat P, int bs, double alpha, double beta, const real_t *__restrict__ nz,
+                                                                double *__restrict__ minv, int *words)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
+    const int ld = 2 * bs + 1, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    double *a = (double *)s_raw + (size_t)w * (bs * ld + bs), *f = a + bs * ld;
+    const int nblk = (P.N + bs - 1) / bs, blk = blockIdx.x * kCsBinvWaves + w;
+    const int b0 = blk < nblk ? blk * bs : 0;
+    const int n = blk < nblk ? (P.N - b0 < bs ? P.N - b0 : bs) : 0;
+    const bool col_b = lane < n, col_i = lane >= bs && lane - bs < n;       // this lane's column exists
+    if (lane < 2 * bs)
+        for (int i = 0; i < bs; ++i) a[i * ld + lane] = lane == bs + i ? 1.0 : 0.0;
+    if (col_b) {
+        const int col = b0 + lane;
+        a[lane * ld + lane] = alpha;                                        // a diagonal that is not stored
+        for (int q = P.colptr[col]; q < P.colptr[col + 1]; ++q) {
+            const int r = P.rowval[q];
+            if (r >= b0 + n) break;                                         // (rows ascend within a column)
+            if (r >= b0) a[(r - b0) * ld + lane] = r == col ? alpha + beta * (double)nz[q] : beta * (double)nz[q];
+        }
+    }
+    __syncthreads();
+    bool bad = false;
+    for (int j = 0; j < bs; ++j) {
+        const bool step = j < n;
+        int best = j;
+        double piv = 1.0;
+        if (step) {
+            double mag = fabs(a[j * ld + j]);
+            for (int i = j + 1; i < n; ++i) {
+                const double m = fabs(a[i * ld + j]);
+                if (m > mag) { mag = m; best = i; }
+            }
+            piv = a[best * ld + j];
+            bad = bad || cs_bad_pivot(piv);
+            if (lane < n) f[lane] = a[(lane == j ? best : (lane == best ? j : lane)) * ld + j] / piv;      // row `lane` after the swap
+        }
+        __syncthreads();
+        if (step && ((col_b && lane > j) || col_i)) {
+            const double t = a[best * ld + lane];
+            a[best * ld + lane] = a[j * ld + lane];
+            for (int i = 0; i < n; ++i)
+                if (i != j) a[i * ld + lane] = a[i * ld + lane] - f[i] * t;
+            a[j * ld + lane] = t / piv;
+        }
+        __syncthreads();
+    }
+    if (bad && lane == 0) {      // (every lane of the wavefront has seen the same pivots)
+        atomicOr(words + W_FLAGS, 2);
+        __hip_atomic_store(words + W_DONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (col_b)      // lane i writes row i of the inverse, plane by plane: n consecutive doubles per plane
+        for (int c = 0; c < bs; ++c) minv[(size_t)c * P.N + b0 + lane] = c < n ? a[lane * ld + bs + c] : 0.0;
+}
+// out = Minv x on a tile of kCsVecTile elements; the blocks that reach into the tile are staged whole in LDS
+template <int WHICH>      // 0: ph from p; 1: sh from s (not needed once the half step has converged)
+__global__ void __launch_bounds__(kBlock) k_cs_bapply(int N, int bs, const double *__restrict__ minv, const double *__restrict__ x,
+                                                      double *__restrict__ out, const int *words)
+{
+    __shared__ double s_x[kCsVecTile + 2 * (kCsBsMax - 1)];
+    if (cs_word(words, W_DONE) || (WHICH == 1 && cs_word(words, W_EARLY))) return;
+    const int t0 = blockIdx.x * kCsVecTile, t1 = t0 + kCsVecTile < N ? t0 + kCsVecTile : N;
+    const int w0 = t0 / bs * bs;
+    int w1 = (t1 + bs - 1) / bs * bs;
+    if (w1 > N) w1 = N;
+    for (int i = w0 + threadIdx.x; i < w1; i += kBlock) s_x[i - w0] = x[i];
+    __syncthreads();
+    // the offset of element i in its block: ONE division per lane (of a number below kBlock + bs); the next element of the lane is
+    // kBlock further on, so its offset follows from kBlock % bs (the same for every lane) by an addition and a compare
+    const int step = kBlock % bs;
+    int off = (t0 - w0 + (int)threadIdx.x) % bs;
+#pragma unroll
+    for (int k = 0; k < kCsVecTile / kBlock; ++k, off = off + step >= bs ? off + step - bs : off + step) {
+        const int i = t0 + threadIdx.x + k * kBlock;
+        if (i >= N) continue;
+        const int b0 = i - off, n = N - b0 < bs ? N - b0 : bs;
+        const double *m = minv + i, *xb = s_x + (b0 - w0);
+        double acc = 0.0;
+#pragma unroll 8
+        for (int c = 0; c < n; ++c) acc += m[(size_t)c * N] * xb[c];
+        out[i] = acc;
+    }
+}
 // the end: bit 0 when the iterations ran out; y, or NaN after a failure unless the caller keeps the last iterate
 __global__ void __launch_bounds__(kBlock) k_cs_final(int N, const double *__restrict__ yacc, real_t *__restrict__ y, int *words, int keep)
 {
@@ -501,6 +613,10 @@ struct fd_csc_solver {
     double rtol = 1e-10;
     int max_iterations = 500, keep = 0;
     bool solved = false;
+    int pc_kind = FD_CSC_PRECOND_JACOBI, pc_bs = 0;      // what the next solve uses
+    double *d_minv = nullptr;          // block Jacobi: minv_bs planes of N doubles (allocated by the first solve that needs them)
+    size_t minv_cap = 0;               // doubles allocated
+    int minv_bs = 0;                   // the block size of the last block-Jacobi solve, 0: none yet
 };
 
 using namespace fdjac;
@@ -508,7 +624,7 @@ using namespace fdjac;
 static void csc_solver_free(fd_csc_solver *s)
 {
     void *ptrs[] = {s->d_colptr, s->d_rowval, s->d_row_ptr, s->d_row_col, s->d_row_slot, s->d_order, s->d_long, s->d_diag,
-                    s->d_vec, s->d_part, s->d_scal, s->d_words};
+                    s->d_vec, s->d_part, s->d_scal, s->d_words, s->d_minv};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (s->h_rec) (void)hipHostFree(s->h_rec);
     for (hipEvent_t e : s->ev) if (e) (void)hipEventDestroy(e);
@@ -708,6 +824,28 @@ int fd_csc_solver_set_policy(fd_csc_solver *s, int keep_unconverged)
     return FD_OK;
 }
 
+int fd_csc_solver_set_preconditioner(fd_csc_solver *s, int kind, int block_size)
+{
+    FD_REQUIRE(s != nullptr, FD_ERR_ARG, "solver is NULL");
+    FD_REQUIRE(kind == FD_CSC_PRECOND_JACOBI || kind == FD_CSC_PRECOND_BLOCK_JACOBI, FD_ERR_ARG, "kind = %d (0: Jacobi, 1: block Jacobi)", kind);
+    if (kind == FD_CSC_PRECOND_BLOCK_JACOBI)
+        FD_REQUIRE(block_size >= 2 && block_size <= kCsBsMax, FD_ERR_ARG, "block_size = %d (2 .. %d)", block_size, kCsBsMax);
+    s->pc_kind = kind;
+    s->pc_bs = kind == FD_CSC_PRECOND_BLOCK_JACOBI ? block_size : 0;
+    return FD_OK;
+}
+
+// the inverses of the last block-Jacobi solve, for the tests: block_size planes of N doubles, owned by the solver
+int fd_csc_solver_block_inverses(fd_csc_solver *s, const void **inv_dev, int64_t *nblocks, int *block_size)
+{
+    FD_REQUIRE(s != nullptr, FD_ERR_ARG, "solver is NULL");
+    FD_REQUIRE(s->minv_bs > 0, FD_ERR_UNSUPPORTED, "no block-Jacobi solve has run on this solver");
+    if (inv_dev) *inv_dev = s->d_minv;
+    if (nblocks) *nblocks = (s->N + s->minv_bs - 1) / s->minv_bs;
+    if (block_size) *block_size = s->minv_bs;
+    return FD_OK;
+}
+
 // the solver's lists, for the tests and for callers that want the pattern by rows: device pointers that live as long as the solver
 int fd_csc_solver_row_lists(fd_csc_solver *s, const void **row_ptr, const void **row_col, const void **row_slot, const void **diag_slot,
                             int64_t *nnz_out, int64_t *long_rows_out)
@@ -761,8 +899,25 @@ int fd_csc_solve_async(fd_csc_solver *s, double alpha, double beta, const void *
     for (int k = 0; k < 10; ++k) *vp[k] = s->d_vec + (size_t)k * (size_t)N;
     const CsPat P = csc_pat(s);
     const unsigned gv = (unsigned)((N + kCsVecTile - 1) / kCsVecTile);
+    const int bs = s->pc_kind == FD_CSC_PRECOND_BLOCK_JACOBI ? s->pc_bs : 0;
+    if (bs > 0 && s->minv_cap < (size_t)bs * (size_t)N) {
+        FD_HIP_CHECK(hipStreamSynchronize(st));
+        if (s->d_minv) (void)hipFree(s->d_minv);
+        s->d_minv = nullptr; s->minv_cap = 0; s->minv_bs = 0;
+        const hipError_t e = hipMalloc((void **)&s->d_minv, sizeof(double) * (size_t)bs * (size_t)N);
+        if (e != hipSuccess) { (void)hipGetLastError(); FD_REQUIRE(false, FD_ERR_NOMEM, "block Jacobi: %d planes of %d doubles: %s", bs, N, hipGetErrorString(e)); }
+        s->minv_cap = (size_t)bs * (size_t)N;
+    }
     FD_HIP_CHECK(hipMemsetAsync(s->d_words, 0, sizeof(int) * W_NWORDS, st));
-    hipLaunchKernelGGL(k_cs_init, dim3(gv), dim3(kBlock), 0, st, P, V, alpha, beta, nz, (const real_t *)b, s->rtol, s->d_scal, s->d_words, s->d_part);
+    if (bs > 0) {
+        const int nblk = (N + bs - 1) / bs;
+        hipLaunchKernelGGL(k_cs_init<1>, dim3(gv), dim3(kBlock), 0, st, P, V, alpha, beta, nz, (const real_t *)b, s->rtol, s->d_scal, s->d_words, s->d_part);
+        hipLaunchKernelGGL(k_cs_binv, dim3((unsigned)((nblk + kCsBinvWaves - 1) / kCsBinvWaves)), dim3(kCsBinvWaves * 64),
+                           sizeof(double) * (size_t)kCsBinvWaves * (size_t)(bs * (2 * bs + 1) + bs), st, P, bs, alpha, beta, nz, s->d_minv, s->d_words);
+        s->minv_bs = bs;
+    } else {
+        hipLaunchKernelGGL(k_cs_init<0>, dim3(gv), dim3(kBlock), 0, st, P, V, alpha, beta, nz, (const real_t *)b, s->rtol, s->d_scal, s->d_words, s->d_part);
+    }
     // the iterations, in batches; the record of batch k is read while batch k + 1 is already enqueued (its kernels leave at once
     // when the solve is done), so the device never waits for the host
     int enq = 0, nb = 0;
@@ -770,9 +925,19 @@ int fd_csc_solve_async(fd_csc_solver *s, double alpha, double beta, const void *
     while (!stop) {
         const int todo = s->max_iterations - enq < s->batch ? s->max_iterations - enq : s->batch;
         for (int it = 0; it < todo; ++it) {
-            hipLaunchKernelGGL(k_cs_p, dim3(gv), dim3(kBlock), 0, st, N, V, (const double *)s->d_scal, (const int *)s->d_words);
+            if (bs > 0) {
+                hipLaunchKernelGGL(k_cs_p<1>, dim3(gv), dim3(kBlock), 0, st, N, V, (const double *)s->d_scal, (const int *)s->d_words);
+                hipLaunchKernelGGL(k_cs_bapply<0>, dim3(gv), dim3(kBlock), 0, st, N, bs, (const double *)s->d_minv, (const double *)V.p, V.ph, (const int *)s->d_words);
+            } else {
+                hipLaunchKernelGGL(k_cs_p<0>, dim3(gv), dim3(kBlock), 0, st, N, V, (const double *)s->d_scal, (const int *)s->d_words);
+            }
             csc_product<double, 1>(s, alpha, beta, nz, V.ph, V.v, V.rhat, true);
-            hipLaunchKernelGGL(k_cs_s, dim3(gv), dim3(kBlock), 0, st, N, V, s->d_scal, s->d_words, s->d_part);
+            if (bs > 0) {
+                hipLaunchKernelGGL(k_cs_s<1>, dim3(gv), dim3(kBlock), 0, st, N, V, s->d_scal, s->d_words, s->d_part);
+                hipLaunchKernelGGL(k_cs_bapply<1>, dim3(gv), dim3(kBlock), 0, st, N, bs, (const double *)s->d_minv, (const double *)V.s, V.sh, (const int *)s->d_words);
+            } else {
+                hipLaunchKernelGGL(k_cs_s<0>, dim3(gv), dim3(kBlock), 0, st, N, V, s->d_scal, s->d_words, s->d_part);
+            }
             csc_product<double, 2>(s, alpha, beta, nz, V.sh, V.t, V.s, true);
             hipLaunchKernelGGL(k_cs_update, dim3(gv), dim3(kBlock), 0, st, N, V, s->d_scal, s->d_words, s->d_part);
         }

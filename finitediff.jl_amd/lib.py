@@ -83,6 +83,7 @@ EXPORTS = (
     "fd_blocktridiag_solver_create", "fd_blocktridiag_solver_destroy", "fd_blocktridiag_solver_set_policy", "fd_blocktridiag_solver_status",
     "fd_blocktridiag_solve_async",
     "fd_csc_solver_create", "fd_csc_solver_destroy", "fd_csc_matvec_async", "fd_csc_solver_set_options", "fd_csc_solver_set_policy", "fd_csc_solve_async", "fd_csc_solver_status", "fd_csc_solver_row_lists",
+    "fd_csc_solver_set_preconditioner", "fd_csc_solver_block_inverses",
     "fd_objective_compile", "fd_objective_destroy", "fd_objective_counts", "fd_hess_plan_create", "fd_hess_plan_destroy",
     "fd_hess_plan_info", "fd_hess_plan_pattern", "fd_hessian_async", "fd_hessian", "fd_gradient_async", "fd_gradient",
 )
@@ -105,6 +106,7 @@ TYPED = (
     "fd_blocktridiag_solver_create", "fd_blocktridiag_solver_destroy", "fd_blocktridiag_solver_set_policy", "fd_blocktridiag_solver_status",
     "fd_blocktridiag_solve_async",
     "fd_csc_solver_create", "fd_csc_solver_destroy", "fd_csc_matvec_async", "fd_csc_solver_set_options", "fd_csc_solver_set_policy", "fd_csc_solve_async", "fd_csc_solver_status", "fd_csc_solver_row_lists",
+    "fd_csc_solver_set_preconditioner", "fd_csc_solver_block_inverses",
 )
 EXPORTS = EXPORTS + tuple("fd32_" + n[3:] for n in TYPED)
 
@@ -285,6 +287,8 @@ def load():
     L.fd_csc_solve_async.argtypes = [vp, dbl, dbl, vp, vp, vp]
     L.fd_csc_solver_status.argtypes = [vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(dbl), C.POINTER(dbl)]
     L.fd_csc_solver_row_lists.argtypes = [vp, pp, pp, pp, pp, C.POINTER(i64), C.POINTER(i64)]
+    L.fd_csc_solver_set_preconditioner.argtypes = [vp, i32, i32]
+    L.fd_csc_solver_block_inverses.argtypes = [vp, pp, C.POINTER(i64), C.POINTER(i32)]
     L.fd_tridiag_solver_create.argtypes = [vp, i64, i64, i64, i32, pp]
     L.fd_tridiag_solver_destroy.argtypes = [vp]
     L.fd_tridiag_solver_status.argtypes = [vp, C.POINTER(i32)]

@@ -715,8 +715,24 @@ int fd_banded_solve_async(fd_banded_solver *solver, double alpha, double beta, c
  *                         Int32 0-based lists row_ptr (N + 1), row_col and row_slot (nnz; the entry's index in nzval) in ascending column
  *                         order per row, diag_slot (N; -1: not stored), the number of entries and of rows longer than 32 entries.  Any
  *                         out pointer may be NULL.  The layout is the solver's own and may change with it: do not build on it.
+ *   fd_csc_solver_set_preconditioner  kind FD_CSC_PRECOND_JACOBI (the default: the solver described above, block_size ignored) or
+ *                         FD_CSC_PRECOND_BLOCK_JACOBI with block_size in 2..32: M = diag(B_k) over the uniform contiguous ranges
+ *                         [k*bs, min((k + 1)*bs, N)) (the last block may be shorter), B_k = alpha*I + beta*J[rows of k, columns of k] from
+ *                         the stored entries (an entry that is not stored is 0, a diagonal that is not stored contributes alpha).
+ *                         Every solve gathers the blocks and inverts them in ONE launch (Gauss-Jordan, partial pivoting: the largest
+ *                         magnitude, the lowest row on ties); a pivot that is zero or not finite is a breakdown (bit 1, no iteration).
+ *                         Each iteration then takes 7 launches instead of 5 (two of them apply the inverses: ph = Minv p, sh = Minv s;
+ *                         + 2 with rows longer than 32 entries).  May be called between solves; the buffers (block_size * N doubles) are
+ *                         allocated by the first solve that needs them and freed with the solver.  Anything else is FD_ERR_ARG.
+ *   fd_csc_solver_block_inverses  DIAGNOSTIC ONLY: a device pointer, owned by the solver, to the inverses of the last block-Jacobi solve
+ *                         (valid once that solve has run; FD_ERR_UNSUPPORTED before the first), the number of blocks and the block size.
+ *                         Layout: block_size PLANES of N doubles; plane c, element i holds Minv[i - b0, c] of the block that starts at
+ *                         b0 = (i / bs)*bs, i.e. column c of every block's inverse at its global row; a shorter last block leaves 0 in
+ *                         the planes c >= its length.  Any out pointer may be NULL.  The layout may change with the solver.
  * Everything is enqueued on the context's stream; fd_csc_solver_create and fd_csc_solver_status synchronise it.  Without a device
  * fd_csc_solver_create is FD_ERR_NODEVICE. */
+#define FD_CSC_PRECOND_JACOBI        0   /* the default */
+#define FD_CSC_PRECOND_BLOCK_JACOBI  1
 typedef struct fd_csc_solver fd_csc_solver;
 int fd_csc_solver_create(fd_ctx *ctx, int64_t N, const void *colptr, const void *rowval, int idx_bytes, int idx_base, int idx_kind,
                          fd_csc_solver **out);
@@ -728,6 +744,8 @@ int fd_csc_solve_async(fd_csc_solver *solver, double alpha, double beta, const v
 int fd_csc_solver_status(fd_csc_solver *solver, int *flags_out, int64_t *iterations_out, double *resid_out, double *bnorm_out);
 int fd_csc_solver_row_lists(fd_csc_solver *solver, const void **row_ptr, const void **row_col, const void **row_slot, const void **diag_slot,
                             int64_t *nnz_out, int64_t *long_rows_out);
+int fd_csc_solver_set_preconditioner(fd_csc_solver *solver, int kind, int block_size);
+int fd_csc_solver_block_inverses(fd_csc_solver *solver, const void **inv_dev, int64_t *nblocks, int *block_size);
 
 /* ---- the consumer for block-banded Jacobians: (alpha*I + beta*J) y = b for a BLOCK-TRIDIAGONAL J (round 6) ---------------------------
  * J = nblk x nblk dense blocks of block_size x block_size (<= 32), block bandwidths (1, 1), in BlockBandedMatrix data as a
@@ -941,6 +959,8 @@ int fd32_csc_solve_async(fd32_csc_solver *solver, double alpha, double beta, con
 int fd32_csc_solver_status(fd32_csc_solver *solver, int *flags_out, int64_t *iterations_out, double *resid_out, double *bnorm_out);
 int fd32_csc_solver_row_lists(fd32_csc_solver *solver, const void **row_ptr, const void **row_col, const void **row_slot, const void **diag_slot,
                             int64_t *nnz_out, int64_t *long_rows_out);
+int fd32_csc_solver_set_preconditioner(fd32_csc_solver *solver, int kind, int block_size);
+int fd32_csc_solver_block_inverses(fd32_csc_solver *solver, const void **inv_dev, int64_t *nblocks, int *block_size);
 typedef struct fd32_tridiag_solver fd32_tridiag_solver;
 int fd32_tridiag_solver_create(fd_ctx *ctx, int64_t N, int64_t row_begin, int64_t row_end, int layout,
                                fd32_tridiag_solver **out);

@@ -12,7 +12,14 @@ infrastructure only.
                the IEEE quotient by eps_c (central: by 2 eps_c)
   layout       CSC nzval, BandedMatrix data, Tridiagonal dl / d / du; uncoloured columns hold 0
 
-The reference's in-place un-perturbation (x1 - eps mask after every colour) is NOT modelled: every colour starts from x."""
+The reference's in-place un-perturbation (x1 - eps mask after every colour) is NOT modelled: every colour starts from x.
+
+The general-pattern anchor.  The hand-over path on ANY CSC pattern (k_perturb -> plain f! -> k_decompress_list / _sorted / _window /
+_window2d) is what every "same bits" comparison of the store routes and of the decompression kernels ends in.  sparse_f restates the
+one residual the library ships for any pattern (FD_F_SPARSE, SparseF::row in csrc/fdjac_functor_f.hip: f_r = sum over the pattern's
+entries (r, j) of row r, ascending j, of w(r, j) phi(x_j), one IEEE operation at a time in a fixed order), so the model covers random
+and rectangular patterns, empty rows and columns, greedy / invalid colourings and columns without a colour
+(tests/exact_general.py holds the cases, tests/test_gpu_exact_general.py runs them); to_dense is the dense-J destination."""
 import numpy as np
 
 import eps_order
@@ -93,8 +100,56 @@ def stencil5_f(x, nx, ny, nl):
     return v.reshape(-1)
 
 
+def sparse_f(M, N, colptr, rowval, dtype=F64):
+    """FD_F_SPARSE (SparseF::row) in the element type: f_r = sum over the entries (r, j) of row r, ascending j, left to right, of
+    w * (v + (q * v) * v) with v = x_j, w = 1 + ((r + 3 j) & 7) / 8 and q = 1 / 4 in the element type (both exact); the first term is
+    ASSIGNED (not added to a zero), a row without entries is +0.  Rows of up to 32 entries are summed term by term across all rows at
+    once, longer ones by np.cumsum -- a strictly sequential accumulation that starts from the first term itself."""
+    T = np.dtype(dtype).type
+    colptr = np.asarray(colptr, np.int64) - 1
+    rows = np.asarray(rowval, np.int64) - 1
+    cols = np.repeat(np.arange(N, dtype=np.int64), np.diff(colptr))
+    order = np.lexsort((cols, rows))                     # by row, then by column
+    rs, cs = rows[order], cols[order]
+    cnt = np.bincount(rs, minlength=M)
+    start = np.concatenate([[0], np.cumsum(cnt)])[:-1]
+    w = (T(1) + T(0.125) * ((rs + 3 * cs) & 7).astype(dtype)).astype(dtype)
+    q = T(0.25)
+    short = np.nonzero(cnt <= 32)[0]
+    long_rows = np.nonzero(cnt > 32)[0]
+    depth = int(cnt[short].max()) if short.size else 0
+    level = []                                           # level[k]: (the short rows with more than k entries, their k-th term's position)
+    for k in range(depth):
+        sel = short[cnt[short] > k]
+        level.append((sel, start[sel] + k))
+
+    def f(x):
+        x = np.asarray(x)
+        assert x.dtype == np.dtype(dtype) and x.size == N, (x.dtype, x.size)
+        with np.errstate(all="ignore"):
+            v = x[cs]
+            t = w * (v + (q * v) * v)
+            out = np.zeros(M, dtype=dtype)
+            for k, (sel, at) in enumerate(level):
+                out[sel] = t[at] if k == 0 else out[sel] + t[at]
+            for r in long_rows:
+                out[r] = np.cumsum(t[start[r]:start[r] + cnt[r]])[-1]
+        return out
+    return f
+
+
 def fixture(family, *prm):
-    """f(x) -> f(x) in x's dtype, for the rational built-in families."""
+    """f(x) -> f(x) in x's dtype, for the rational built-in families ("sparse", M, N, colptr, rowval: the residual of any pattern)."""
+    if family == "sparse":
+        M, N, colptr, rowval = prm
+        fs = {}
+
+        def f(x):
+            x = np.asarray(x)
+            if x.dtype not in fs:
+                fs[x.dtype] = sparse_f(M, N, colptr, rowval, x.dtype)
+            return fs[x.dtype](x)
+        return f
     if family in ("tridiag", "tridiag_nl"):
         return lambda x: tridiag_f(x, family == "tridiag_nl")
     if family in ("lap5", "lap5_nl"):
@@ -103,24 +158,30 @@ def fixture(family, *prm):
     raise ValueError(family)
 
 
-def colour_values(f, x, colors0, C, eps, fdtype):
-    """D[c][r]: the value the plain evaluation stores for row r in a column of colour c."""
+def colour_values(f, x, colors0, C, eps, fdtype, f_in=None):
+    """D[c][r]: the value the plain evaluation stores for row r in a column of colour c; (C, M) for a residual of M rows.  f_in: the
+    caller's f(x) of a forward difference -- subtracted as it is given."""
     x = np.asarray(x)
     T = x.dtype.type
-    D = np.empty((C, x.size), dtype=x.dtype)
     with np.errstate(all="ignore"):
-        base = f(x) if fdtype == "forward" else None
+        base = None
+        if fdtype == "forward":
+            base = f(x) if f_in is None else np.asarray(f_in, dtype=x.dtype)
+        D = None
         for c in range(C):
             e = T(eps[c])
             z = np.copysign(T(0), e)
             m = colors0 == c
             xp = np.where(m, x + e, x + z)
             if fdtype == "forward":
-                D[c] = (f(xp) - base) / e
+                row = (f(xp) - base) / e
             else:
                 xm = np.where(m, x - e, x - z)
-                D[c] = (f(xp) - f(xm)) / (T(2) * e)
-    return D
+                row = (f(xp) - f(xm)) / (T(2) * e)
+            if D is None:
+                D = np.empty((C, row.size), dtype=x.dtype)
+            D[c] = row
+    return D if D is not None else np.empty((0, x.size), dtype=x.dtype)
 
 
 def to_csc(D, colors0, colptr, rowval):
@@ -132,6 +193,18 @@ def to_csc(D, colors0, colptr, rowval):
     out = np.zeros(rows.size, D.dtype)
     ok = c >= 0
     out[ok] = D[c[ok], rows[ok]]
+    return out
+
+
+def to_dense(D, colors0, colptr, rowval, M, N):
+    """The dense-J destination with a 1-based CSC sparsity pattern, column-major as an (M, N) array: entry (r, j) of the pattern holds
+    D[colour of j][r]; everything else -- entries outside the pattern, the pattern's entries of a column without a colour -- holds 0
+    (the reference zero-fills J before its colour loop, and so does tests/test_gpu_parity.py::test_dense_J_sparse_pattern's J)."""
+    colptr = np.asarray(colptr) - 1
+    rows = np.asarray(rowval) - 1
+    cols = np.repeat(np.arange(N), np.diff(colptr))
+    out = np.zeros((M, N), D.dtype, order="F")
+    out[rows, cols] = to_csc(D, colors0, colptr + 1, rowval)
     return out
 
 

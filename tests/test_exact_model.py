@@ -1,10 +1,14 @@
 """The exact host model (tests/exact_model.py) tied to the reference: it agrees with the C and numpy oracles on ordinary inputs at the
 oracles' tolerance, its step sizes are within 4 ulps of an mpmath evaluation of max(relstep * sqrt(||x_c||_2), absstep) * dir at the
 edges of the range (overflowing / underflowing sums of squares, subnormals, NaN / Inf coordinates), and the oracles take the same
-edge semantics (NaN propagates through the step rule, the scaled norm where the plain sum leaves the range).  CPU only."""
+edge semantics (NaN propagates through the step rule, the scaled norm where the plain sum leaves the range).  The general-pattern
+pieces (sparse_f, rectangular colour_values, to_dense) against independent restatements, and the inputs of every case of
+tests/test_gpu_exact_general.py evaluated with the model alone.  CPU only."""
 import numpy as np
 import pytest
 
+import color_model
+import exact_general as G
 import exact_model as X
 from finitediff_jl_amd import patterns as P
 from oracle import np_oracle
@@ -234,3 +238,148 @@ def test_oracles_nan_coordinate_poisons_only_its_colour(oracle):
             other = ~last & ~(rows_nan[rowval - 1] & (fdtype == "forward"))
             other &= ~rows_nan[rowval - 1]
             assert np.isfinite(out[other]).all()
+
+
+# ---- the general-pattern anchor: sparse_f, rectangular residuals, the dense-J destination, the cases of test_gpu_exact_general.py ----
+@pytest.mark.parametrize("pname", ["random_band600", "tall", "wide", "ragged"])
+def test_sparse_f_equals_the_float64_restatement_bit_for_bit(pname):
+    # tests/test_gpu_storetable.py::sparse_np_factory is the Float64 restatement the oracle comparisons use: a random band, M > N,
+    # M < N (rows of up to 61 entries), and the ragged pattern (empty rows and columns, one row of 3000 entries: the cumsum branch)
+    from test_gpu_storetable import sparse_np_factory
+    M, N, colptr, rowval = G.pattern(pname)
+    cnt = np.bincount(rowval - 1, minlength=M)
+    if pname == "ragged":
+        assert (cnt == 0).any() and (np.diff(colptr) == 0).any() and cnt.max() == 3000
+    if pname == "wide":
+        assert cnt.max() > 32
+    rng = np.random.default_rng(M + N)
+    x = rng.random(N) - 0.25
+    x[rng.random(N) < 0.05] = -0.0
+    want = np.full(M, np.nan)
+    sparse_np_factory(M, N, colptr, rowval)(want, x)
+    got = X.fixture("sparse", M, N, colptr, rowval)(x)
+    assert got.dtype == np.float64 and X.same_bits(got, want).all()
+    assert not np.signbit(got[cnt == 0]).any()                   # an empty row is +0
+    # the element type is the argument's: Float32 in, Float32 arithmetic (the Float64 sum of the same terms differs)
+    g32 = X.fixture("sparse", M, N, colptr, rowval)(x.astype(np.float32))
+    assert g32.dtype == np.float32 and np.allclose(g32, want, rtol=1e-4 * max(1, cnt.max()) ** 0.5, atol=1e-5)
+
+
+@pytest.mark.parametrize("pname", ["random_band600", "tall", "wide"])
+def test_model_forward_jacobian_against_the_analytic_one(pname):
+    """f_r = sum_j w(r, j) phi(x_j), phi(v) = v + v^2 / 4: dJ[r, j] = w (1 + x_j / 2).  With a VALID colouring exactly one term of row r
+    moves, t(v) = w (v + v^2 / 4), and in exact arithmetic (t(v + e) - t(v)) / e = w (1 + v / 2) + w e / 4: the truncation term of this
+    quadratic is exactly w eps_c / 4.
+
+    ASSERTED: |error| <= w eps_c / 4 + 4 len_r u max|term| / eps_c with u = 2^-52 and max|term| the largest term of row r -- the bound
+    the general-pattern anchor is specified with.  Its rounding part counts, per evaluation, the moved term's 3 roundings ((q v) v,
+    v + ., w .; q v is exact) and the row's len_r - 1 additions at (u / 2) of ONE term's size each, plus the point's own rounding
+    (fl(v + e) differs from v + e by at most (u / 2) (v + e), which moves the numerator by t'(v) (u / 2) (v + e) <= 1.2 (u / 2) t):
+    (2 len_r + 5.2) (u / 2) max|term| <= 4 len_r u max|term| for every len_r >= 1.  An addition's error scales with its partial sum, not
+    with one term, so for a long row this count is a first-order one (errors of independent sign; on these patterns the worst ratio
+    is 0.49 / 0.76 / 0.19 of the bound), not a worst case.
+
+    ALSO ASSERTED, weaker: the same expression with S_r, the row's value, in place of max|term|.  With x > 0 all terms are positive, S_r
+    bounds every partial sum and every term, and the count above is then a rigorous worst case."""
+    M, N, colptr, rowval = G.pattern(pname)
+    colors = G.colouring(pname, "greedy")
+    assert color_model.valid(M, colptr, rowval, colors)
+    c0, C = colors - 1, int(colors.max())
+    x = np.random.default_rng(N).random(N) + 0.1
+    f = X.fixture("sparse", M, N, colptr, rowval)
+    u = 2.0 ** -52
+    cols, rows = P.csc_cols(colptr) - 1, rowval - 1
+    w = 1.0 + 0.125 * ((rows + 3 * cols) & 7)
+    n = np.bincount(rows, minlength=M)[rows]
+    for dir in (1.0, -1.0):
+        eps, scaled = X.epsilons(x, c0, C, "forward", dir=dir)
+        assert not scaled.any()
+        got = X.to_csc(X.colour_values(f, x, c0, C, eps, "forward"), c0, colptr, rowval)
+        e = np.abs(eps[c0[cols]])
+        xs = x + np.abs(eps).max()                                # (every coordinate at its largest: terms grow with v > 0)
+        term = w * (xs[cols] + (0.25 * xs[cols]) * xs[cols])
+        tmax = np.zeros(M)
+        np.maximum.at(tmax, rows, term)
+        err = np.abs(got - w * (1.0 + 0.5 * x[cols]))
+        bound = w * e / 4 + 4 * n * u * tmax[rows] / e
+        assert (err <= bound).all(), (pname, float(np.max(err / bound)))
+        assert (err > 0.1 * bound).any()                          # (the bound is of the error's own size, not a blanket)
+        assert (err <= w * e / 4 + 4 * n * u * f(xs)[rows] / e).all()
+
+
+def test_model_layouts_against_an_entry_by_entry_assembly():
+    # 7 x 5, one column without a colour, one empty column, one empty row: to_csc and to_dense against a plain Python loop
+    M, N = 7, 5
+    A = np.zeros((M, N), bool)
+    for r, j in [(0, 0), (2, 0), (6, 0), (1, 1), (2, 1), (3, 2), (6, 2), (0, 4), (4, 4), (6, 4)]:      # (column 3 and row 5 are empty)
+        A[r, j] = True
+    colptr, rowval = P.csc_from_dense(A)
+    colors = np.array([1, 2, 0, 3, 2])                            # column 2 has no colour
+    c0, C = colors - 1, 3
+    D = np.random.default_rng(0).random((C, M)) + 1.0
+    csc = X.to_csc(D, c0, colptr, rowval)
+    dense = X.to_dense(D, c0, colptr, rowval, M, N)
+    want_dense = np.zeros((M, N))
+    want_csc = []
+    for j in range(N):
+        for r in range(M):
+            if A[r, j]:
+                v = D[colors[j] - 1, r] if colors[j] > 0 else 0.0
+                want_dense[r, j] = v
+                want_csc.append(v)
+    assert dense.shape == (M, N) and dense.flags.f_contiguous
+    assert np.array_equal(csc, np.array(want_csc)) and np.array_equal(dense, want_dense)
+    assert np.all(csc[colptr[2] - 1:colptr[3] - 1] == 0) and np.all(dense[~A] == 0)
+    # rectangular residuals: D is (C, M), and a caller's f_in is what a forward difference subtracts
+    f = X.fixture("sparse", M, N, colptr, rowval)
+    x = np.random.default_rng(1).random(N)
+    eps, _ = X.epsilons(x, c0, C, "forward")
+    fin = np.arange(M, dtype=np.float64)
+    for fdtype in ("forward", "central"):
+        assert X.colour_values(f, x, c0, C, eps, fdtype).shape == (C, M)
+    shifted = X.colour_values(f, x, c0, C, eps, "forward", f_in=fin)
+    xp = np.where(c0 == 1, x + eps[1], x + 0.0)
+    assert X.same_bits(shifted[1], (f(xp) - fin) / eps[1]).all()
+
+
+def test_general_colourings_are_what_their_names_say():
+    for pname in ("random_band", "random_band600", "ragged", "wide", "tall", "lap5", "tiny_65", "tiny_257"):
+        M, N, colptr, rowval = G.pattern(pname)
+        g, n5, inv = (G.colouring(pname, k) for k in ("greedy", "none5", "invalid"))
+        assert color_model.valid(M, colptr, rowval, g) and g.min() >= 1
+        assert color_model.valid(M, colptr, rowval, n5) and (n5 == 0).sum() == 5
+        assert not color_model.valid(M, colptr, rowval, inv) and inv.max() <= 6 and inv.min() >= 1
+        for c in (g, inv):                                        # not cyclic: the step-size reduction reads the colours
+            assert not np.array_equal(c, (np.arange(N) + c[0] - 1) % c.max() + 1)
+    M, N, colptr, rowval = G.pattern("lap5")
+    for kind in ("stencil", "stencil_none5"):
+        c = G.colouring("lap5", kind)
+        assert color_model.valid(M, colptr, rowval, c) and c.max() == 5 and (c == 0).sum() == (5 if kind == "stencil_none5" else 0)
+        assert not np.array_equal(c, (np.arange(N) + c[0] - 1) % 5 + 1)
+    assert G.colouring("random_band", "greedy").max() > 8         # per-colour lists, k_eps_finalize
+    assert G.colouring("ragged", "greedy").max() >= 3000          # (one colour per column of the dense row: Int32 colours)
+
+
+_KEYS = {}
+for _c in G.CASES:
+    _KEYS.setdefault(G.model_key(_c), _c)
+
+
+@pytest.mark.parametrize("case", list(_KEYS.values()), ids=[c["id"] for c in _KEYS.values()])
+def test_general_cases_keep_most_stored_values_finite(case):
+    # the condition under which a bit-for-bit comparison of a case means something: at least 90 % of the stored values are finite
+    # (a NaN matches any NaN).  few_huge must reach the scaled norm, nan_inf a non-finite step size.
+    want, eps, scaled = G.model(case)
+    assert want.size > 0
+    frac = float(np.isfinite(want).mean())
+    assert frac >= G.MIN_FINITE, (case["id"], frac)
+    if case["family"] == "few_huge":
+        assert scaled.any() and np.isfinite(eps).all() and frac < 1.0
+    if case["family"] == "nan_inf":
+        assert np.isnan(eps).any() and frac < 1.0
+    if case["family"] == "cancel":              # the 1e30 columns are one colour's, and every x + eps is absorbed: zero numerators
+        inp = G.inputs(case)
+        assert np.unique(inp["colors"][inp["x"] >= 1e30]).size == 1 and (inp["x"] >= 1e30).sum() > 8
+        assert np.isfinite(eps).all() and (want == 0).all()
+    if case["family"] in ("tiny_1e-200", "subnormal") and case["dtype"] == "f64":
+        assert scaled.any()

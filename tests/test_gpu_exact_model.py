@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import exact_model as X
+from exact_operands import operands as _operands
 from finitediff_jl_amd import patterns as P
 import finitediff_jl_amd as fd
 
@@ -21,60 +22,16 @@ def _ulps(a, b):
     return np.abs(a.view(it).astype(np.int64) - b.view(it).astype(np.int64))
 
 
-def _operands(case, N, C, dtype, seed):
-    """(x, relstep, absstep): the operand families of the matrix (colour k of column j is (j + shift) mod C, or the grid's)."""
-    rng = np.random.default_rng(seed)
-    x = rng.random(N) - 0.25
-    rel, ab = None, None
-    pick = lambda k: np.arange(N) % max(C, 1) == k % max(C, 1)
-    if case == "signed_zeros":
-        x[rng.random(N) < 0.5] = -0.0
-        x[rng.random(N) < 0.3] = 0.0
-    elif case == "cancel":                       # x + eps absorbed in a colour: zero numerators
-        x[pick(1)] = 1e30 * (1 + rng.random(int(pick(1).sum())))
-        rel, ab = 1e-30, 1e-30
-    elif case == "eps_2p100_in":
-        rel, ab = 1e-300, 2.0 ** 100
-    elif case == "eps_2p100_out":
-        rel, ab = 1e-300, 2.0 ** 100 * (1 + 2.0 ** -40)
-    elif case == "eps_2m100_in":
-        rel, ab = 1e-300, 2.0 ** -100
-    elif case == "eps_2m100_out":
-        rel, ab = 1e-300, 2.0 ** -100 * (1 - 2.0 ** -40)
-    elif case == "num_2p800":
-        x = x * 1e240                            # numerators ~2^800, and a sum of squares that overflows (scaled norm)
-    elif case == "huge_range":
-        k = np.nonzero(pick(0))[0]
-        x[k] = 10.0 ** rng.uniform(154, 300, k.size) * np.where(rng.random(k.size) < 0.5, -1, 1)
-    elif case == "tiny_1e-200":
-        x = x * 1e-200
-        ab = 0.0
-    elif case == "subnormal":
-        x = 5e-324 * rng.integers(-1000, 1000, N).astype(np.float64)
-        ab = 0.0
-    elif case == "nan_inf":
-        if N >= 3 * C:
-            x[C * (N // (3 * C)) + 0] = np.nan
-            x[C * (N // (3 * C)) + 1 + C] = np.inf
-            x[C * (2 * N // (3 * C)) + 2 + C] = -np.inf
-    elif case == "f32_huge":
-        x[pick(0)] = 3.0e38
-        x[pick(2)] = -3.3e38
-    elif case == "f32_subnormal":
-        x = (1.4e-45 * rng.integers(-1000, 1000, N)).astype(np.float64)
-        ab = 0.0
-    return x.astype(dtype), rel, ab
-
-
 CASES64 = ["ordinary", "signed_zeros", "cancel", "eps_2p100_in", "eps_2p100_out", "eps_2m100_in", "eps_2m100_out", "num_2p800",
            "huge_range", "tiny_1e-200", "subnormal", "nan_inf"]
 CASES32 = ["ordinary", "signed_zeros", "f32_huge", "f32_subnormal", "nan_inf"]
 
 
-def _check(plan, outs_dev, want_outs, x, c0, C, fdtype, rel, ab, dir, dtype, f, defined_order=True):
+def _check(plan, outs_dev, want_outs, x, c0, C, fdtype, rel, ab, dir, dtype, f, defined_order=True, f_in=None):
     """The step sizes (bits, or 4 ulps + mpmath semantics after the scaled norm), then every stored value against the model.
     defined_order=False: a reduction with a summation order of its own (more than kRegColors = 8 colours, the single-workgroup
-    small-problem launch) -- its plain sums are within 4 ulps of the model's, NaN where the model's are."""
+    small-problem launch) -- its plain sums are within 4 ulps of the model's, NaN where the model's are.  f_in: the caller's f(x) of
+    a forward difference, which the model subtracts as it is given."""
     got_eps = plan.epsilons().astype(dtype)
     eps, scaled = X.epsilons(x, c0, C, fdtype, relstep=rel, absstep=ab, dir=dir, dtype=dtype)
     plain = ~scaled
@@ -86,7 +43,7 @@ def _check(plan, outs_dev, want_outs, x, c0, C, fdtype, rel, ab, dir, dtype, f, 
     assert ok.all(), ("eps", got_eps, eps)
     if scaled.any():
         assert (_ulps(got_eps[scaled], eps[scaled]) <= 4).all(), ("scaled eps", got_eps, eps)
-    D = X.colour_values(f, x, c0, C, got_eps, fdtype)
+    D = X.colour_values(f, x, c0, C, got_eps, fdtype, f_in=f_in)
     for o, lay in zip(outs_dev, want_outs(D)):
         g = o.cpu().numpy()
         m = X.same_bits(g, lay)

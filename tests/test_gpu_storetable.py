@@ -48,7 +48,8 @@ def lap7_np(fx, xx, nx, ny, nz):
 
 
 def sparse_np_factory(M, N, colptr, rowval):
-    """FD_F_SPARSE in numpy: f_r = sum over the entries (r, j), ascending j, left to right, of w(r, j) phi(x_j)."""
+    """FD_F_SPARSE in numpy: f_r = sum over the entries (r, j), ascending j, left to right, of w(r, j) phi(x_j).  (Float64; the exact
+    model's sparse_f -- tests/exact_model.py -- restates it in the element type and is held to these bits by tests/test_exact_model.py.)"""
     cols = P.csc_cols(colptr) - 1
     rows = rowval - 1
     order = np.lexsort((cols, rows))             # by row, then by column

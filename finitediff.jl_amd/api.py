@@ -689,6 +689,101 @@ class CscSolver:
         return out + [nlong.value]
 
 
+class CscLeastSquares:
+    """fd_csc_lsq: the least-squares consumer.  For a rectangular J (M x N) in ``SparseMatrixCSC`` storage -- the nzval a CSC plan has just
+    written, left on the device -- ``matvec`` enqueues y = J v or y = J^T v and ``solve`` enqueues the damped Gauss-Newton step
+    y = argmin ||J y - b||^2 + mu y^T W y, W = I (``damping="identity"``, Levenberg) or diag(sum_i J_ij^2) (``"colnorm"``, Marquardt), by
+    preconditioned CGLS on the normal equations whose scalars never leave the device.  ``pattern`` is a ``SparseMatrixCSC`` /
+    ``DevicePatternCSC`` or ``(colptr, rowval, M, N)`` with numpy arrays or CUDA tensors of int32 / int64 (``idx_base``-based).  A solve
+    that does not converge within ``max_iterations`` (``status()`` flags bit 0) or breaks down (bit 1) fills y and r_out with NaN unless
+    ``set_policy(True)``."""
+
+    DAMPING = {"identity": 0, "colnorm": 1}
+
+    def __init__(self, pattern, ctx=None, dtype=np.float64, idx_base=1):
+        self.ctx = ctx or Context.default()
+        self.dtype = np.dtype(dtype)
+        self.Lt = _l.typed(self.ctx.L, self.dtype)
+        if isinstance(pattern, (SparseMatrixCSC, DevicePatternCSC)):
+            colptr, rowval, M, N = pattern.colptr, pattern.rowval, pattern.m, pattern.n
+            idx_base = getattr(pattern, "idx_base", 1)
+        else:
+            colptr, rowval, M, N = pattern
+        dev = _is_torch(colptr) and colptr.is_cuda
+        if dev:
+            if not (_is_torch(rowval) and rowval.is_cuda) or rowval.dtype != colptr.dtype or colptr.element_size() not in (4, 8):
+                raise TypeError("colptr and rowval must be CUDA tensors of one integer type (int32 or int64)")
+            colptr, rowval = colptr.contiguous(), rowval.contiguous()
+            ib, pc, pr = colptr.element_size(), colptr.data_ptr(), rowval.data_ptr()
+        else:
+            colptr = np.ascontiguousarray(colptr.numpy() if _is_torch(colptr) else colptr)
+            rowval = np.ascontiguousarray(rowval.numpy() if _is_torch(rowval) else rowval)
+            if colptr.dtype not in (np.int32, np.int64) or rowval.dtype != colptr.dtype:
+                raise TypeError("colptr and rowval must be int32 or int64 arrays of one type")
+            ib, pc, pr = colptr.dtype.itemsize, colptr.ctypes.data, rowval.ctypes.data
+        if colptr.shape[0] != int(N) + 1:
+            raise ValueError("colptr must hold N + 1 entries")
+        h = C.c_void_p()
+        _l.check(self.Lt.fd_csc_lsq_create(self.ctx.handle, int(M), int(N), pc, pr or None, ib, int(idx_base), _l.DEVICE if dev else _l.HOST, C.byref(h)))
+        self.handle, self.M, self.N = h, int(M), int(N)
+        self._fin = weakref.finalize(self, self.Lt.fd_csc_lsq_destroy, h)
+
+    def _dev(self, a, what):
+        p, k, _keep = _ptr(a, what, self.dtype)
+        if k != _l.DEVICE:
+            raise ValueError("the consumer takes device arrays")
+        return p
+
+    def _vals(self, J):
+        return self._dev(J.nzval if isinstance(J, (SparseMatrixCSC, DevicePatternCSC)) else J, "J")
+
+    def matvec(self, J, v, y, transpose=False):
+        """Enqueue y = J v (v of N, y of M) or, transposed, y = J^T v (v of M, y of N) on the context's stream (fd_csc_lsq_matvec_async)."""
+        _l.check(self.Lt.fd_csc_lsq_matvec_async(self.handle, self._vals(J), self._dev(v, "v"), self._dev(y, "y"), 1 if transpose else 0))
+
+    def solve(self, J, b, y, mu=0.0, damping="identity", r_out=None):
+        """Enqueue (J^T J + mu W) y = J^T b on the context's stream (fd_csc_lsq_solve_async); ``r_out`` (M elements) receives b - J y."""
+        kind = self.DAMPING.get(damping, damping)
+        _l.check(self.Lt.fd_csc_lsq_solve_async(self.handle, float(mu), int(kind), self._vals(J), self._dev(b, "b"), self._dev(y, "y"),
+                                                None if r_out is None else self._dev(r_out, "r_out")))
+
+    def set_options(self, rtol=1e-10, max_iterations=500):
+        _l.check(self.Lt.fd_csc_lsq_set_options(self.handle, float(rtol), int(max_iterations)))
+
+    def set_policy(self, keep_unconverged):
+        _l.check(self.Lt.fd_csc_lsq_set_policy(self.handle, 1 if keep_unconverged else 0))
+
+    def status(self):
+        """Synchronises.  {"flags": bit 0 not converged | bit 1 breakdown, "iterations", "grad": the recurred
+        ||J^T (b - J y) - mu W y||_2, "grad0": ||J^T b||_2}."""
+        f, it, g, g0 = C.c_int(), C.c_int64(), C.c_double(), C.c_double()
+        _l.check(self.Lt.fd_csc_lsq_status(self.handle, C.byref(f), C.byref(it), C.byref(g), C.byref(g0)))
+        return {"flags": f.value, "iterations": it.value, "grad": g.value, "grad0": g0.value}
+
+    def _ints(self, p, n):
+        import torch
+        if n == 0:
+            return torch.empty(0, dtype=torch.int32, device="cuda:%d" % self.ctx.device)
+        view = _DevView(p, n, False)
+        view.__cuda_array_interface__["typestr"] = "<i4"
+        return torch.as_tensor(view, device="cuda:%d" % self.ctx.device).clone()
+
+    def row_lists(self):
+        """The consumer's lists as int32 CUDA tensors (copies): row_ptr, row_col, row_slot; and the number of long rows."""
+        ps = [C.c_void_p() for _ in range(3)]
+        nnz, nlong = C.c_int64(), C.c_int64()
+        _l.check(self.Lt.fd_csc_lsq_row_lists(self.handle, *[C.byref(p) for p in ps], C.byref(nnz), C.byref(nlong)))
+        self.ctx.synchronize()
+        return [self._ints(p.value, n) for p, n in zip(ps, (self.M + 1, nnz.value, nnz.value))] + [nlong.value]
+
+    def long_columns(self):
+        """The columns of more than 32 entries, ascending, as an int32 CUDA tensor (a copy)."""
+        p, n = C.c_void_p(), C.c_int64()
+        _l.check(self.Lt.fd_csc_lsq_long_columns(self.handle, C.byref(p), C.byref(n)))
+        self.ctx.synchronize()
+        return self._ints(p.value, n.value)
+
+
 class BlockTridiagSolver:
     """fd_blocktridiag_solver: (alpha*I + beta*J) y = b on the device for a block-tridiagonal J of ``nblk`` dense ``b x b`` blocks
     (b <= 32) in ``BlockBandedMatrix`` data (block bandwidths (1, 1), uniform block sizes) -- the storage a block-banded plan fills

@@ -1,0 +1,660 @@
+// The LEAST-SQUARES consumer: for a rectangular J (M x N) in SparseMatrixCSC storage, on the nzval a CSC plan has just written,
+//     y = J v,   y = J^T v,   and the damped Gauss-Newton step   (J^T J + mu W) y = J^T b,   W = I or diag(g), g_j = sum_i J_ij^2,
+// by CGLS on the normal equations (J^T J is never formed) preconditioned by m_j = g_j + mu w_j.  DESIGN.md 4.10 has the contract;
+// tests/csc_lsq_model.py restates every order below in numpy and the GPU tests compare bits.
+//
+// CREATE (device): as the square consumer's (fdjac_csc_common.h), rows against M and colptr against N + 1: the pattern by rows (sorted by
+// slot = by column), the rows of more than kCsLong entries, a lane order per tile of 256 rows; and the same for the columns on colptr
+// itself: the columns of more than kCsLong entries in ASCENDING order (flags, a scan, a scatter) and a lane order per tile of 256 columns.
+//
+// ORDERS.  Row r of at most kCsLong entries: acc = 0; acc += nzval[slot_k] * v[col_k], k ascending (ascending column); a longer row by
+// one workgroup: thread t adds entries t, t + 256, ... in that order, then block_sum().  Column j of at most kCsLong entries: one lane, storage
+// order from +0.0 (g_j: acc += a * a; the product: acc += a * v[row]); a longer column by one workgroup in the same way as a long row.  No
+// LDS window of v.  A tile's results cross LDS once, so that everything behind the sums (s, z, the dots) is formed in row / column order.
+// Dots of the product kernels: tiles of 256 (element t), dots of the vector kernels: tiles of kCsVecTile (thread t adds t, t + 256, t + 512,
+// t + 768), block_sum() per tile, the last-arriving workgroup (an integer ticket) adds the tiles' sums.  All arithmetic is Float64 for
+// either element type, nothing is contracted into an FMA, no floating-point atomics, no grid-wide barrier.
+//
+// THE SOLVE.  r = b, y = 0.  k_cl_cols<1>: g, s = J^T r, m = g + mu w (zero or not finite: breakdown), z = s / m, p = z, gamma = s.z,
+// ||s||^2 (-> tol^2 = rtol^2 ||s||^2; 0: done, no iteration), pi = sum (w p) p.  An iteration is four launches (+ 1 with long rows, + 1 with
+// long columns):
+//   k_cl_rows<1>   q = J p, q.q;  delta = q.q + mu pi (zero or not finite: breakdown);  alpha = gamma / delta
+//   k_cl_update    r = r - alpha q,  y = y + alpha p
+//   k_cl_cols<2>   s = J^T r - mu (w y), z = s / m, gamma' = s.z, ||s||^2;  the iteration is counted;  ||s||^2 <= tol^2: done;  gamma' not
+//                  finite: breakdown;  otherwise beta = gamma' / gamma, gamma = gamma'
+//   k_cl_p         p = z + beta p,  pi = sum (w p) p
+// Every kernel of an iteration reads the `done` word first and leaves.
+#include "fdjac_internal.h"
+#include "fdjac_device.h"
+#include "fdjac_csc_common.h"
+#include <cmath>
+#include <cstring>
+#include <new>
+
+namespace fdjac {
+
+// scalars of a least-squares solve, in device memory
+enum { LS_GAMMA = 0, LS_ALPHA, LS_BETA, LS_PI, LS_TOL2, LS_GN2, LS_G02, LS_NSCAL = 8 };
+
+struct ClPat {                         // the pattern as the kernels see it
+    int M, N, nnz, nlong_r, nlong_c;
+    const int *colptr, *rowval, *row_ptr, *row_col, *row_slot, *row_order, *long_rows, *col_order, *long_cols;
+};
+struct ClVecs { double *r, *q, *y, *p, *s, *z, *m, *g; };      // r, q: M doubles; the others: N
+
+__device__ __forceinline__ bool cl_not_finite(double x) { return !(fabs(x) < __builtin_huge_val()); }
+__device__ __forceinline__ void cl_breakdown(int *words)
+{
+    atomicOr(words + W_FLAGS, 2);
+    __hip_atomic_store(words + W_DONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// ---- create ------------------------------------------------------------------------------------------------------------------------
+// one lane per entry: its row (validated against M, 0-based), its column (binary search in the monotone cptr), rows strictly ascending
+// within the column, the row's count
+__global__ void __launch_bounds__(kBlock) k_cl_entries(const void *__restrict__ rowval, int ib, int base, const int *__restrict__ cptr,
+                                                       int64_t M, int64_t N, int64_t nnz, int *__restrict__ erow, int *__restrict__ ecol,
+                                                       int *__restrict__ rcnt, unsigned *err)
+{
+    for (int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x; q < nnz; q += (int64_t)gridDim.x * kBlock) {
+        const int64_t r = cs_load(rowval, ib, q) - base;
+        const bool ok = r >= 0 && r < M;
+        int64_t lo = 0, hi = N;      // cptr[lo] <= q < cptr[hi]
+        while (hi - lo > 1) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (cptr[mid] <= q) lo = mid; else hi = mid;
+        }
+        erow[q] = ok ? (int)r : 0;
+        ecol[q] = (int)lo;
+        if (!ok) { atomicOr(err, (unsigned)CS_BAD_ROW); continue; }
+        if (q > cptr[lo] && cs_load(rowval, ib, q - 1) - base >= r) atomicOr(err, (unsigned)CS_BAD_ORDER);
+        atomicAdd(&rcnt[r], 1);
+    }
+}
+// the long columns in ascending order: a flag per column, its exclusive scan, a scatter
+__global__ void __launch_bounds__(kBlock) k_cl_flag_long(const int *__restrict__ ptr, int64_t n, int *__restrict__ flag)
+{
+    const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (j < n) flag[j] = ptr[j + 1] - ptr[j] > kCsLong ? 1 : 0;
+}
+__global__ void __launch_bounds__(kBlock) k_cl_scatter_long(const int *__restrict__ ptr, int64_t n, const int *__restrict__ pos, int *__restrict__ list)
+{
+    const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (j < n && ptr[j + 1] - ptr[j] > kCsLong) list[pos[j]] = (int)j;
+}
+
+// ---- products --------------------------------------------------------------------------------------------------------------------------
+// long rows first: workgroup i sums row long_rows[i] and writes y there; the row kernel then takes those values from y
+template <typename TV>
+__global__ void __launch_bounds__(kBlock) k_cl_long_rows(ClPat P, const real_t *__restrict__ nz, const TV *__restrict__ v, TV *__restrict__ y,
+                                                         const int *words)
+{
+    __shared__ double s_w[kBlock / 64];
+    if (words && cs_word(words, W_DONE)) return;
+    const int r = P.long_rows[blockIdx.x], a = P.row_ptr[r], n = P.row_ptr[r + 1] - a;
+    double acc = 0.0;
+    for (int k = threadIdx.x; k < n; k += kBlock) acc += (double)nz[P.row_slot[a + k]] * (double)v[P.row_col[a + k]];
+    const double t = cs_block_sum(acc, s_w);
+    if (threadIdx.x == 0) y[r] = (TV)t;
+}
+
+// rows: a tile of 256 rows per workgroup, lane i takes row row_order[tile * 256 + i]; v is read from memory; the results cross LDS once so
+// that y is written -- and q.q is summed -- in row order.  MODE 0: y only.  1: q = J p of an iteration, q.q -> delta, alpha.
+template <typename TV, int MODE>
+__global__ void __launch_bounds__(kBlock) k_cl_rows(ClPat P, const real_t *__restrict__ nz, const TV *__restrict__ v, TV *__restrict__ y,
+                                                    double mu, double *scal, int *words, double *part)
+{
+    __shared__ double s_out[kBlock];
+    __shared__ double s_w[kBlock / 64];
+    if (MODE != 0 && cs_word(words, W_DONE)) return;
+    const int r0 = (int)blockIdx.x * kBlock;
+    const int r = P.row_order[r0 + threadIdx.x];
+    if (r >= 0) {
+        const int a = P.row_ptr[r], n = P.row_ptr[r + 1] - a;
+        if (n <= kCsLong) {
+            double acc = 0.0;
+            for (int k0 = 0; k0 < n; k0 += 8) {      // eight entries' gathers requested before the first is used
+                double pa[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pv[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    if (k0 + k < n) {
+                        pa[k] = (double)nz[P.row_slot[a + k0 + k]];
+                        pv[k] = (double)v[P.row_col[a + k0 + k]];
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < 8; ++k) if (k0 + k < n) acc += pa[k] * pv[k];
+            }
+            s_out[r - r0] = acc;
+        } else {
+            s_out[r - r0] = (double)y[r];         // k_cl_long_rows has written it
+        }
+    }
+    __syncthreads();
+    const int row = r0 + threadIdx.x;
+    double yr = 0.0;
+    if (row < P.M) {
+        yr = s_out[threadIdx.x];
+        y[row] = (TV)yr;
+    }
+    if (MODE == 1) {
+        double mine[1] = {row < P.M ? yr * yr : 0.0}, tot[1];
+        if (cs_finish<1>(mine, part, words, tot, s_w) && threadIdx.x == 0) {
+            const double delta = tot[0] + mu * scal[LS_PI];
+            if (cs_bad_pivot(delta)) cl_breakdown(words);
+            else scal[LS_ALPHA] = scal[LS_GAMMA] / delta;
+        }
+    }
+}
+
+// long columns first: workgroup i sums column long_cols[i] and writes y there (WITH_G: and g_j = sum a^2 into g); the column kernel then
+// takes those values from y / g
+template <typename TV, int WITH_G>
+__global__ void __launch_bounds__(kBlock) k_cl_long_cols(ClPat P, const real_t *__restrict__ nz, const TV *__restrict__ v, TV *__restrict__ y,
+                                                         double *__restrict__ g, const int *words)
+{
+    __shared__ double s_w[kBlock / 64];
+    if (words && cs_word(words, W_DONE)) return;
+    const int j = P.long_cols[blockIdx.x], a = P.colptr[j], n = P.colptr[j + 1] - a;
+    double acc = 0.0, accg = 0.0;
+    for (int k = threadIdx.x; k < n; k += kBlock) {
+        const double e = (double)nz[a + k];
+        acc += e * (double)v[P.rowval[a + k]];
+        if (WITH_G) accg += e * e;
+    }
+    const double t = cs_block_sum(acc, s_w);
+    if (threadIdx.x == 0) y[j] = (TV)t;
+    if (WITH_G) {
+        const double tg = cs_block_sum(accg, s_w);
+        if (threadIdx.x == 0) g[j] = tg;
+    }
+}
+
+// columns: a tile of 256 columns per workgroup, lane i takes column col_order[tile * 256 + i] (storage order from +0.0, eight entries'
+// gathers ahead); the results cross LDS once so that what follows is formed in column order.
+// MODE 0: y = J^T v.   1: the start of a solve (v = r = b; y = V.s).   2: step 3 of an iteration (v = r; y = V.s).
+template <typename TV, int MODE>
+__global__ void __launch_bounds__(kBlock) k_cl_cols(ClPat P, const real_t *__restrict__ nz, const TV *v, TV *y, ClVecs V,
+                                                    double mu, int kind, double rtol, double *scal, int *words, double *part)
+{
+    __shared__ double s_out[kBlock];
+    __shared__ double s_g[MODE == 1 ? kBlock : 1];
+    __shared__ double s_w[kBlock / 64];
+    if (MODE == 2 && cs_word(words, W_DONE)) return;
+    const int j0 = (int)blockIdx.x * kBlock;
+    const int j = P.col_order[j0 + threadIdx.x];
+    if (j >= 0) {
+        const int a = P.colptr[j], n = P.colptr[j + 1] - a;
+        if (n <= kCsLong) {
+            double acc = 0.0, accg = 0.0;
+            for (int k0 = 0; k0 < n; k0 += 8) {
+                double pa[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pv[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    if (k0 + k < n) {
+                        pa[k] = (double)nz[a + k0 + k];
+                        pv[k] = (double)v[P.rowval[a + k0 + k]];
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    if (k0 + k < n) {
+                        acc += pa[k] * pv[k];
+                        if (MODE == 1) accg += pa[k] * pa[k];
+                    }
+                }
+            }
+            s_out[j - j0] = acc;
+            if (MODE == 1) s_g[j - j0] = accg;
+        } else {
+            s_out[j - j0] = (double)y[j];         // k_cl_long_cols has written it
+            if (MODE == 1) s_g[j - j0] = V.g[j];
+        }
+    }
+    __syncthreads();
+    const int col = j0 + threadIdx.x;
+    const bool in = col < P.N;
+    if (MODE == 0) {
+        if (in) y[col] = (TV)s_out[threadIdx.x];
+    } else if (MODE == 1) {
+        double mine[3] = {0.0, 0.0, 0.0}, tot[3];
+        bool bad = false;
+        if (in) {
+            const double g = s_g[threadIdx.x], s = s_out[threadIdx.x];
+            const double w = kind ? g : 1.0;
+            const double m = g + mu * w;
+            bad = cs_bad_pivot(m);
+            const double z = s / m;
+            V.g[col] = g; V.m[col] = m; V.s[col] = s; V.z[col] = z; V.p[col] = z; V.y[col] = 0.0;
+            mine[0] = s * z; mine[1] = s * s; mine[2] = (w * z) * z;
+        }
+        if (bad) atomicOr(words + W_FLAGS, 2);
+        if (cs_finish<3>(mine, part, words, tot, s_w) && threadIdx.x == 0) {
+            scal[LS_GAMMA] = tot[0]; scal[LS_PI] = tot[2]; scal[LS_ALPHA] = 0.0; scal[LS_BETA] = 0.0;
+            scal[LS_GN2] = tot[1]; scal[LS_G02] = tot[1];
+            scal[LS_TOL2] = (rtol * rtol) * tot[1];
+            int done = 0;
+            if (tot[1] == 0.0) done = 1;                                             // J^T b = 0: y = 0, no iteration
+            else if (cs_word(words, W_FLAGS) & 2) done = 1;                          // an m_j that is zero or not finite
+            else if (cl_not_finite(tot[0])) { atomicOr(words + W_FLAGS, 2); done = 1; }   // gamma
+            if (done) __hip_atomic_store(words + W_DONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    } else {
+        double mine[2] = {0.0, 0.0}, tot[2];
+        if (in) {
+            const double w = kind ? V.g[col] : 1.0;
+            const double s = s_out[threadIdx.x] - mu * (w * V.y[col]);
+            const double z = s / V.m[col];
+            V.s[col] = s; V.z[col] = z;
+            mine[0] = s * z; mine[1] = s * s;
+        }
+        if (cs_finish<2>(mine, part, words, tot, s_w) && threadIdx.x == 0) {
+            scal[LS_GN2] = tot[1];
+            words[W_ITERS] = words[W_ITERS] + 1;
+            if (tot[1] <= scal[LS_TOL2]) {
+                __hip_atomic_store(words + W_DONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            } else if (cl_not_finite(tot[0])) {
+                cl_breakdown(words);
+            } else {
+                scal[LS_BETA] = tot[0] / scal[LS_GAMMA];
+                scal[LS_GAMMA] = tot[0];
+            }
+        }
+    }
+}
+
+// ---- the vector kernels ----------------------------------------------------------------------------------------------------------------
+// r = b (the element type widened)
+__global__ void __launch_bounds__(kBlock) k_cl_start(int M, const real_t *__restrict__ b, double *__restrict__ r)
+{
+    const int i0 = blockIdx.x * kCsVecTile + threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < kCsVecTile / kBlock; ++k) {
+        const int i = i0 + k * kBlock;
+        if (i < M) r[i] = (double)b[i];
+    }
+}
+// r = r - alpha q (M elements), y = y + alpha p (N elements)
+__global__ void __launch_bounds__(kBlock) k_cl_update(int M, int N, ClVecs V, const double *scal, const int *words)
+{
+    if (cs_word(words, W_DONE)) return;
+    const double al = scal[LS_ALPHA];
+    const int i0 = blockIdx.x * kCsVecTile + threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < kCsVecTile / kBlock; ++k) {
+        const int i = i0 + k * kBlock;
+        if (i < M) V.r[i] = V.r[i] - al * V.q[i];
+        if (i < N) V.y[i] = V.y[i] + al * V.p[i];
+    }
+}
+// p = z + beta p, pi = sum (w p) p
+__global__ void __launch_bounds__(kBlock) k_cl_p(int N, int kind, ClVecs V, double *scal, int *words, double *part)
+{
+    __shared__ double s_w[kBlock / 64];
+    if (cs_word(words, W_DONE)) return;
+    const double bk = scal[LS_BETA];
+    const int i0 = blockIdx.x * kCsVecTile + threadIdx.x;
+    double mine[1] = {0.0}, tot[1];
+#pragma unroll
+    for (int k = 0; k < kCsVecTile / kBlock; ++k) {
+        const int i = i0 + k * kBlock;
+        if (i >= N) continue;
+        const double p = V.z[i] + bk * V.p[i];
+        const double w = kind ? V.g[i] : 1.0;
+        V.p[i] = p;
+        mine[0] += (w * p) * p;
+    }
+    if (cs_finish<1>(mine, part, words, tot, s_w) && threadIdx.x == 0) scal[LS_PI] = tot[0];
+}
+// the end: bit 0 when the iterations ran out; y and the residual, or NaN after a failure unless the caller keeps the last iterate
+__global__ void __launch_bounds__(kBlock) k_cl_final(int M, int N, ClVecs V, real_t *__restrict__ y, real_t *__restrict__ r_out, int *words, int keep)
+{
+    const int flags = (cs_word(words, W_FLAGS) & 2) | (cs_word(words, W_DONE) ? 0 : 1);
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i == 0) words[W_FINAL] = flags;
+    const bool nan = flags && !keep;
+    const double qnan = __longlong_as_double(0x7FF8000000000000ll);
+    if (i < N) y[i] = (real_t)(nan ? qnan : V.y[i]);
+    if (r_out && i < M) r_out[i] = (real_t)(nan ? qnan : V.r[i]);
+}
+
+}  // namespace fdjac
+
+struct fd_csc_lsq {
+    fd_ctx *ctx = nullptr;
+    int64_t M = 0, N = 0, nnz = 0;
+    int nlong_r = 0, nlong_c = 0, batch = fdjac::kCsBatchDefault;
+    int *d_colptr = nullptr, *d_rowval = nullptr, *d_row_ptr = nullptr, *d_row_col = nullptr, *d_row_slot = nullptr, *d_row_order = nullptr,
+        *d_long_rows = nullptr, *d_col_order = nullptr, *d_long_cols = nullptr;
+    double *d_vec = nullptr;           // r, q (M doubles each), then y, p, s, z, m, g (N each)
+    double *d_part = nullptr;          // the tiles' sums: 3 x ceil(max(M, N) / 256)
+    double *d_scal = nullptr;
+    int *d_words = nullptr;
+    fdjac::CsRecord *h_rec = nullptr;  // pinned: one record per batch in flight (two)
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    double rtol = 1e-10;
+    int max_iterations = 500, keep = 0;
+    bool solved = false;
+};
+
+using namespace fdjac;
+
+static void cl_free(fd_csc_lsq *s)
+{
+    void *ptrs[] = {s->d_colptr, s->d_rowval, s->d_row_ptr, s->d_row_col, s->d_row_slot, s->d_row_order, s->d_long_rows, s->d_col_order,
+                    s->d_long_cols, s->d_vec, s->d_part, s->d_scal, s->d_words};
+    for (void *p : ptrs) if (p) (void)hipFree(p);
+    if (s->h_rec) (void)hipHostFree(s->h_rec);
+    for (hipEvent_t e : s->ev) if (e) (void)hipEventDestroy(e);
+    delete s;
+}
+
+static ClPat cl_pat(const fd_csc_lsq *s)
+{
+    ClPat P;
+    P.M = (int)s->M; P.N = (int)s->N; P.nnz = (int)s->nnz; P.nlong_r = s->nlong_r; P.nlong_c = s->nlong_c;
+    P.colptr = s->d_colptr; P.rowval = s->d_rowval; P.row_ptr = s->d_row_ptr; P.row_col = s->d_row_col; P.row_slot = s->d_row_slot;
+    P.row_order = s->d_row_order; P.long_rows = s->d_long_rows; P.col_order = s->d_col_order; P.long_cols = s->d_long_cols;
+    return P;
+}
+static ClVecs cl_vecs(const fd_csc_lsq *s)
+{
+    ClVecs V;
+    const size_t M = (size_t)s->M, N = (size_t)s->N;
+    V.r = s->d_vec; V.q = V.r + M; V.y = V.q + M; V.p = V.y + N; V.s = V.p + N; V.z = V.s + N; V.m = V.z + N; V.g = V.m + N;
+    return V;
+}
+static unsigned cl_tiles(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
+
+int fd_csc_lsq_create(fd_ctx *ctx, int64_t M, int64_t N, const void *colptr, const void *rowval, int idx_bytes, int idx_base, int idx_kind,
+                      fd_csc_lsq **out)
+{
+    FD_REQUIRE(out != nullptr, FD_ERR_ARG, "NULL argument");
+    *out = nullptr;
+    if (!ctx) {      // (no context can exist without a device: say which of the two is the matter)
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { (void)hipGetLastError(); FD_REQUIRE(false, FD_ERR_NODEVICE, "no HIP device"); }
+        FD_REQUIRE(false, FD_ERR_ARG, "ctx is NULL");
+    }
+    FD_REQUIRE(colptr != nullptr, FD_ERR_ARG, "colptr is NULL");
+    FD_REQUIRE(M >= 1 && M < ((int64_t)1 << 31) - 4096, FD_ERR_ARG, "M = %lld", (long long)M);
+    FD_REQUIRE(N >= 1 && N < ((int64_t)1 << 31) - 4096, FD_ERR_ARG, "N = %lld", (long long)N);
+    FD_REQUIRE(idx_bytes == 4 || idx_bytes == 8, FD_ERR_ARG, "idx_bytes = %d (4 or 8)", idx_bytes);
+    FD_REQUIRE(idx_base == 0 || idx_base == 1, FD_ERR_ARG, "idx_base = %d (0 or 1)", idx_base);
+    FD_REQUIRE(idx_kind == FD_HOST || idx_kind == FD_DEVICE, FD_ERR_ARG, "idx_kind = %d", idx_kind);
+    FD_HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    // nnz from the two ends of colptr
+    int64_t ends[2] = {0, 0};
+    for (int k = 0; k < 2; ++k) {
+        const char *src = (const char *)colptr + (size_t)(k ? N : 0) * idx_bytes;
+        int64_t v64 = 0; int32_t v32 = 0;
+        void *dst = idx_bytes == 8 ? (void *)&v64 : (void *)&v32;
+        if (idx_kind == FD_DEVICE) { FD_HIP_CHECK(hipStreamSynchronize(st)); FD_HIP_CHECK(hipMemcpy(dst, src, idx_bytes, hipMemcpyDeviceToHost)); }
+        else std::memcpy(dst, src, idx_bytes);
+        ends[k] = idx_bytes == 8 ? v64 : (int64_t)v32;
+    }
+    const int64_t nnz = ends[1] - ends[0];
+    FD_REQUIRE(ends[0] == idx_base, FD_ERR_SHAPE, "colptr[first] = %lld, expected the index base %d", (long long)ends[0], idx_base);
+    FD_REQUIRE(nnz >= 0 && nnz < ((int64_t)1 << 31) - 4096, FD_ERR_SHAPE, "colptr[last] - colptr[first] = %lld entries (0 <= nnz < 2^31)", (long long)nnz);
+    FD_REQUIRE(nnz == 0 || rowval != nullptr, FD_ERR_ARG, "rowval is NULL");
+
+    fd_csc_lsq *s = new (std::nothrow) fd_csc_lsq();
+    FD_REQUIRE(s != nullptr, FD_ERR_NOMEM, "out of host memory");
+    s->ctx = ctx; s->M = M; s->N = N; s->nnz = nnz;
+    if (const char *v = test_switch("FDJAC_CSC_BATCH")) { const int b = atoi(v); if (b >= 1 && b <= 64) s->batch = b; }
+    const int64_t big = M > N ? M : N, nz1 = nnz > 0 ? nnz : 1;
+    const int64_t mpad = (M + kBlock - 1) / kBlock * kBlock, npad = (N + kBlock - 1) / kBlock * kBlock;
+    const int64_t nscan = (big + kCsScanTile - 1) / kCsScanTile + 2;
+    const int64_t npart = 3 * ((big + kBlock - 1) / kBlock);
+    void *raw_cp = nullptr, *raw_rv = nullptr;
+    int *ecol = nullptr, *cnt = nullptr, *pos = nullptr, *bsum = nullptr, *tmp = nullptr, *misc = nullptr;
+    int rc = FD_OK;
+    unsigned err = 0;
+    int host_misc[4] = {0, 0, 0, 0};      // err, -, the long rows, their cursor
+    int ncl = 0;
+    auto fail = [&](int code) {
+        void *t[] = {raw_cp, raw_rv, ecol, cnt, pos, bsum, tmp, misc};
+        (void)hipStreamSynchronize(st);
+        for (void *p : t) if (p) (void)hipFree(p);
+        if (code != FD_OK) cl_free(s);
+        return code;
+    };
+#define CL_TRY(expr)                                                                                              \
+    do {                                                                                                          \
+        hipError_t _e = (expr);                                                                                   \
+        if (_e != hipSuccess) {                                                                                   \
+            set_error("csc least squares: %s failed: %s", #expr, hipGetErrorString(_e));                          \
+            return fail(_e == hipErrorOutOfMemory ? FD_ERR_NOMEM : FD_ERR_HIP);                                   \
+        }                                                                                                         \
+    } while (0)
+    CL_TRY(hipMalloc((void **)&s->d_colptr, sizeof(int) * (size_t)(N + 1)));
+    CL_TRY(hipMalloc((void **)&s->d_rowval, sizeof(int) * (size_t)nz1));
+    CL_TRY(hipMalloc((void **)&s->d_row_ptr, sizeof(int) * (size_t)(M + 1)));
+    CL_TRY(hipMalloc((void **)&s->d_row_col, sizeof(int) * (size_t)nz1));
+    CL_TRY(hipMalloc((void **)&s->d_row_slot, sizeof(int) * (size_t)nz1));
+    CL_TRY(hipMalloc((void **)&s->d_row_order, sizeof(int) * (size_t)mpad));
+    CL_TRY(hipMalloc((void **)&s->d_col_order, sizeof(int) * (size_t)npad));
+    CL_TRY(hipMalloc((void **)&ecol, sizeof(int) * (size_t)nz1));
+    CL_TRY(hipMalloc((void **)&cnt, sizeof(int) * (size_t)big));
+    CL_TRY(hipMalloc((void **)&pos, sizeof(int) * (size_t)(N + 1)));
+    CL_TRY(hipMalloc((void **)&bsum, sizeof(int) * (size_t)nscan));
+    CL_TRY(hipMalloc((void **)&misc, sizeof(int) * 4));
+    const void *cp = colptr, *rv = rowval;
+    if (idx_kind == FD_HOST) {
+        CL_TRY(hipMalloc(&raw_cp, (size_t)idx_bytes * (size_t)(N + 1)));
+        CL_TRY(hipMemcpyAsync(raw_cp, colptr, (size_t)idx_bytes * (size_t)(N + 1), hipMemcpyHostToDevice, st));
+        cp = raw_cp;
+        if (nnz > 0) {
+            CL_TRY(hipMalloc(&raw_rv, (size_t)idx_bytes * (size_t)nnz));
+            CL_TRY(hipMemcpyAsync(raw_rv, rowval, (size_t)idx_bytes * (size_t)nnz, hipMemcpyHostToDevice, st));
+            rv = raw_rv;
+        }
+    }
+    CL_TRY(hipMemsetAsync(misc, 0, sizeof(int) * 4, st));
+    CL_TRY(hipMemsetAsync(cnt, 0, sizeof(int) * (size_t)big, st));
+    hipLaunchKernelGGL(k_cs_colptr, dim3(csc_grid(N + 1, kBlock)), dim3(kBlock), 0, st, cp, idx_bytes, idx_base, N, nnz, s->d_colptr, (unsigned *)misc);
+    CL_TRY(hipGetLastError());
+    CL_TRY(hipMemcpyAsync(host_misc, misc, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
+    CL_TRY(hipStreamSynchronize(st));
+    err = (unsigned)host_misc[0];
+    if (err & CS_BAD_COLPTR) { set_error("csc least squares: colptr is not a monotone sequence of N + 1 entries from the index base to nnz + base"); return fail(FD_ERR_SHAPE); }
+    if (nnz > 0) {
+        hipLaunchKernelGGL(k_cl_entries, dim3(csc_grid(nnz, kBlock)), dim3(kBlock), 0, st, rv, idx_bytes, idx_base, (const int *)s->d_colptr, M, N, nnz,
+                           s->d_rowval, ecol, cnt, (unsigned *)misc);
+        CL_TRY(hipGetLastError());
+    }
+    CL_TRY(hipMemcpyAsync(host_misc, misc, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
+    CL_TRY(hipStreamSynchronize(st));
+    err = (unsigned)host_misc[0];
+    if (err & CS_BAD_ROW) { set_error("csc least squares: rowval holds a row outside the %lld x %lld matrix", (long long)M, (long long)N); return fail(FD_ERR_SHAPE); }
+    if (err & CS_BAD_ORDER) { set_error("csc least squares: the rows of a column are not strictly ascending"); return fail(FD_ERR_SHAPE); }
+    // the pattern by rows
+    rc = csc_exscan(st, cnt, M, s->d_row_ptr, bsum);
+    if (rc != FD_OK) return fail(rc);
+    CL_TRY(hipMemsetAsync(cnt, 0, sizeof(int) * (size_t)big, st));
+    if (nnz > 0) {
+        hipLaunchKernelGGL(k_cs_fill, dim3(csc_grid(nnz, kBlock)), dim3(kBlock), 0, st, (const int *)s->d_rowval, nnz, (const int *)s->d_row_ptr, cnt, s->d_row_slot);
+        CL_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_cs_sort_short, dim3(cl_tiles(M, kBlock)), dim3(kBlock), 0, st, (const int *)s->d_row_ptr, M, s->d_row_slot, (const int *)ecol,
+                       s->d_row_col, misc + 2);
+    hipLaunchKernelGGL(k_cs_order, dim3(cl_tiles(M, kBlock)), dim3(kBlock), 0, st, (const int *)s->d_row_ptr, M, s->d_row_order);
+    // the columns: their lane order and the long ones in ascending order
+    hipLaunchKernelGGL(k_cs_order, dim3(cl_tiles(N, kBlock)), dim3(kBlock), 0, st, (const int *)s->d_colptr, N, s->d_col_order);
+    hipLaunchKernelGGL(k_cl_flag_long, dim3(cl_tiles(N, kBlock)), dim3(kBlock), 0, st, (const int *)s->d_colptr, N, cnt);
+    CL_TRY(hipGetLastError());
+    rc = csc_exscan(st, cnt, N, pos, bsum);
+    if (rc != FD_OK) return fail(rc);
+    CL_TRY(hipMemcpyAsync(host_misc, misc, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
+    CL_TRY(hipMemcpyAsync(&ncl, pos + N, sizeof(int), hipMemcpyDeviceToHost, st));
+    CL_TRY(hipStreamSynchronize(st));
+    s->nlong_r = host_misc[2];
+    s->nlong_c = ncl;
+    if (s->nlong_r > 0) {
+        CL_TRY(hipMalloc((void **)&s->d_long_rows, sizeof(int) * (size_t)s->nlong_r));
+        CL_TRY(hipMalloc((void **)&tmp, sizeof(int) * (size_t)nz1));
+        hipLaunchKernelGGL(k_cs_list_long, dim3(cl_tiles(M, kBlock)), dim3(kBlock), 0, st, (const int *)s->d_row_ptr, M, s->d_long_rows, misc + 3);
+        hipLaunchKernelGGL(k_cs_sort_long, dim3((unsigned)s->nlong_r), dim3(kBlock), 0, st, (const int *)s->d_row_ptr, (const int *)s->d_long_rows, s->d_row_slot, tmp,
+                           (const int *)ecol, s->d_row_col);
+        CL_TRY(hipGetLastError());
+    }
+    if (s->nlong_c > 0) {
+        CL_TRY(hipMalloc((void **)&s->d_long_cols, sizeof(int) * (size_t)s->nlong_c));
+        hipLaunchKernelGGL(k_cl_scatter_long, dim3(cl_tiles(N, kBlock)), dim3(kBlock), 0, st, (const int *)s->d_colptr, N, (const int *)pos, s->d_long_cols);
+        CL_TRY(hipGetLastError());
+    }
+    CL_TRY(hipMalloc((void **)&s->d_vec, sizeof(double) * (2 * (size_t)M + 6 * (size_t)N)));
+    CL_TRY(hipMalloc((void **)&s->d_part, sizeof(double) * (size_t)npart));
+    CL_TRY(hipMalloc((void **)&s->d_scal, sizeof(double) * LS_NSCAL));
+    CL_TRY(hipMalloc((void **)&s->d_words, sizeof(int) * W_NWORDS));
+    CL_TRY(hipHostMalloc((void **)&s->h_rec, sizeof(CsRecord) * 2, hipHostMallocDefault));
+    CL_TRY(hipEventCreateWithFlags(&s->ev[0], hipEventDisableTiming));
+    CL_TRY(hipEventCreateWithFlags(&s->ev[1], hipEventDisableTiming));
+    CL_TRY(hipMemsetAsync(s->d_scal, 0, sizeof(double) * LS_NSCAL, st));
+    CL_TRY(hipMemsetAsync(s->d_words, 0, sizeof(int) * W_NWORDS, st));
+    CL_TRY(hipStreamSynchronize(st));
+#undef CL_TRY
+    (void)fail(FD_OK);
+    *out = s;
+    return FD_OK;
+}
+
+int fd_csc_lsq_destroy(fd_csc_lsq *s)
+{
+    if (!s) return FD_OK;
+    (void)hipSetDevice(s->ctx->device);
+    (void)hipStreamSynchronize(s->ctx->stream);
+    cl_free(s);
+    return FD_OK;
+}
+
+int fd_csc_lsq_set_options(fd_csc_lsq *s, double rtol, int max_iterations)
+{
+    FD_REQUIRE(s != nullptr, FD_ERR_ARG, "lsq is NULL");
+    FD_REQUIRE(rtol >= 0.0 && rtol < 1.0, FD_ERR_ARG, "rtol = %g (0 <= rtol < 1)", rtol);
+    FD_REQUIRE(max_iterations >= 1, FD_ERR_ARG, "max_iterations = %d", max_iterations);
+    s->rtol = rtol; s->max_iterations = max_iterations;
+    return FD_OK;
+}
+
+int fd_csc_lsq_set_policy(fd_csc_lsq *s, int keep_unconverged)
+{
+    FD_REQUIRE(s != nullptr, FD_ERR_ARG, "lsq is NULL");
+    s->keep = keep_unconverged ? 1 : 0;
+    return FD_OK;
+}
+
+// the lists, for the tests and for callers that want the pattern by rows: device pointers that live as long as the consumer
+int fd_csc_lsq_row_lists(fd_csc_lsq *s, const void **row_ptr, const void **row_col, const void **row_slot, int64_t *nnz_out, int64_t *long_rows_out)
+{
+    FD_REQUIRE(s != nullptr, FD_ERR_ARG, "lsq is NULL");
+    if (row_ptr) *row_ptr = s->d_row_ptr;
+    if (row_col) *row_col = s->d_row_col;
+    if (row_slot) *row_slot = s->d_row_slot;
+    if (nnz_out) *nnz_out = s->nnz;
+    if (long_rows_out) *long_rows_out = s->nlong_r;
+    return FD_OK;
+}
+
+int fd_csc_lsq_long_columns(fd_csc_lsq *s, const void **long_cols, int64_t *count_out)
+{
+    FD_REQUIRE(s != nullptr, FD_ERR_ARG, "lsq is NULL");
+    if (long_cols) *long_cols = s->d_long_cols;
+    if (count_out) *count_out = s->nlong_c;
+    return FD_OK;
+}
+
+// q = J v on the stream: the long rows, then the tiles
+template <typename TV, int MODE>
+static void cl_product_rows(fd_csc_lsq *s, const real_t *nz, const TV *v, TV *y, double mu, bool guarded)
+{
+    hipStream_t st = s->ctx->stream;
+    const ClPat P = cl_pat(s);
+    if (s->nlong_r > 0)
+        hipLaunchKernelGGL((k_cl_long_rows<TV>), dim3((unsigned)s->nlong_r), dim3(kBlock), 0, st, P, nz, v, y, guarded ? (const int *)s->d_words : (const int *)nullptr);
+    hipLaunchKernelGGL((k_cl_rows<TV, MODE>), dim3(cl_tiles(s->M, kBlock)), dim3(kBlock), 0, st, P, nz, v, y, mu, s->d_scal, s->d_words, s->d_part);
+}
+// y = J^T v on the stream: the long columns, then the tiles
+template <typename TV, int MODE>
+static void cl_product_cols(fd_csc_lsq *s, const real_t *nz, const TV *v, TV *y, double mu, int kind)
+{
+    hipStream_t st = s->ctx->stream;
+    const ClPat P = cl_pat(s);
+    const ClVecs V = cl_vecs(s);
+    if (s->nlong_c > 0)
+        hipLaunchKernelGGL((k_cl_long_cols<TV, MODE == 1>), dim3((unsigned)s->nlong_c), dim3(kBlock), 0, st, P, nz, v, y, V.g,
+                           MODE == 2 ? (const int *)s->d_words : (const int *)nullptr);
+    hipLaunchKernelGGL((k_cl_cols<TV, MODE>), dim3(cl_tiles(s->N, kBlock)), dim3(kBlock), 0, st, P, nz, v, y, V, mu, kind, s->rtol, s->d_scal, s->d_words, s->d_part);
+}
+
+int fd_csc_lsq_matvec_async(fd_csc_lsq *s, const void *nzval, const void *v, void *y, int transpose)
+{
+    FD_REQUIRE(s && v && y && (nzval || s->nnz == 0), FD_ERR_ARG, "NULL argument");
+    FD_REQUIRE(v != y, FD_ERR_ARG, "y must not be v");
+    FD_HIP_CHECK(hipSetDevice(s->ctx->device));
+    if (transpose) cl_product_cols<real_t, 0>(s, (const real_t *)nzval, (const real_t *)v, (real_t *)y, 0.0, 0);
+    else cl_product_rows<real_t, 0>(s, (const real_t *)nzval, (const real_t *)v, (real_t *)y, 0.0, false);
+    FD_HIP_CHECK(hipGetLastError());
+    return FD_OK;
+}
+
+int fd_csc_lsq_solve_async(fd_csc_lsq *s, double mu, int damping_kind, const void *nzval, const void *b, void *y, void *r_out)
+{
+    FD_REQUIRE(s && b && y && (nzval || s->nnz == 0), FD_ERR_ARG, "NULL argument");
+    FD_REQUIRE(damping_kind == FD_CSC_LSQ_DAMP_IDENTITY || damping_kind == FD_CSC_LSQ_DAMP_COLNORM, FD_ERR_ARG,
+               "damping_kind = %d (0: identity, 1: column norms)", damping_kind);
+    FD_REQUIRE(mu >= 0.0, FD_ERR_ARG, "mu = %g (mu >= 0)", mu);      // (a NaN fails the comparison)
+    FD_HIP_CHECK(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    const int M = (int)s->M, N = (int)s->N;
+    const real_t *nz = (const real_t *)nzval;
+    const ClVecs V = cl_vecs(s);
+    const unsigned gv = cl_tiles(N, kCsVecTile), gu = cl_tiles(M > N ? M : N, kCsVecTile);
+    FD_HIP_CHECK(hipMemsetAsync(s->d_words, 0, sizeof(int) * W_NWORDS, st));
+    hipLaunchKernelGGL(k_cl_start, dim3(cl_tiles(M, kCsVecTile)), dim3(kBlock), 0, st, M, (const real_t *)b, V.r);
+    cl_product_cols<double, 1>(s, nz, V.r, V.s, mu, damping_kind);
+    // the iterations, in batches; the record of batch k is read while batch k + 1 is already enqueued (its kernels leave at once
+    // when the solve is done), so the device never waits for the host
+    int enq = 0, nb = 0;
+    bool stop = false;
+    while (!stop) {
+        const int todo = s->max_iterations - enq < s->batch ? s->max_iterations - enq : s->batch;
+        for (int it = 0; it < todo; ++it) {
+            cl_product_rows<double, 1>(s, nz, V.p, V.q, mu, true);
+            hipLaunchKernelGGL(k_cl_update, dim3(gu), dim3(kBlock), 0, st, M, N, V, (const double *)s->d_scal, (const int *)s->d_words);
+            cl_product_cols<double, 2>(s, nz, V.r, V.s, mu, damping_kind);
+            hipLaunchKernelGGL(k_cl_p, dim3(gv), dim3(kBlock), 0, st, N, damping_kind, V, s->d_scal, s->d_words, s->d_part);
+        }
+        enq += todo;
+        FD_HIP_CHECK(hipGetLastError());
+        FD_HIP_CHECK(hipMemcpyAsync(&s->h_rec[nb & 1], s->d_words, sizeof(CsRecord), hipMemcpyDeviceToHost, st));
+        FD_HIP_CHECK(hipEventRecord(s->ev[nb & 1], st));
+        if (nb >= 1) {
+            FD_HIP_CHECK(hipEventSynchronize(s->ev[(nb - 1) & 1]));
+            stop = s->h_rec[(nb - 1) & 1].done != 0;
+        }
+        ++nb;
+        if (enq >= s->max_iterations) stop = true;
+    }
+    hipLaunchKernelGGL(k_cl_final, dim3(cl_tiles(M > N ? M : N, kBlock)), dim3(kBlock), 0, st, M, N, V, (real_t *)y, (real_t *)r_out, s->d_words, s->keep);
+    FD_HIP_CHECK(hipGetLastError());
+    s->solved = true;
+    return FD_OK;
+}
+
+int fd_csc_lsq_status(fd_csc_lsq *s, int *flags_out, int64_t *iterations_out, double *grad_norm_out, double *grad0_norm_out)
+{
+    FD_REQUIRE(s != nullptr, FD_ERR_ARG, "lsq is NULL");
+    FD_HIP_CHECK(hipSetDevice(s->ctx->device));
+    FD_HIP_CHECK(hipStreamSynchronize(s->ctx->stream));
+    int w[W_NWORDS];
+    double sc[LS_NSCAL];
+    FD_HIP_CHECK(hipMemcpy(w, s->d_words, sizeof w, hipMemcpyDeviceToHost));
+    FD_HIP_CHECK(hipMemcpy(sc, s->d_scal, sizeof sc, hipMemcpyDeviceToHost));
+    if (flags_out) *flags_out = s->solved ? w[W_FINAL] : 0;
+    if (iterations_out) *iterations_out = w[W_ITERS];
+    if (grad_norm_out) *grad_norm_out = std::sqrt(sc[LS_GN2]);
+    if (grad0_norm_out) *grad0_norm_out = std::sqrt(sc[LS_G02]);
+    return FD_OK;
+}

@@ -11,3 +11,4 @@
 #include "fdjac_bandsolve.hip"
 #include "fdjac_blocksolve.hip"
 #include "fdjac_cscsolve.hip"
+#include "fdjac_csclsq.hip"

@@ -747,6 +747,46 @@ int fd_csc_solver_row_lists(fd_csc_solver *solver, const void **row_ptr, const v
 int fd_csc_solver_set_preconditioner(fd_csc_solver *solver, int kind, int block_size);
 int fd_csc_solver_block_inverses(fd_csc_solver *solver, const void **inv_dev, int64_t *nblocks, int *block_size);
 
+/* ---- the LEAST-SQUARES consumer: J v, J^T v and the damped Gauss-Newton step for a RECTANGULAR J (M x N) in SparseMatrixCSC storage ----
+ * The pattern is that of a CSC plan that holds every column: colptr (N + 1) and rowval (nnz), Int32 or Int64, base 0 or 1, on the host or
+ * on the device, exactly as fd_csc_solver_create takes them; M >= 1, N >= 1, nnz < 2^31, rows strictly ascending within a column and below
+ * M: validated on the device, a bad pattern is FD_ERR_SHAPE with a message.  nzval, v, b, y and r_out are DEVICE arrays of the library's
+ * element type; all arithmetic is Float64.  The consumer depends on no fd_plan and keeps its own lists.
+ *   fd_csc_lsq_matvec_async  y = J v (transpose = 0: v of N, y of M, row-wise) or y = J^T v (v of M, y of N, column-wise: a column of more
+ *                         than 32 entries is summed by one workgroup); y must not be v.  Defined summation orders.
+ *   fd_csc_lsq_solve_async   y = argmin ||J y - b||^2 + mu y^T W y, i.e. (J^T J + mu W) y = J^T b, mu >= 0, W = I
+ *                         (FD_CSC_LSQ_DAMP_IDENTITY, Levenberg) or W = diag(g), g_j = sum_i J_ij^2 (FD_CSC_LSQ_DAMP_COLNORM, Marquardt), by
+ *                         CGLS on the normal equations (J^T J is never formed) preconditioned by m_j = g_j + mu w_j, from y0 = 0, until
+ *                         ||J^T (b - J y) - mu W y||_2 <= rtol * ||J^T b||_2 (fd_csc_lsq_set_options: rtol, default 1e-10; max_iterations,
+ *                         default 500).  Every scalar stays on the device; the iterations are enqueued in batches and the call waits only
+ *                         for one 16-byte record per batch, one batch behind the device.  J^T b = 0: y = 0, no iteration.  r_out may be
+ *                         NULL; otherwise it receives the recurred residual b - J y (M elements).  Another damping_kind, mu < 0 or a NaN
+ *                         mu is FD_ERR_ARG.
+ *   fd_csc_lsq_status     synchronises; flags bit 0: not converged within max_iterations; bit 1: breakdown (an m_j that is zero or not finite
+ *                         -- the structurally empty column that nothing damps --, q.q + mu p^T W p zero or not finite, s.z not finite); the
+ *                         iterations of the last solve, the recurred ||J^T (b - J y) - mu W y||_2 and ||J^T b||_2.  After either failure y
+ *                         and r_out are NaN, unless fd_csc_lsq_set_policy(lsq, 1): then they are the last iterate's.
+ *   fd_csc_lsq_row_lists  DIAGNOSTIC ONLY: device pointers, owned by the consumer, to its Int32 0-based lists row_ptr (M + 1), row_col and
+ *                         row_slot (nnz) in ascending column order per row, the number of entries and of rows longer than 32 entries.
+ *   fd_csc_lsq_long_columns  DIAGNOSTIC ONLY: a device pointer to the Int32 0-based columns of more than 32 entries, ascending (NULL when
+ *                         there is none), and their number.  Any out pointer may be NULL; the layouts may change with the consumer.
+ * Everything is enqueued on the context's stream; fd_csc_lsq_create and fd_csc_lsq_status synchronise it.  Without a device
+ * fd_csc_lsq_create is FD_ERR_NODEVICE. */
+#define FD_CSC_LSQ_DAMP_IDENTITY  0
+#define FD_CSC_LSQ_DAMP_COLNORM   1
+typedef struct fd_csc_lsq fd_csc_lsq;
+int fd_csc_lsq_create(fd_ctx *ctx, int64_t M, int64_t N, const void *colptr, const void *rowval, int idx_bytes, int idx_base, int idx_kind,
+                      fd_csc_lsq **out);
+int fd_csc_lsq_destroy(fd_csc_lsq *lsq);
+int fd_csc_lsq_matvec_async(fd_csc_lsq *lsq, const void *nzval, const void *v, void *y, int transpose);
+int fd_csc_lsq_set_options(fd_csc_lsq *lsq, double rtol, int max_iterations);
+int fd_csc_lsq_set_policy(fd_csc_lsq *lsq, int keep_unconverged);
+int fd_csc_lsq_solve_async(fd_csc_lsq *lsq, double mu, int damping_kind, const void *nzval, const void *b, void *y, void *r_out);
+int fd_csc_lsq_status(fd_csc_lsq *lsq, int *flags_out, int64_t *iterations_out, double *grad_norm_out, double *grad0_norm_out);
+int fd_csc_lsq_row_lists(fd_csc_lsq *lsq, const void **row_ptr, const void **row_col, const void **row_slot, int64_t *nnz_out,
+                         int64_t *long_rows_out);
+int fd_csc_lsq_long_columns(fd_csc_lsq *lsq, const void **long_cols, int64_t *count_out);
+
 /* ---- the consumer for block-banded Jacobians: (alpha*I + beta*J) y = b for a BLOCK-TRIDIAGONAL J (round 6) ---------------------------
  * J = nblk x nblk dense blocks of block_size x block_size (<= 32), block bandwidths (1, 1), in BlockBandedMatrix data as a
  * fd_plan_create_blockbanded plan of uniform block sizes fills it (block column J's in-band blocks stacked into one column-major
@@ -961,6 +1001,18 @@ int fd32_csc_solver_row_lists(fd32_csc_solver *solver, const void **row_ptr, con
                             int64_t *nnz_out, int64_t *long_rows_out);
 int fd32_csc_solver_set_preconditioner(fd32_csc_solver *solver, int kind, int block_size);
 int fd32_csc_solver_block_inverses(fd32_csc_solver *solver, const void **inv_dev, int64_t *nblocks, int *block_size);
+typedef struct fd32_csc_lsq fd32_csc_lsq;
+int fd32_csc_lsq_create(fd_ctx *ctx, int64_t M, int64_t N, const void *colptr, const void *rowval, int idx_bytes, int idx_base, int idx_kind,
+                      fd32_csc_lsq **out);
+int fd32_csc_lsq_destroy(fd32_csc_lsq *lsq);
+int fd32_csc_lsq_matvec_async(fd32_csc_lsq *lsq, const void *nzval, const void *v, void *y, int transpose);
+int fd32_csc_lsq_set_options(fd32_csc_lsq *lsq, double rtol, int max_iterations);
+int fd32_csc_lsq_set_policy(fd32_csc_lsq *lsq, int keep_unconverged);
+int fd32_csc_lsq_solve_async(fd32_csc_lsq *lsq, double mu, int damping_kind, const void *nzval, const void *b, void *y, void *r_out);
+int fd32_csc_lsq_status(fd32_csc_lsq *lsq, int *flags_out, int64_t *iterations_out, double *grad_norm_out, double *grad0_norm_out);
+int fd32_csc_lsq_row_lists(fd32_csc_lsq *lsq, const void **row_ptr, const void **row_col, const void **row_slot, int64_t *nnz_out,
+                         int64_t *long_rows_out);
+int fd32_csc_lsq_long_columns(fd32_csc_lsq *lsq, const void **long_cols, int64_t *count_out);
 typedef struct fd32_tridiag_solver fd32_tridiag_solver;
 int fd32_tridiag_solver_create(fd_ctx *ctx, int64_t N, int64_t row_begin, int64_t row_end, int layout,
                                fd32_tridiag_solver **out);

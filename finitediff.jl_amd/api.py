@@ -584,25 +584,26 @@ class BandedSolver:
         return v.value
 
 
-class CscSolver:
-    """fd_csc_solver: the sparse consumer.  For a square J in ``SparseMatrixCSC`` storage -- the nzval a CSC plan has just written, left
-    on the device -- ``matvec`` enqueues y = (alpha*I + beta*J) v (or its transpose) and ``solve`` enqueues y = (alpha*I + beta*J)^-1 b by
-    BiCGStab whose scalars never leave the device, preconditioned by the diagonal or (``set_preconditioner``) by the inverses of the
-    diagonal blocks.  ``pattern`` is a ``SparseMatrixCSC`` / ``DevicePatternCSC`` or
-    ``(colptr, rowval, N)`` with numpy arrays or CUDA tensors of int32 / int64 (``idx_base``-based).  A solve that does not converge
-    within ``max_iterations`` (``status()`` flags bit 0) or breaks down (bit 1) fills y with NaN unless ``set_policy(True)``."""
+class _CscConsumer:
+    """What CscSolver and CscLeastSquares share: the marshalling of a pattern's indices and the calls that differ only in the C prefix."""
+    _prefix = None      # "fd_csc_solver" / "fd_csc_lsq": <prefix>_create, _destroy, _set_options, _set_policy
+    _noun = None        # in "the <noun> takes device arrays"
 
-    def __init__(self, pattern, ctx=None, dtype=np.float64, idx_base=1):
+    def _create(self, pattern, ctx, dtype, idx_base, square):
+        """<prefix>_create on the pattern's indices; a square consumer's pattern tuple and C call carry N alone.  Returns (M, N)."""
         self.ctx = ctx or Context.default()
         self.dtype = np.dtype(dtype)
         self.Lt = _l.typed(self.ctx.L, self.dtype)
         if isinstance(pattern, (SparseMatrixCSC, DevicePatternCSC)):
-            if pattern.m != pattern.n:
+            if square and pattern.m != pattern.n:
                 raise ValueError("the sparse solver takes a square pattern")
-            colptr, rowval, N = pattern.colptr, pattern.rowval, pattern.n
+            colptr, rowval, M, N = pattern.colptr, pattern.rowval, pattern.m, pattern.n
             idx_base = getattr(pattern, "idx_base", 1)
-        else:
+        elif square:
             colptr, rowval, N = pattern
+            M = N
+        else:
+            colptr, rowval, M, N = pattern
         dev = _is_torch(colptr) and colptr.is_cuda
         if dev:
             if not (_is_torch(rowval) and rowval.is_cuda) or rowval.dtype != colptr.dtype or colptr.element_size() not in (4, 8):
@@ -618,18 +619,49 @@ class CscSolver:
         if colptr.shape[0] != int(N) + 1:
             raise ValueError("colptr must hold N + 1 entries")
         h = C.c_void_p()
-        _l.check(self.Lt.fd_csc_solver_create(self.ctx.handle, int(N), pc, pr or None, ib, int(idx_base), _l.DEVICE if dev else _l.HOST, C.byref(h)))
-        self.handle, self.N = h, int(N)
-        self._fin = weakref.finalize(self, self.Lt.fd_csc_solver_destroy, h)
+        dims = (int(N),) if square else (int(M), int(N))
+        _l.check(getattr(self.Lt, self._prefix + "_create")(self.ctx.handle, *dims, pc, pr or None, ib, int(idx_base), _l.DEVICE if dev else _l.HOST, C.byref(h)))
+        self.handle = h
+        self._fin = weakref.finalize(self, getattr(self.Lt, self._prefix + "_destroy"), h)
+        return int(M), int(N)
 
     def _dev(self, a, what):
         p, k, _keep = _ptr(a, what, self.dtype)
         if k != _l.DEVICE:
-            raise ValueError("the solver takes device arrays")
+            raise ValueError("the %s takes device arrays" % self._noun)
         return p
 
     def _vals(self, J):
         return self._dev(J.nzval if isinstance(J, (SparseMatrixCSC, DevicePatternCSC)) else J, "J")
+
+    def set_options(self, rtol=1e-10, max_iterations=500):
+        _l.check(getattr(self.Lt, self._prefix + "_set_options")(self.handle, float(rtol), int(max_iterations)))
+
+    def set_policy(self, keep_unconverged):
+        _l.check(getattr(self.Lt, self._prefix + "_set_policy")(self.handle, 1 if keep_unconverged else 0))
+
+    def _ints(self, p, n):
+        """n Int32 of the consumer's at device address p as a CUDA tensor (a copy)."""
+        import torch
+        if n == 0:
+            return torch.empty(0, dtype=torch.int32, device="cuda:%d" % self.ctx.device)
+        view = _DevView(p, n, False)
+        view.__cuda_array_interface__["typestr"] = "<i4"
+        return torch.as_tensor(view, device="cuda:%d" % self.ctx.device).clone()
+
+
+class CscSolver(_CscConsumer):
+    """fd_csc_solver: the sparse consumer.  For a square J in ``SparseMatrixCSC`` storage -- the nzval a CSC plan has just written, left
+    on the device -- ``matvec`` enqueues y = (alpha*I + beta*J) v (or its transpose) and ``solve`` enqueues y = (alpha*I + beta*J)^-1 b by
+    BiCGStab whose scalars never leave the device, preconditioned by the diagonal or (``set_preconditioner``) by the inverses of the
+    diagonal blocks.  ``pattern`` is a ``SparseMatrixCSC`` / ``DevicePatternCSC`` or
+    ``(colptr, rowval, N)`` with numpy arrays or CUDA tensors of int32 / int64 (``idx_base``-based).  A solve that does not converge
+    within ``max_iterations`` (``status()`` flags bit 0) or breaks down (bit 1) fills y with NaN unless ``set_policy(True)``."""
+
+    _prefix, _noun = "fd_csc_solver", "solver"
+
+    def __init__(self, pattern, ctx=None, dtype=np.float64, idx_base=1):
+        _M, self.N = self._create(pattern, ctx, dtype, idx_base, square=True)
 
     def matvec(self, J, v, y, alpha=0.0, beta=1.0, transpose=False):
         """Enqueue y = (alpha*I + beta*J) v, or its transpose, on the context's stream (fd_csc_matvec_async)."""
@@ -639,12 +671,6 @@ class CscSolver:
     def solve(self, J, b, y, alpha=1.0, beta=-1.0):
         """Enqueue y = (alpha*I + beta*J)^-1 b on the context's stream (fd_csc_solve_async)."""
         _l.check(self.Lt.fd_csc_solve_async(self.handle, float(alpha), float(beta), self._vals(J), self._dev(b, "b"), self._dev(y, "y")))
-
-    def set_options(self, rtol=1e-10, max_iterations=500):
-        _l.check(self.Lt.fd_csc_solver_set_options(self.handle, float(rtol), int(max_iterations)))
-
-    def set_policy(self, keep_unconverged):
-        _l.check(self.Lt.fd_csc_solver_set_policy(self.handle, 1 if keep_unconverged else 0))
 
     def status(self):
         """Synchronises.  {"flags": bit 0 not converged | bit 1 breakdown, "iterations", "resid": ||r||_2 of the recurrence, "bnorm"}."""
@@ -674,22 +700,13 @@ class CscSolver:
 
     def row_lists(self):
         """The solver's lists as int32 CUDA tensors (copies): row_ptr, row_col, row_slot, diag_slot; and the number of long rows."""
-        import torch
         ps = [C.c_void_p() for _ in range(4)]
         nnz, nlong = C.c_int64(), C.c_int64()
         _l.check(self.Lt.fd_csc_solver_row_lists(self.handle, *[C.byref(p) for p in ps], C.byref(nnz), C.byref(nlong)))
-        out = []
-        for p, n in zip(ps, (self.N + 1, nnz.value, nnz.value, self.N)):
-            if n == 0:
-                out.append(torch.empty(0, dtype=torch.int32, device="cuda:%d" % self.ctx.device))
-                continue
-            view = _DevView(p.value, n, False)
-            view.__cuda_array_interface__["typestr"] = "<i4"
-            out.append(torch.as_tensor(view, device="cuda:%d" % self.ctx.device).clone())
-        return out + [nlong.value]
+        return [self._ints(p.value, n) for p, n in zip(ps, (self.N + 1, nnz.value, nnz.value, self.N))] + [nlong.value]
 
 
-class CscLeastSquares:
+class CscLeastSquares(_CscConsumer):
     """fd_csc_lsq: the least-squares consumer.  For a rectangular J (M x N) in ``SparseMatrixCSC`` storage -- the nzval a CSC plan has just
     written, left on the device -- ``matvec`` enqueues y = J v or y = J^T v and ``solve`` enqueues the damped Gauss-Newton step
     y = argmin ||J y - b||^2 + mu y^T W y, W = I (``damping="identity"``, Levenberg) or diag(sum_i J_ij^2) (``"colnorm"``, Marquardt), by
@@ -700,42 +717,10 @@ class CscLeastSquares:
 
     DAMPING = {"identity": 0, "colnorm": 1}
 
+    _prefix, _noun = "fd_csc_lsq", "consumer"
+
     def __init__(self, pattern, ctx=None, dtype=np.float64, idx_base=1):
-        self.ctx = ctx or Context.default()
-        self.dtype = np.dtype(dtype)
-        self.Lt = _l.typed(self.ctx.L, self.dtype)
-        if isinstance(pattern, (SparseMatrixCSC, DevicePatternCSC)):
-            colptr, rowval, M, N = pattern.colptr, pattern.rowval, pattern.m, pattern.n
-            idx_base = getattr(pattern, "idx_base", 1)
-        else:
-            colptr, rowval, M, N = pattern
-        dev = _is_torch(colptr) and colptr.is_cuda
-        if dev:
-            if not (_is_torch(rowval) and rowval.is_cuda) or rowval.dtype != colptr.dtype or colptr.element_size() not in (4, 8):
-                raise TypeError("colptr and rowval must be CUDA tensors of one integer type (int32 or int64)")
-            colptr, rowval = colptr.contiguous(), rowval.contiguous()
-            ib, pc, pr = colptr.element_size(), colptr.data_ptr(), rowval.data_ptr()
-        else:
-            colptr = np.ascontiguousarray(colptr.numpy() if _is_torch(colptr) else colptr)
-            rowval = np.ascontiguousarray(rowval.numpy() if _is_torch(rowval) else rowval)
-            if colptr.dtype not in (np.int32, np.int64) or rowval.dtype != colptr.dtype:
-                raise TypeError("colptr and rowval must be int32 or int64 arrays of one type")
-            ib, pc, pr = colptr.dtype.itemsize, colptr.ctypes.data, rowval.ctypes.data
-        if colptr.shape[0] != int(N) + 1:
-            raise ValueError("colptr must hold N + 1 entries")
-        h = C.c_void_p()
-        _l.check(self.Lt.fd_csc_lsq_create(self.ctx.handle, int(M), int(N), pc, pr or None, ib, int(idx_base), _l.DEVICE if dev else _l.HOST, C.byref(h)))
-        self.handle, self.M, self.N = h, int(M), int(N)
-        self._fin = weakref.finalize(self, self.Lt.fd_csc_lsq_destroy, h)
-
-    def _dev(self, a, what):
-        p, k, _keep = _ptr(a, what, self.dtype)
-        if k != _l.DEVICE:
-            raise ValueError("the consumer takes device arrays")
-        return p
-
-    def _vals(self, J):
-        return self._dev(J.nzval if isinstance(J, (SparseMatrixCSC, DevicePatternCSC)) else J, "J")
+        self.M, self.N = self._create(pattern, ctx, dtype, idx_base, square=False)
 
     def matvec(self, J, v, y, transpose=False):
         """Enqueue y = J v (v of N, y of M) or, transposed, y = J^T v (v of M, y of N) on the context's stream (fd_csc_lsq_matvec_async)."""
@@ -747,26 +732,12 @@ class CscLeastSquares:
         _l.check(self.Lt.fd_csc_lsq_solve_async(self.handle, float(mu), int(kind), self._vals(J), self._dev(b, "b"), self._dev(y, "y"),
                                                 None if r_out is None else self._dev(r_out, "r_out")))
 
-    def set_options(self, rtol=1e-10, max_iterations=500):
-        _l.check(self.Lt.fd_csc_lsq_set_options(self.handle, float(rtol), int(max_iterations)))
-
-    def set_policy(self, keep_unconverged):
-        _l.check(self.Lt.fd_csc_lsq_set_policy(self.handle, 1 if keep_unconverged else 0))
-
     def status(self):
         """Synchronises.  {"flags": bit 0 not converged | bit 1 breakdown, "iterations", "grad": the recurred
         ||J^T (b - J y) - mu W y||_2, "grad0": ||J^T b||_2}."""
         f, it, g, g0 = C.c_int(), C.c_int64(), C.c_double(), C.c_double()
         _l.check(self.Lt.fd_csc_lsq_status(self.handle, C.byref(f), C.byref(it), C.byref(g), C.byref(g0)))
         return {"flags": f.value, "iterations": it.value, "grad": g.value, "grad0": g0.value}
-
-    def _ints(self, p, n):
-        import torch
-        if n == 0:
-            return torch.empty(0, dtype=torch.int32, device="cuda:%d" % self.ctx.device)
-        view = _DevView(p, n, False)
-        view.__cuda_array_interface__["typestr"] = "<i4"
-        return torch.as_tensor(view, device="cuda:%d" % self.ctx.device).clone()
 
     def row_lists(self):
         """The consumer's lists as int32 CUDA tensors (copies): row_ptr, row_col, row_slot; and the number of long rows."""

@@ -1,17 +1,43 @@
-// Device helpers and create kernels shared by the consumers on SparseMatrixCSC storage (fdjac_cscsolve.hip, fdjac_csclsq.hip): index
-// loads, the integer scan, the fill / sort passes that turn a column pattern into lists by rows, the lane order of a tile, and the
-// ordered sums (block_sum, the ticket that lets the last-arriving workgroup finish a dot).  Kernels are static: every translation
-// unit that includes this header has its own copies.
+// Shared by the consumers on SparseMatrixCSC storage (fdjac_cscsolve.hip, fdjac_csclsq.hip).  CREATE lives in fdjac_csc_pattern.hip: it
+// touches indices only, so it is compiled once, with the Float64 build, and both element builds call it through the declarations below
+// (CscLists, csc_lists_build, csc_lists_free).  Here: the constants, the device helpers of the iteration kernels (index loads, the ordered
+// sums block_sum and the ticket that lets the last-arriving workgroup finish a dot, the breakdown store) and CscSolveState, the host
+// side of a solve that both consumers share: its device words and scalars, the batch loop and the status read-back.
 #pragma once
 #include "fdjac_internal.h"
 #include "fdjac_device.h"
+
+// ---- the pattern, built once (fdjac_csc_pattern.hip) ---------------------------------------------------------------------------------
+// No real_t in any of it: these names stay in the Float64 build's namespace, whatever fdjac_internal.h renames for the Float32 one.
+#pragma push_macro("fdjac")
+#undef fdjac
+namespace fdjac {
+enum { CSC_WANT_DIAG = 1, CSC_WANT_COLUMNS = 2 };
+struct CscLists {                      // device arrays, 0-based Int32
+    int64_t M = 0, N = 0, nnz = 0;
+    int nlong_r = 0, nlong_c = 0, reach = 0;     // rows / columns of more than kCsLong entries; max |row - column| (with diag)
+    int *colptr = nullptr, *rowval = nullptr;    // the pattern by columns, validated
+    int *row_ptr = nullptr, *row_col = nullptr, *row_slot = nullptr;      // ... by rows: every row's columns ascending, and their slots
+    int *row_order = nullptr, *long_rows = nullptr;      // the lanes' rows per tile of 256; the long rows in the order an atomic cursor gave
+    int *diag = nullptr;                                 // CSC_WANT_DIAG (M == N): the slot of (j, j), -1: not stored
+    int *col_order = nullptr, *long_cols = nullptr;      // CSC_WANT_COLUMNS: the lanes' columns per tile; the long columns, ascending
+};
+// Checks the arguments (`who` opens every message), validates the pattern and builds the lists on ctx's stream; three host
+// synchronisations.  After a failure nothing is left allocated.
+int csc_lists_build(fd_ctx *ctx, const char *who, int64_t M, int64_t N, const void *colptr, const void *rowval, int idx_bytes, int idx_base,
+                    int idx_kind, unsigned want, CscLists *out);
+void csc_lists_free(CscLists *L);      // (the caller has synchronised the stream; a half-built object is fine)
+}
+#ifdef FDJAC_F32
+namespace fdjac32 { using fdjac::CSC_WANT_DIAG; using fdjac::CSC_WANT_COLUMNS; using fdjac::CscLists; using fdjac::csc_lists_build; using fdjac::csc_lists_free; }
+#endif
+#pragma pop_macro("fdjac")
 
 namespace fdjac {
 
 constexpr int kCsLong = 32;            // rows of more entries than this are summed by a workgroup each
 constexpr int kCsVecTile = 1024;       // elements per workgroup of the vector kernels
 constexpr int kCsBatchDefault = 8;     // iterations enqueued per record read back
-enum { CS_BAD_COLPTR = 1, CS_BAD_ROW = 2, CS_BAD_ORDER = 4 };
 // words of a solve, in device memory (the first four are the record the host reads per batch)
 enum { W_DONE = 0, W_EARLY, W_FLAGS, W_ITERS, W_TICKET, W_FINAL, W_NWORDS = 8 };
 
@@ -23,158 +49,10 @@ __device__ __forceinline__ int64_t cs_load(const void *p, int bytes, int64_t i)
 }
 __device__ __forceinline__ bool cs_bad_pivot(double x) { return !(fabs(x) > 0.0 && fabs(x) < __builtin_huge_val()); }
 __device__ __forceinline__ int cs_word(const int *w, int i) { return __hip_atomic_load(w + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// ---- create ------------------------------------------------------------------------------------------------------------------------
-static __global__ void __launch_bounds__(kBlock) k_cs_colptr(const void *__restrict__ colptr, int ib, int base, int64_t N, int64_t nnz,
-                                                      int *__restrict__ cptr, unsigned *err)
+__device__ __forceinline__ void cs_breakdown(int *words)      // flag bit 1, and the solve is over
 {
-    bool bad = false;
-    for (int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x; j <= N; j += (int64_t)gridDim.x * kBlock) {
-        const int64_t a = cs_load(colptr, ib, j) - base;
-        if (j < N) bad = bad || a > cs_load(colptr, ib, j + 1) - base;
-        bad = bad || a < 0 || a > nnz || (j == 0 && a != 0) || (j == N && a != nnz);
-        cptr[j] = (int)(a < 0 ? 0 : (a > nnz ? nnz : a));
-    }
-    if (bad) atomicOr(err, (unsigned)CS_BAD_COLPTR);
-}
-
-constexpr int kCsScanPer = 8, kCsScanTile = kBlock * kCsScanPer;
-__device__ __forceinline__ int cs_block_exscan(int v, int *s_w, int &total)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += t;
-    }
-    __syncthreads();
-    if (lane == 63) s_w[w] = inc;
-    __syncthreads();
-    int before = 0;
-    total = 0;
-#pragma unroll
-    for (int i = 0; i < kBlock / 64; ++i) {
-        if (i < w) before += s_w[i];
-        total += s_w[i];
-    }
-    return before + inc - v;
-}
-static __global__ void __launch_bounds__(kBlock) k_cs_scan_sums(const int *__restrict__ in, int64_t n, int *__restrict__ bsum)
-{
-    __shared__ int s_w[kBlock / 64];
-    const int64_t i0 = (int64_t)blockIdx.x * kCsScanTile + (int64_t)threadIdx.x * kCsScanPer;
-    int s = 0;
-#pragma unroll
-    for (int k = 0; k < kCsScanPer; ++k) s += i0 + k < n ? in[i0 + k] : 0;
-    int total;
-    (void)cs_block_exscan(s, s_w, total);
-    if (threadIdx.x == 0) bsum[blockIdx.x] = total;
-}
-static __global__ void __launch_bounds__(kBlock) k_cs_scan_top(int *__restrict__ bsum, int64_t nb)      // in place; bsum[nb] = the total
-{
-    __shared__ int s_w[kBlock / 64];
-    int carry = 0;
-    for (int64_t b0 = 0; b0 < nb; b0 += kBlock) {
-        const int64_t i = b0 + threadIdx.x;
-        const int v = i < nb ? bsum[i] : 0;
-        int total;
-        const int ex = cs_block_exscan(v, s_w, total);
-        if (i < nb) bsum[i] = carry + ex;
-        carry += total;
-    }
-    if (threadIdx.x == 0) bsum[nb] = carry;
-}
-static __global__ void __launch_bounds__(kBlock) k_cs_scan_apply(const int *__restrict__ in, int64_t n, const int *__restrict__ bsum, int64_t nb,
-                                                          int *__restrict__ out)
-{
-    __shared__ int s_w[kBlock / 64];
-    const int64_t i0 = (int64_t)blockIdx.x * kCsScanTile + (int64_t)threadIdx.x * kCsScanPer;
-    int v[kCsScanPer], s = 0;
-#pragma unroll
-    for (int k = 0; k < kCsScanPer; ++k) {
-        v[k] = i0 + k < n ? in[i0 + k] : 0;
-        s += v[k];
-    }
-    int total;
-    int run = bsum[blockIdx.x] + cs_block_exscan(s, s_w, total);
-#pragma unroll
-    for (int k = 0; k < kCsScanPer; ++k) {
-        if (i0 + k < n) out[i0 + k] = run;
-        run += v[k];
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) out[n] = bsum[nb];
-}
-
-// the fill pass: slot q joins its row at the position an atomic cursor hands out (any order: the segments are sorted next)
-static __global__ void __launch_bounds__(kBlock) k_cs_fill(const int *__restrict__ erow, int64_t nnz, const int *__restrict__ rptr,
-                                                    int *__restrict__ cursor, int *__restrict__ rslot)
-{
-    for (int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x; q < nnz; q += (int64_t)gridDim.x * kBlock) {
-        const int r = erow[q];
-        rslot[rptr[r] + atomicAdd(&cursor[r], 1)] = (int)q;
-    }
-}
-// short rows: one lane ranks every slot of its row among the row's (slots are distinct; at most kCsLong^2 compares, no private array),
-// parks the sorted slots in the row's segment of rcol, then writes slots and columns; long rows are counted
-static __global__ void __launch_bounds__(kBlock) k_cs_sort_short(const int *__restrict__ rptr, int64_t N, int *rslot, const int *__restrict__ ecol,
-                                                          int *rcol, int *nlong)
-{
-    const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (r >= N) return;
-    const int a = rptr[r], n = rptr[r + 1] - a;
-    if (n > kCsLong) { atomicAdd(nlong, 1); return; }
-    for (int k = 0; k < n; ++k) {
-        const int v = rslot[a + k];
-        int rank = 0;
-        for (int i = 0; i < n; ++i) rank += rslot[a + i] < v ? 1 : 0;
-        rcol[a + rank] = v;
-    }
-    for (int k = 0; k < n; ++k) {
-        const int v = rcol[a + k];
-        rslot[a + k] = v;
-        rcol[a + k] = ecol[v];
-    }
-}
-static __global__ void __launch_bounds__(kBlock) k_cs_list_long(const int *__restrict__ rptr, int64_t N, int *__restrict__ list, int *cnt)
-{
-    const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (r < N && rptr[r + 1] - rptr[r] > kCsLong) list[atomicAdd(cnt, 1)] = (int)r;
-}
-// long rows: one workgroup per row ranks every slot among the row's (slots are distinct) into tmp, then copies back
-static __global__ void __launch_bounds__(kBlock) k_cs_sort_long(const int *__restrict__ rptr, const int *__restrict__ list, int *__restrict__ rslot,
-                                                         int *__restrict__ tmp, const int *__restrict__ ecol, int *__restrict__ rcol)
-{
-    const int r = list[blockIdx.x], a = rptr[r], n = rptr[r + 1] - a;
-    for (int k = threadIdx.x; k < n; k += kBlock) {
-        const int v = rslot[a + k];
-        int rank = 0;
-        for (int i = 0; i < n; ++i) rank += rslot[a + i] < v ? 1 : 0;
-        tmp[a + rank] = v;
-    }
-    __threadfence_block();
-    __syncthreads();
-    for (int k = threadIdx.x; k < n; k += kBlock) {
-        const int v = tmp[a + k];
-        rslot[a + k] = v;
-        rcol[a + k] = ecol[v];
-    }
-}
-// the lanes' rows: within every tile of 256 rows, descending length (capped at kCsLong + 1), ties by ascending row
-static __global__ void __launch_bounds__(kBlock) k_cs_order(const int *__restrict__ rptr, int64_t N, int *__restrict__ order)
-{
-    __shared__ int s_len[kBlock];
-    const int64_t r0 = (int64_t)blockIdx.x * kBlock, r = r0 + threadIdx.x;
-    int len = -1;
-    if (r < N) { len = rptr[r + 1] - rptr[r]; if (len > kCsLong) len = kCsLong + 1; }
-    s_len[threadIdx.x] = len;
-    __syncthreads();
-    int rank = 0;
-    for (int u = 0; u < kBlock; ++u) {
-        const int lu = s_len[u];
-        rank += (lu > len || (lu == len && u < (int)threadIdx.x)) ? 1 : 0;
-    }
-    order[r0 + rank] = r < N ? (int)r : -1;
+    atomicOr(words + W_FLAGS, 2);
+    __hip_atomic_store(words + W_DONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // ---- sums ----------------------------------------------------------------------------------------------------------------------------
@@ -216,16 +94,91 @@ __device__ __forceinline__ bool cs_finish(const double (&mine)[ND], double *part
     return true;
 }
 
-}  // namespace fdjac
-
-static inline unsigned csc_grid(int64_t n, int per) { const int64_t g = (n + per - 1) / per; return (unsigned)(g < 1 ? 1 : (g > 65536 ? 65536 : g)); }
-
-static inline int csc_exscan(hipStream_t st, const int *in, int64_t n, int *out, int *bsum)
+// ---- the host side of a solve ------------------------------------------------------------------------------------------------------
+// a HIP call of a consumer's create: the failure is reported under the consumer's name, out of memory as FD_ERR_NOMEM
+inline int csc_hip_failed(const char *who, const char *what, hipError_t e)
 {
-    const int64_t nb = (n + fdjac::kCsScanTile - 1) / fdjac::kCsScanTile;
-    hipLaunchKernelGGL(fdjac::k_cs_scan_sums, dim3((unsigned)nb), dim3(fdjac::kBlock), 0, st, in, n, bsum);
-    hipLaunchKernelGGL(fdjac::k_cs_scan_top, dim3(1), dim3(fdjac::kBlock), 0, st, bsum, nb);
-    hipLaunchKernelGGL(fdjac::k_cs_scan_apply, dim3((unsigned)nb), dim3(fdjac::kBlock), 0, st, in, n, (const int *)bsum, nb, out);
-    FD_HIP_CHECK(hipGetLastError());
-    return FD_OK;
+    set_error("%s: %s failed: %s", who, what, hipGetErrorString(e));
+    return e == hipErrorOutOfMemory ? FD_ERR_NOMEM : FD_ERR_HIP;
 }
+#define CSC_TRY(who, expr)                                                    \
+    do {                                                                      \
+        hipError_t _e = (expr);                                               \
+        if (_e != hipSuccess) return ::fdjac::csc_hip_failed(who, #expr, _e); \
+    } while (0)
+
+struct CscSolveState {
+    double *d_part = nullptr;          // the tiles' sums of the dots
+    double *d_scal = nullptr;          // the consumer's scalars
+    int *d_words = nullptr;            // W_*
+    CsRecord *h_rec = nullptr;         // pinned: one record per batch in flight (two)
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    int nscal = 0, batch = kCsBatchDefault;
+    double rtol = 1e-10;
+    int max_iterations = 500, keep = 0;
+    bool solved = false;
+
+    int create(const char *who, hipStream_t st, int nscal_, int64_t npart)
+    {
+        nscal = nscal_;
+        if (const char *v = test_switch("FDJAC_CSC_BATCH")) { const int b = atoi(v); if (b >= 1 && b <= 64) batch = b; }
+        CSC_TRY(who, hipMalloc((void **)&d_part, sizeof(double) * (size_t)npart));
+        CSC_TRY(who, hipMalloc((void **)&d_scal, sizeof(double) * (size_t)nscal));
+        CSC_TRY(who, hipMalloc((void **)&d_words, sizeof(int) * W_NWORDS));
+        CSC_TRY(who, hipHostMalloc((void **)&h_rec, sizeof(CsRecord) * 2, hipHostMallocDefault));
+        CSC_TRY(who, hipEventCreateWithFlags(&ev[0], hipEventDisableTiming));
+        CSC_TRY(who, hipEventCreateWithFlags(&ev[1], hipEventDisableTiming));
+        CSC_TRY(who, hipMemsetAsync(d_scal, 0, sizeof(double) * (size_t)nscal, st));
+        CSC_TRY(who, hipMemsetAsync(d_words, 0, sizeof(int) * W_NWORDS, st));
+        CSC_TRY(who, hipStreamSynchronize(st));
+        return FD_OK;
+    }
+    void free()      // (the caller has synchronised the stream; a half-built object is fine)
+    {
+        void *ptrs[] = {d_part, d_scal, d_words};
+        for (void *p : ptrs) if (p) (void)hipFree(p);
+        if (h_rec) (void)hipHostFree(h_rec);
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    }
+    int set_options(double rtol_, int max_iterations_)
+    {
+        FD_REQUIRE(rtol_ >= 0.0 && rtol_ < 1.0, FD_ERR_ARG, "rtol = %g (0 <= rtol < 1)", rtol_);
+        FD_REQUIRE(max_iterations_ >= 1, FD_ERR_ARG, "max_iterations = %d", max_iterations_);
+        rtol = rtol_; max_iterations = max_iterations_;
+        return FD_OK;
+    }
+    // The iterations, in batches: enqueue_iteration() launches one iteration's kernels on st.  The record of batch k is read while batch
+    // k + 1 is already enqueued (its kernels leave at once when the solve is done), so the device never waits for the host.
+    template <class F> int run(hipStream_t st, F enqueue_iteration)
+    {
+        int enq = 0, nb = 0;
+        bool stop = false;
+        while (!stop) {
+            const int todo = max_iterations - enq < batch ? max_iterations - enq : batch;
+            for (int it = 0; it < todo; ++it) enqueue_iteration();
+            enq += todo;
+            FD_HIP_CHECK(hipGetLastError());
+            FD_HIP_CHECK(hipMemcpyAsync(&h_rec[nb & 1], d_words, sizeof(CsRecord), hipMemcpyDeviceToHost, st));
+            FD_HIP_CHECK(hipEventRecord(ev[nb & 1], st));
+            if (nb >= 1) {
+                FD_HIP_CHECK(hipEventSynchronize(ev[(nb - 1) & 1]));
+                stop = h_rec[(nb - 1) & 1].done != 0;
+            }
+            ++nb;
+            if (enq >= max_iterations) stop = true;
+        }
+        return FD_OK;
+    }
+    // synchronises; w[W_FINAL] is replaced by 0 before the first solve
+    int read_status(const fd_ctx *ctx, int (&w)[W_NWORDS], double *scalars)
+    {
+        FD_HIP_CHECK(hipSetDevice(ctx->device));
+        FD_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        FD_HIP_CHECK(hipMemcpy(w, d_words, sizeof w, hipMemcpyDeviceToHost));
+        FD_HIP_CHECK(hipMemcpy(scalars, d_scal, sizeof(double) * (size_t)nscal, hipMemcpyDeviceToHost));
+        if (!solved) w[W_FINAL] = 0;
+        return FD_OK;
+    }
+};
+
+}  // namespace fdjac

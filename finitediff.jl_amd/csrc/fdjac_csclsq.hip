@@ -3,9 +3,7 @@
 // by CGLS on the normal equations (J^T J is never formed) preconditioned by m_j = g_j + mu w_j.  DESIGN.md 4.10 has the contract;
 // tests/csc_lsq_model.py restates every order below in numpy and the GPU tests compare bits.
 //
-// CREATE (device): as the square consumer's (fdjac_csc_common.h), rows against M and colptr against N + 1: the pattern by rows (sorted by
-// slot = by column), the rows of more than kCsLong entries, a lane order per tile of 256 rows; and the same for the columns on colptr
-// itself: the columns of more than kCsLong entries in ASCENDING order (flags, a scan, a scatter) and a lane order per tile of 256 columns.
+// CREATE is the shared builder's (fdjac_csc_pattern.hip), with the columns' lane order and the long columns in ascending order.
 //
 // ORDERS.  Row r of at most kCsLong entries: acc = 0; acc += nzval[slot_k] * v[col_k], k ascending (ascending column); a longer row by
 // one workgroup: thread t adds entries t, t + 256, ... in that order, then block_sum().  Column j of at most kCsLong entries: one lane, storage
@@ -28,7 +26,6 @@
 #include "fdjac_device.h"
 #include "fdjac_csc_common.h"
 #include <cmath>
-#include <cstring>
 #include <new>
 
 namespace fdjac {
@@ -43,45 +40,6 @@ struct ClPat {                         // the pattern as the kernels see it
 struct ClVecs { double *r, *q, *y, *p, *s, *z, *m, *g; };      // r, q: M doubles; the others: N
 
 __device__ __forceinline__ bool cl_not_finite(double x) { return !(fabs(x) < __builtin_huge_val()); }
-__device__ __forceinline__ void cl_breakdown(int *words)
-{
-    atomicOr(words + W_FLAGS, 2);
-    __hip_atomic_store(words + W_DONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// ---- create ------------------------------------------------------------------------------------------------------------------------
-// one lane per entry: its row (validated against M, 0-based), its column (binary search in the monotone cptr), rows strictly ascending
-// within the column, the row's count
-__global__ void __launch_bounds__(kBlock) k_cl_entries(const void *__restrict__ rowval, int ib, int base, const int *__restrict__ cptr,
-                                                       int64_t M, int64_t N, int64_t nnz, int *__restrict__ erow, int *__restrict__ ecol,
-                                                       int *__restrict__ rcnt, unsigned *err)
-{
-    for (int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x; q < nnz; q += (int64_t)gridDim.x * kBlock) {
-        const int64_t r = cs_load(rowval, ib, q) - base;
-        const bool ok = r >= 0 && r < M;
-        int64_t lo = 0, hi = N;      // cptr[lo] <= q < cptr[hi]
-        while (hi - lo > 1) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (cptr[mid] <= q) lo = mid; else hi = mid;
-        }
-        erow[q] = ok ? (int)r : 0;
-        ecol[q] = (int)lo;
-        if (!ok) { atomicOr(err, (unsigned)CS_BAD_ROW); continue; }
-        if (q > cptr[lo] && cs_load(rowval, ib, q - 1) - base >= r) atomicOr(err, (unsigned)CS_BAD_ORDER);
-        atomicAdd(&rcnt[r], 1);
-    }
-}
-// the long columns in ascending order: a flag per column, its exclusive scan, a scatter
-__global__ void __launch_bounds__(kBlock) k_cl_flag_long(const int *__restrict__ ptr, int64_t n, int *__restrict__ flag)
-{
-    const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (j < n) flag[j] = ptr[j + 1] - ptr[j] > kCsLong ? 1 : 0;
-}
-__global__ void __launch_bounds__(kBlock) k_cl_scatter_long(const int *__restrict__ ptr, int64_t n, const int *__restrict__ pos, int *__restrict__ list)
-{
-    const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (j < n && ptr[j + 1] - ptr[j] > kCsLong) list[pos[j]] = (int)j;
-}
 
 // ---- products --------------------------------------------------------------------------------------------------------------------------
 // long rows first: workgroup i sums row long_rows[i] and writes y there; the row kernel then takes those values from y
@@ -141,7 +99,7 @@ __global__ void __launch_bounds__(kBlock) k_cl_rows(ClPat P, const real_t *__res
         double mine[1] = {row < P.M ? yr * yr : 0.0}, tot[1];
         if (cs_finish<1>(mine, part, words, tot, s_w) && threadIdx.x == 0) {
             const double delta = tot[0] + mu * scal[LS_PI];
-            if (cs_bad_pivot(delta)) cl_breakdown(words);
+            if (cs_bad_pivot(delta)) cs_breakdown(words);
             else scal[LS_ALPHA] = scal[LS_GAMMA] / delta;
         }
     }
@@ -254,7 +212,7 @@ __global__ void __launch_bounds__(kBlock) k_cl_cols(ClPat P, const real_t *__res
             if (tot[1] <= scal[LS_TOL2]) {
                 __hip_atomic_store(words + W_DONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             } else if (cl_not_finite(tot[0])) {
-                cl_breakdown(words);
+                cs_breakdown(words);
             } else {
                 scal[LS_BETA] = tot[0] / scal[LS_GAMMA];
                 scal[LS_GAMMA] = tot[0];
@@ -322,200 +280,62 @@ __global__ void __launch_bounds__(kBlock) k_cl_final(int M, int N, ClVecs V, rea
 
 struct fd_csc_lsq {
     fd_ctx *ctx = nullptr;
-    int64_t M = 0, N = 0, nnz = 0;
-    int nlong_r = 0, nlong_c = 0, batch = fdjac::kCsBatchDefault;
-    int *d_colptr = nullptr, *d_rowval = nullptr, *d_row_ptr = nullptr, *d_row_col = nullptr, *d_row_slot = nullptr, *d_row_order = nullptr,
-        *d_long_rows = nullptr, *d_col_order = nullptr, *d_long_cols = nullptr;
+    fdjac::CscLists L;                 // (fdjac_csc_pattern.hip)
+    fdjac::CscSolveState S;
     double *d_vec = nullptr;           // r, q (M doubles each), then y, p, s, z, m, g (N each)
-    double *d_part = nullptr;          // the tiles' sums: 3 x ceil(max(M, N) / 256)
-    double *d_scal = nullptr;
-    int *d_words = nullptr;
-    fdjac::CsRecord *h_rec = nullptr;  // pinned: one record per batch in flight (two)
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    double rtol = 1e-10;
-    int max_iterations = 500, keep = 0;
-    bool solved = false;
 };
 
 using namespace fdjac;
 
 static void cl_free(fd_csc_lsq *s)
 {
-    void *ptrs[] = {s->d_colptr, s->d_rowval, s->d_row_ptr, s->d_row_col, s->d_row_slot, s->d_row_order, s->d_long_rows, s->d_col_order,
-                    s->d_long_cols, s->d_vec, s->d_part, s->d_scal, s->d_words};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    if (s->h_rec) (void)hipHostFree(s->h_rec);
-    for (hipEvent_t e : s->ev) if (e) (void)hipEventDestroy(e);
+    csc_lists_free(&s->L);
+    s->S.free();
+    if (s->d_vec) (void)hipFree(s->d_vec);
     delete s;
 }
 
 static ClPat cl_pat(const fd_csc_lsq *s)
 {
+    const CscLists &L = s->L;
     ClPat P;
-    P.M = (int)s->M; P.N = (int)s->N; P.nnz = (int)s->nnz; P.nlong_r = s->nlong_r; P.nlong_c = s->nlong_c;
-    P.colptr = s->d_colptr; P.rowval = s->d_rowval; P.row_ptr = s->d_row_ptr; P.row_col = s->d_row_col; P.row_slot = s->d_row_slot;
-    P.row_order = s->d_row_order; P.long_rows = s->d_long_rows; P.col_order = s->d_col_order; P.long_cols = s->d_long_cols;
+    P.M = (int)L.M; P.N = (int)L.N; P.nnz = (int)L.nnz; P.nlong_r = L.nlong_r; P.nlong_c = L.nlong_c;
+    P.colptr = L.colptr; P.rowval = L.rowval; P.row_ptr = L.row_ptr; P.row_col = L.row_col; P.row_slot = L.row_slot;
+    P.row_order = L.row_order; P.long_rows = L.long_rows; P.col_order = L.col_order; P.long_cols = L.long_cols;
     return P;
 }
 static ClVecs cl_vecs(const fd_csc_lsq *s)
 {
     ClVecs V;
-    const size_t M = (size_t)s->M, N = (size_t)s->N;
+    const size_t M = (size_t)s->L.M, N = (size_t)s->L.N;
     V.r = s->d_vec; V.q = V.r + M; V.y = V.q + M; V.p = V.y + N; V.s = V.p + N; V.z = V.s + N; V.m = V.z + N; V.g = V.m + N;
     return V;
 }
 static unsigned cl_tiles(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
+
+static int cl_init(fd_csc_lsq *s, fd_ctx *ctx, int64_t M, int64_t N, const void *colptr, const void *rowval, int idx_bytes, int idx_base, int idx_kind)
+{
+    const char *who = "csc least squares";
+    const int rc = csc_lists_build(ctx, who, M, N, colptr, rowval, idx_bytes, idx_base, idx_kind, CSC_WANT_COLUMNS, &s->L);
+    if (rc != FD_OK) return rc;
+    s->ctx = ctx;
+    CSC_TRY(who, hipMalloc((void **)&s->d_vec, sizeof(double) * (2 * (size_t)M + 6 * (size_t)N)));
+    return s->S.create(who, ctx->stream, LS_NSCAL, 3 * (((M > N ? M : N) + kBlock - 1) / kBlock));
+}
 
 int fd_csc_lsq_create(fd_ctx *ctx, int64_t M, int64_t N, const void *colptr, const void *rowval, int idx_bytes, int idx_base, int idx_kind,
                       fd_csc_lsq **out)
 {
     FD_REQUIRE(out != nullptr, FD_ERR_ARG, "NULL argument");
     *out = nullptr;
-    if (!ctx) {      // (no context can exist without a device: say which of the two is the matter)
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { (void)hipGetLastError(); FD_REQUIRE(false, FD_ERR_NODEVICE, "no HIP device"); }
-        FD_REQUIRE(false, FD_ERR_ARG, "ctx is NULL");
-    }
-    FD_REQUIRE(colptr != nullptr, FD_ERR_ARG, "colptr is NULL");
-    FD_REQUIRE(M >= 1 && M < ((int64_t)1 << 31) - 4096, FD_ERR_ARG, "M = %lld", (long long)M);
-    FD_REQUIRE(N >= 1 && N < ((int64_t)1 << 31) - 4096, FD_ERR_ARG, "N = %lld", (long long)N);
-    FD_REQUIRE(idx_bytes == 4 || idx_bytes == 8, FD_ERR_ARG, "idx_bytes = %d (4 or 8)", idx_bytes);
-    FD_REQUIRE(idx_base == 0 || idx_base == 1, FD_ERR_ARG, "idx_base = %d (0 or 1)", idx_base);
-    FD_REQUIRE(idx_kind == FD_HOST || idx_kind == FD_DEVICE, FD_ERR_ARG, "idx_kind = %d", idx_kind);
-    FD_HIP_CHECK(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    // nnz from the two ends of colptr
-    int64_t ends[2] = {0, 0};
-    for (int k = 0; k < 2; ++k) {
-        const char *src = (const char *)colptr + (size_t)(k ? N : 0) * idx_bytes;
-        int64_t v64 = 0; int32_t v32 = 0;
-        void *dst = idx_bytes == 8 ? (void *)&v64 : (void *)&v32;
-        if (idx_kind == FD_DEVICE) { FD_HIP_CHECK(hipStreamSynchronize(st)); FD_HIP_CHECK(hipMemcpy(dst, src, idx_bytes, hipMemcpyDeviceToHost)); }
-        else std::memcpy(dst, src, idx_bytes);
-        ends[k] = idx_bytes == 8 ? v64 : (int64_t)v32;
-    }
-    const int64_t nnz = ends[1] - ends[0];
-    FD_REQUIRE(ends[0] == idx_base, FD_ERR_SHAPE, "colptr[first] = %lld, expected the index base %d", (long long)ends[0], idx_base);
-    FD_REQUIRE(nnz >= 0 && nnz < ((int64_t)1 << 31) - 4096, FD_ERR_SHAPE, "colptr[last] - colptr[first] = %lld entries (0 <= nnz < 2^31)", (long long)nnz);
-    FD_REQUIRE(nnz == 0 || rowval != nullptr, FD_ERR_ARG, "rowval is NULL");
-
     fd_csc_lsq *s = new (std::nothrow) fd_csc_lsq();
     FD_REQUIRE(s != nullptr, FD_ERR_NOMEM, "out of host memory");
-    s->ctx = ctx; s->M = M; s->N = N; s->nnz = nnz;
-    if (const char *v = test_switch("FDJAC_CSC_BATCH")) { const int b = atoi(v); if (b >= 1 && b <= 64) s->batch = b; }
-    const int64_t big = M > N ? M : N, nz1 = nnz > 0 ? nnz : 1;
-    const int64_t mpad = (M + kBlock - 1) / kBlock * kBlock, npad = (N + kBlock - 1) / kBlock * kBlock;
-    const int64_t nscan = (big + kCsScanTile - 1) / kCsScanTile + 2;
-    const int64_t npart = 3 * ((big + kBlock - 1) / kBlock);
-    void *raw_cp = nullptr, *raw_rv = nullptr;
-    int *ecol = nullptr, *cnt = nullptr, *pos = nullptr, *bsum = nullptr, *tmp = nullptr, *misc = nullptr;
-    int rc = FD_OK;
-    unsigned err = 0;
-    int host_misc[4] = {0, 0, 0, 0};      // err, -, the long rows, their cursor
-    int ncl = 0;
-    auto fail = [&](int code) {
-        void *t[] = {raw_cp, raw_rv, ecol, cnt, pos, bsum, tmp, misc};
-        (void)hipStreamSynchronize(st);
-        for (void *p : t) if (p) (void)hipFree(p);
-        if (code != FD_OK) cl_free(s);
-        return code;
-    };
-#define CL_TRY(expr)                                                                                              \
-    do {                                                                                                          \
-        hipError_t _e = (expr);                                                                                   \
-        if (_e != hipSuccess) {                                                                                   \
-            set_error("csc least squares: %s failed: %s", #expr, hipGetErrorString(_e));                          \
-            return fail(_e == hipErrorOutOfMemory ? FD_ERR_NOMEM : FD_ERR_HIP);                                   \
-        }                                                                                                         \
-    } while (0)
-    CL_TRY(hipMalloc((void **)&s->d_colptr, sizeof(int) * (size_t)(N + 1)));
-    CL_TRY(hipMalloc((void **)&s->d_rowval, sizeof(int) * (size_t)nz1));
-    CL_TRY(hipMalloc((void **)&s->d_row_ptr, sizeof(int) * (size_t)(M + 1)));
-    CL_TRY(hipMalloc((void **)&s->d_row_col, sizeof(int) * (size_t)nz1));
-    CL_TRY(hipMalloc((void **)&s->d_row_slot, sizeof(int) * (size_t)nz1));
-    CL_TRY(hipMalloc((void **)&s->d_row_order, sizeof(int) * (size_t)mpad));
-    CL_TRY(hipMalloc((void **)&s->d_col_order, sizeof(int) * (size_t)npad));
-    CL_TRY(hipMalloc((void **)&ecol, sizeof(int) * (size_t)nz1));
-    CL_TRY(hipMalloc((void **)&cnt, sizeof(int) * (size_t)big));
-    CL_TRY(hipMalloc((void **)&pos, sizeof(int) * (size_t)(N + 1)));
-    CL_TRY(hipMalloc((void **)&bsum, sizeof(int) * (size_t)nscan));
-    CL_TRY(hipMalloc((void **)&misc, sizeof(int) * 4));
-    const void *cp = colptr, *rv = rowval;
-    if (idx_kind == FD_HOST) {
-        CL_TRY(hipMalloc(&raw_cp, (size_t)idx_bytes * (size_t)(N + 1)));
-        CL_TRY(hipMemcpyAsync(raw_cp, colptr, (size_t)idx_bytes * (size_t)(N + 1), hipMemcpyHostToDevice, st));
-        cp = raw_cp;
-        if (nnz > 0) {
-            CL_TRY(hipMalloc(&raw_rv, (size_t)idx_bytes * (size_t)nnz));
-            CL_TRY(hipMemcpyAsync(raw_rv, rowval, (size_t)idx_bytes * (size_t)nnz, hipMemcpyHostToDevice, st));
-            rv = raw_rv;
-        }
+    const int rc = cl_init(s, ctx, M, N, colptr, rowval, idx_bytes, idx_base, idx_kind);
+    if (rc != FD_OK) {
+        if (s->ctx) (void)hipStreamSynchronize(s->ctx->stream);
+        cl_free(s);
+        return rc;
     }
-    CL_TRY(hipMemsetAsync(misc, 0, sizeof(int) * 4, st));
-    CL_TRY(hipMemsetAsync(cnt, 0, sizeof(int) * (size_t)big, st));
-    hipLaunchKernelGGL(k_cs_colptr, dim3(csc_grid(N + 1, kBlock)), dim3(kBlock), 0, st, cp, idx_bytes, idx_base, N, nnz, s->d_colptr, (unsigned *)misc);
-    CL_TRY(hipGetLastError());
-    CL_TRY(hipMemcpyAsync(host_misc, misc, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
-    CL_TRY(hipStreamSynchronize(st));
-    err = (unsigned)host_misc[0];
-    if (err & CS_BAD_COLPTR) { set_error("csc least squares: colptr is not a monotone sequence of N + 1 entries from the index base to nnz + base"); return fail(FD_ERR_SHAPE); }
-    if (nnz > 0) {
-        hipLaunchKernelGGL(k_cl_entries, dim3(csc_grid(nnz, kBlock)), dim3(kBlock), 0, st, rv, idx_bytes, idx_base, (const int *)s->d_colptr, M, N, nnz,
-                           s->d_rowval, ecol, cnt, (unsigned *)misc);
-        CL_TRY(hipGetLastError());
-    }
-    CL_TRY(hipMemcpyAsync(host_misc, misc, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
-    CL_TRY(hipStreamSynchronize(st));
-    err = (unsigned)host_misc[0];
-    if (err & CS_BAD_ROW) { set_error("csc least squares: rowval holds a row outside the %lld x %lld matrix", (long long)M, (long long)N); return fail(FD_ERR_SHAPE); }
-    if (err & CS_BAD_ORDER) { set_error("csc least squares: the rows of a column are not strictly ascending"); return fail(FD_ERR_SHAPE); }
-    // the pattern by rows
-    rc = csc_exscan(st, cnt, M, s->d_row_ptr, bsum);
-    if (rc != FD_OK) return fail(rc);
-    CL_TRY(hipMemsetAsync(cnt, 0, sizeof(int) * (size_t)big, st));
-    if (nnz > 0) {
-        hipLaunchKernelGGL(k_cs_fill, dim3(csc_grid(nnz, kBlock)), dim3(kBlock), 0, st, (const int *)s->d_rowval, nnz, (const int *)s->d_row_ptr, cnt, s->d_row_slot);
-        CL_TRY(hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_cs_sort_short, dim3(cl_tiles(M, kBlock)), dim3(kBlock), 0, st, (const int *)s->d_row_ptr, M, s->d_row_slot, (const int *)ecol,
-                       s->d_row_col, misc + 2);
-    hipLaunchKernelGGL(k_cs_order, dim3(cl_tiles(M, kBlock)), dim3(kBlock), 0, st, (const int *)s->d_row_ptr, M, s->d_row_order);
-    // the columns: their lane order and the long ones in ascending order
-    hipLaunchKernelGGL(k_cs_order, dim3(cl_tiles(N, kBlock)), dim3(kBlock), 0, st, (const int *)s->d_colptr, N, s->d_col_order);
-    hipLaunchKernelGGL(k_cl_flag_long, dim3(cl_tiles(N, kBlock)), dim3(kBlock), 0, st, (const int *)s->d_colptr, N, cnt);
-    CL_TRY(hipGetLastError());
-    rc = csc_exscan(st, cnt, N, pos, bsum);
-    if (rc != FD_OK) return fail(rc);
-    CL_TRY(hipMemcpyAsync(host_misc, misc, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
-    CL_TRY(hipMemcpyAsync(&ncl, pos + N, sizeof(int), hipMemcpyDeviceToHost, st));
-    CL_TRY(hipStreamSynchronize(st));
-    s->nlong_r = host_misc[2];
-    s->nlong_c = ncl;
-    if (s->nlong_r > 0) {
-        CL_TRY(hipMalloc((void **)&s->d_long_rows, sizeof(int) * (size_t)s->nlong_r));
-        CL_TRY(hipMalloc((void **)&tmp, sizeof(int) * (size_t)nz1));
-        hipLaunchKernelGGL(k_cs_list_long, dim3(cl_tiles(M, kBlock)), dim3(kBlock), 0, st, (const int *)s->d_row_ptr, M, s->d_long_rows, misc + 3);
-        hipLaunchKernelGGL(k_cs_sort_long, dim3((unsigned)s->nlong_r), dim3(kBlock), 0, st, (const int *)s->d_row_ptr, (const int *)s->d_long_rows, s->d_row_slot, tmp,
-                           (const int *)ecol, s->d_row_col);
-        CL_TRY(hipGetLastError());
-    }
-    if (s->nlong_c > 0) {
-        CL_TRY(hipMalloc((void **)&s->d_long_cols, sizeof(int) * (size_t)s->nlong_c));
-        hipLaunchKernelGGL(k_cl_scatter_long, dim3(cl_tiles(N, kBlock)), dim3(kBlock), 0, st, (const int *)s->d_colptr, N, (const int *)pos, s->d_long_cols);
-        CL_TRY(hipGetLastError());
-    }
-    CL_TRY(hipMalloc((void **)&s->d_vec, sizeof(double) * (2 * (size_t)M + 6 * (size_t)N)));
-    CL_TRY(hipMalloc((void **)&s->d_part, sizeof(double) * (size_t)npart));
-    CL_TRY(hipMalloc((void **)&s->d_scal, sizeof(double) * LS_NSCAL));
-    CL_TRY(hipMalloc((void **)&s->d_words, sizeof(int) * W_NWORDS));
-    CL_TRY(hipHostMalloc((void **)&s->h_rec, sizeof(CsRecord) * 2, hipHostMallocDefault));
-    CL_TRY(hipEventCreateWithFlags(&s->ev[0], hipEventDisableTiming));
-    CL_TRY(hipEventCreateWithFlags(&s->ev[1], hipEventDisableTiming));
-    CL_TRY(hipMemsetAsync(s->d_scal, 0, sizeof(double) * LS_NSCAL, st));
-    CL_TRY(hipMemsetAsync(s->d_words, 0, sizeof(int) * W_NWORDS, st));
-    CL_TRY(hipStreamSynchronize(st));
-#undef CL_TRY
-    (void)fail(FD_OK);
     *out = s;
     return FD_OK;
 }
@@ -532,16 +352,13 @@ int fd_csc_lsq_destroy(fd_csc_lsq *s)
 int fd_csc_lsq_set_options(fd_csc_lsq *s, double rtol, int max_iterations)
 {
     FD_REQUIRE(s != nullptr, FD_ERR_ARG, "lsq is NULL");
-    FD_REQUIRE(rtol >= 0.0 && rtol < 1.0, FD_ERR_ARG, "rtol = %g (0 <= rtol < 1)", rtol);
-    FD_REQUIRE(max_iterations >= 1, FD_ERR_ARG, "max_iterations = %d", max_iterations);
-    s->rtol = rtol; s->max_iterations = max_iterations;
-    return FD_OK;
+    return s->S.set_options(rtol, max_iterations);
 }
 
 int fd_csc_lsq_set_policy(fd_csc_lsq *s, int keep_unconverged)
 {
     FD_REQUIRE(s != nullptr, FD_ERR_ARG, "lsq is NULL");
-    s->keep = keep_unconverged ? 1 : 0;
+    s->S.keep = keep_unconverged ? 1 : 0;
     return FD_OK;
 }
 
@@ -549,19 +366,19 @@ int fd_csc_lsq_set_policy(fd_csc_lsq *s, int keep_unconverged)
 int fd_csc_lsq_row_lists(fd_csc_lsq *s, const void **row_ptr, const void **row_col, const void **row_slot, int64_t *nnz_out, int64_t *long_rows_out)
 {
     FD_REQUIRE(s != nullptr, FD_ERR_ARG, "lsq is NULL");
-    if (row_ptr) *row_ptr = s->d_row_ptr;
-    if (row_col) *row_col = s->d_row_col;
-    if (row_slot) *row_slot = s->d_row_slot;
-    if (nnz_out) *nnz_out = s->nnz;
-    if (long_rows_out) *long_rows_out = s->nlong_r;
+    if (row_ptr) *row_ptr = s->L.row_ptr;
+    if (row_col) *row_col = s->L.row_col;
+    if (row_slot) *row_slot = s->L.row_slot;
+    if (nnz_out) *nnz_out = s->L.nnz;
+    if (long_rows_out) *long_rows_out = s->L.nlong_r;
     return FD_OK;
 }
 
 int fd_csc_lsq_long_columns(fd_csc_lsq *s, const void **long_cols, int64_t *count_out)
 {
     FD_REQUIRE(s != nullptr, FD_ERR_ARG, "lsq is NULL");
-    if (long_cols) *long_cols = s->d_long_cols;
-    if (count_out) *count_out = s->nlong_c;
+    if (long_cols) *long_cols = s->L.long_cols;
+    if (count_out) *count_out = s->L.nlong_c;
     return FD_OK;
 }
 
@@ -571,9 +388,9 @@ static void cl_product_rows(fd_csc_lsq *s, const real_t *nz, const TV *v, TV *y,
 {
     hipStream_t st = s->ctx->stream;
     const ClPat P = cl_pat(s);
-    if (s->nlong_r > 0)
-        hipLaunchKernelGGL((k_cl_long_rows<TV>), dim3((unsigned)s->nlong_r), dim3(kBlock), 0, st, P, nz, v, y, guarded ? (const int *)s->d_words : (const int *)nullptr);
-    hipLaunchKernelGGL((k_cl_rows<TV, MODE>), dim3(cl_tiles(s->M, kBlock)), dim3(kBlock), 0, st, P, nz, v, y, mu, s->d_scal, s->d_words, s->d_part);
+    if (P.nlong_r > 0)
+        hipLaunchKernelGGL((k_cl_long_rows<TV>), dim3((unsigned)P.nlong_r), dim3(kBlock), 0, st, P, nz, v, y, guarded ? (const int *)s->S.d_words : (const int *)nullptr);
+    hipLaunchKernelGGL((k_cl_rows<TV, MODE>), dim3(cl_tiles(P.M, kBlock)), dim3(kBlock), 0, st, P, nz, v, y, mu, s->S.d_scal, s->S.d_words, s->S.d_part);
 }
 // y = J^T v on the stream: the long columns, then the tiles
 template <typename TV, int MODE>
@@ -582,15 +399,15 @@ static void cl_product_cols(fd_csc_lsq *s, const real_t *nz, const TV *v, TV *y,
     hipStream_t st = s->ctx->stream;
     const ClPat P = cl_pat(s);
     const ClVecs V = cl_vecs(s);
-    if (s->nlong_c > 0)
-        hipLaunchKernelGGL((k_cl_long_cols<TV, MODE == 1>), dim3((unsigned)s->nlong_c), dim3(kBlock), 0, st, P, nz, v, y, V.g,
-                           MODE == 2 ? (const int *)s->d_words : (const int *)nullptr);
-    hipLaunchKernelGGL((k_cl_cols<TV, MODE>), dim3(cl_tiles(s->N, kBlock)), dim3(kBlock), 0, st, P, nz, v, y, V, mu, kind, s->rtol, s->d_scal, s->d_words, s->d_part);
+    if (P.nlong_c > 0)
+        hipLaunchKernelGGL((k_cl_long_cols<TV, MODE == 1>), dim3((unsigned)P.nlong_c), dim3(kBlock), 0, st, P, nz, v, y, V.g,
+                           MODE == 2 ? (const int *)s->S.d_words : (const int *)nullptr);
+    hipLaunchKernelGGL((k_cl_cols<TV, MODE>), dim3(cl_tiles(P.N, kBlock)), dim3(kBlock), 0, st, P, nz, v, y, V, mu, kind, s->S.rtol, s->S.d_scal, s->S.d_words, s->S.d_part);
 }
 
 int fd_csc_lsq_matvec_async(fd_csc_lsq *s, const void *nzval, const void *v, void *y, int transpose)
 {
-    FD_REQUIRE(s && v && y && (nzval || s->nnz == 0), FD_ERR_ARG, "NULL argument");
+    FD_REQUIRE(s && v && y && (nzval || s->L.nnz == 0), FD_ERR_ARG, "NULL argument");
     FD_REQUIRE(v != y, FD_ERR_ARG, "y must not be v");
     FD_HIP_CHECK(hipSetDevice(s->ctx->device));
     if (transpose) cl_product_cols<real_t, 0>(s, (const real_t *)nzval, (const real_t *)v, (real_t *)y, 0.0, 0);
@@ -601,58 +418,41 @@ int fd_csc_lsq_matvec_async(fd_csc_lsq *s, const void *nzval, const void *v, voi
 
 int fd_csc_lsq_solve_async(fd_csc_lsq *s, double mu, int damping_kind, const void *nzval, const void *b, void *y, void *r_out)
 {
-    FD_REQUIRE(s && b && y && (nzval || s->nnz == 0), FD_ERR_ARG, "NULL argument");
+    FD_REQUIRE(s && b && y && (nzval || s->L.nnz == 0), FD_ERR_ARG, "NULL argument");
     FD_REQUIRE(damping_kind == FD_CSC_LSQ_DAMP_IDENTITY || damping_kind == FD_CSC_LSQ_DAMP_COLNORM, FD_ERR_ARG,
                "damping_kind = %d (0: identity, 1: column norms)", damping_kind);
     FD_REQUIRE(mu >= 0.0, FD_ERR_ARG, "mu = %g (mu >= 0)", mu);      // (a NaN fails the comparison)
     FD_HIP_CHECK(hipSetDevice(s->ctx->device));
     hipStream_t st = s->ctx->stream;
-    const int M = (int)s->M, N = (int)s->N;
+    CscSolveState &S = s->S;
+    const int M = (int)s->L.M, N = (int)s->L.N;
     const real_t *nz = (const real_t *)nzval;
     const ClVecs V = cl_vecs(s);
     const unsigned gv = cl_tiles(N, kCsVecTile), gu = cl_tiles(M > N ? M : N, kCsVecTile);
-    FD_HIP_CHECK(hipMemsetAsync(s->d_words, 0, sizeof(int) * W_NWORDS, st));
+    FD_HIP_CHECK(hipMemsetAsync(S.d_words, 0, sizeof(int) * W_NWORDS, st));
     hipLaunchKernelGGL(k_cl_start, dim3(cl_tiles(M, kCsVecTile)), dim3(kBlock), 0, st, M, (const real_t *)b, V.r);
     cl_product_cols<double, 1>(s, nz, V.r, V.s, mu, damping_kind);
-    // the iterations, in batches; the record of batch k is read while batch k + 1 is already enqueued (its kernels leave at once
-    // when the solve is done), so the device never waits for the host
-    int enq = 0, nb = 0;
-    bool stop = false;
-    while (!stop) {
-        const int todo = s->max_iterations - enq < s->batch ? s->max_iterations - enq : s->batch;
-        for (int it = 0; it < todo; ++it) {
-            cl_product_rows<double, 1>(s, nz, V.p, V.q, mu, true);
-            hipLaunchKernelGGL(k_cl_update, dim3(gu), dim3(kBlock), 0, st, M, N, V, (const double *)s->d_scal, (const int *)s->d_words);
-            cl_product_cols<double, 2>(s, nz, V.r, V.s, mu, damping_kind);
-            hipLaunchKernelGGL(k_cl_p, dim3(gv), dim3(kBlock), 0, st, N, damping_kind, V, s->d_scal, s->d_words, s->d_part);
-        }
-        enq += todo;
-        FD_HIP_CHECK(hipGetLastError());
-        FD_HIP_CHECK(hipMemcpyAsync(&s->h_rec[nb & 1], s->d_words, sizeof(CsRecord), hipMemcpyDeviceToHost, st));
-        FD_HIP_CHECK(hipEventRecord(s->ev[nb & 1], st));
-        if (nb >= 1) {
-            FD_HIP_CHECK(hipEventSynchronize(s->ev[(nb - 1) & 1]));
-            stop = s->h_rec[(nb - 1) & 1].done != 0;
-        }
-        ++nb;
-        if (enq >= s->max_iterations) stop = true;
-    }
-    hipLaunchKernelGGL(k_cl_final, dim3(cl_tiles(M > N ? M : N, kBlock)), dim3(kBlock), 0, st, M, N, V, (real_t *)y, (real_t *)r_out, s->d_words, s->keep);
+    const int rc = S.run(st, [&] {      // one iteration: 4 launches (+ 1 with long rows, + 1 with long columns)
+        cl_product_rows<double, 1>(s, nz, V.p, V.q, mu, true);
+        hipLaunchKernelGGL(k_cl_update, dim3(gu), dim3(kBlock), 0, st, M, N, V, (const double *)S.d_scal, (const int *)S.d_words);
+        cl_product_cols<double, 2>(s, nz, V.r, V.s, mu, damping_kind);
+        hipLaunchKernelGGL(k_cl_p, dim3(gv), dim3(kBlock), 0, st, N, damping_kind, V, S.d_scal, S.d_words, S.d_part);
+    });
+    if (rc != FD_OK) return rc;
+    hipLaunchKernelGGL(k_cl_final, dim3(cl_tiles(M > N ? M : N, kBlock)), dim3(kBlock), 0, st, M, N, V, (real_t *)y, (real_t *)r_out, S.d_words, S.keep);
     FD_HIP_CHECK(hipGetLastError());
-    s->solved = true;
+    S.solved = true;
     return FD_OK;
 }
 
 int fd_csc_lsq_status(fd_csc_lsq *s, int *flags_out, int64_t *iterations_out, double *grad_norm_out, double *grad0_norm_out)
 {
     FD_REQUIRE(s != nullptr, FD_ERR_ARG, "lsq is NULL");
-    FD_HIP_CHECK(hipSetDevice(s->ctx->device));
-    FD_HIP_CHECK(hipStreamSynchronize(s->ctx->stream));
     int w[W_NWORDS];
     double sc[LS_NSCAL];
-    FD_HIP_CHECK(hipMemcpy(w, s->d_words, sizeof w, hipMemcpyDeviceToHost));
-    FD_HIP_CHECK(hipMemcpy(sc, s->d_scal, sizeof sc, hipMemcpyDeviceToHost));
-    if (flags_out) *flags_out = s->solved ? w[W_FINAL] : 0;
+    const int rc = s->S.read_status(s->ctx, w, sc);
+    if (rc != FD_OK) return rc;
+    if (flags_out) *flags_out = w[W_FINAL];
     if (iterations_out) *iterations_out = w[W_ITERS];
     if (grad_norm_out) *grad_norm_out = std::sqrt(sc[LS_GN2]);
     if (grad0_norm_out) *grad0_norm_out = std::sqrt(sc[LS_G02]);

@@ -3,11 +3,7 @@
 //     y = (alpha I + beta J) v,   y = (alpha I + beta J)^T v,   and   (alpha I + beta J) y = b   by Jacobi-preconditioned BiCGStab.
 // DESIGN.md 4.9 has the contract; tests/csc_solve_model.py restates every summation order below in numpy and the GPU tests compare bits.
 //
-// CREATE (device): colptr / rowval are converted to 0-based Int32 and validated; every entry finds its column by a binary search in
-// colptr and joins its row (counts by integer atomics, an exclusive scan, a fill pass whose order depends on the atomics' arrival);
-// every row's segment is then SORTED by slot -- storage order is column order, so the lists equal a host counting sort's whatever
-// the arrival order was.  Rows of more than kCsLong entries go on a list of their own.  A row order per tile of 256 rows (descending
-// length, ties by row) deals lanes to rows of similar length.
+// CREATE is the shared builder's (fdjac_csc_pattern.hip), with the diagonal's slots and the pattern's reach.
 //
 // ORDERS.  Row r of at most kCsLong entries: acc = 0; acc += nzval[slot_k] * v[col_k] for k ascending; y_r = alpha v_r + beta acc.
 // A longer row is summed by ONE workgroup: thread t adds the entries k = t, t + 256, ... in that order, then block_sum().
@@ -34,7 +30,6 @@
 #include "fdjac_device.h"
 #include "fdjac_csc_common.h"
 #include <cmath>
-#include <cstring>
 #include <new>
 
 namespace fdjac {
@@ -49,32 +44,6 @@ struct CsPat {                         // the pattern as the kernels see it
     int N, nnz, nlong, reach, window;
     const int *colptr, *rowval, *row_ptr, *row_col, *row_slot, *order, *long_rows, *diag;
 };
-
-// ---- create (the scans, the fill / sort passes and the lane order: fdjac_csc_common.h) ----------------------------------------------
-// one lane per entry: its row (validated, 0-based), its column (binary search in the monotone cptr), rows strictly ascending within
-// the column, the row's count, the diagonal's slot and the pattern's reach
-__global__ void __launch_bounds__(kBlock) k_cs_entries(const void *__restrict__ rowval, int ib, int base, const int *__restrict__ cptr,
-                                                       int64_t N, int64_t nnz, int *__restrict__ erow, int *__restrict__ ecol,
-                                                       int *__restrict__ rcnt, int *__restrict__ diag, int *reach, unsigned *err)
-{
-    for (int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x; q < nnz; q += (int64_t)gridDim.x * kBlock) {
-        const int64_t r = cs_load(rowval, ib, q) - base;
-        const bool ok = r >= 0 && r < N;
-        int64_t lo = 0, hi = N;      // cptr[lo] <= q < cptr[hi]
-        while (hi - lo > 1) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (cptr[mid] <= q) lo = mid; else hi = mid;
-        }
-        erow[q] = ok ? (int)r : 0;
-        ecol[q] = (int)lo;
-        if (!ok) { atomicOr(err, (unsigned)CS_BAD_ROW); continue; }
-        if (q > cptr[lo] && cs_load(rowval, ib, q - 1) - base >= r) atomicOr(err, (unsigned)CS_BAD_ORDER);
-        atomicAdd(&rcnt[r], 1);
-        if (r == lo) diag[lo] = (int)q;
-        const int d = (int)(r > lo ? r - lo : lo - r);
-        if (d > 0) atomicMax(reach, d);
-    }
-}
 
 // ---- products --------------------------------------------------------------------------------------------------------------------------
 // long rows first: workgroup i sums row long_rows[i] and writes y there; the row kernel then takes those values from y
@@ -151,13 +120,13 @@ __global__ void __launch_bounds__(kBlock) k_cs_rows(CsPat P, double alpha, doubl
     if (MODE == 1) {
         double mine[1] = {row < P.N ? c[row] * yr : 0.0}, tot[1];
         if (cs_finish<1>(mine, part, words, tot, s_w) && threadIdx.x == 0) {
-            if (cs_bad_pivot(tot[0])) { atomicOr(words + W_FLAGS, 2); __hip_atomic_store(words + W_DONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+            if (cs_bad_pivot(tot[0])) cs_breakdown(words);
             else scal[S_ALPHA] = scal[S_RHO] / tot[0];
         }
     } else if (MODE == 2) {
         double mine[2] = {row < P.N ? yr * c[row] : 0.0, row < P.N ? yr * yr : 0.0}, tot[2];
         if (cs_finish<2>(mine, part, words, tot, s_w) && threadIdx.x == 0) {
-            if (cs_bad_pivot(tot[1])) { atomicOr(words + W_FLAGS, 2); __hip_atomic_store(words + W_DONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+            if (cs_bad_pivot(tot[1])) cs_breakdown(words);
             else scal[S_OMEGA] = tot[0] / tot[1];
         }
     }
@@ -345,10 +314,7 @@ __global__ void __launch_bounds__(kCsBinvWaves * 64) k_cs_binv(CsPat P, int bs, 
         }
         __syncthreads();
     }
-    if (bad && lane == 0) {      // (every lane of the wavefront has seen the same pivots)
-        atomicOr(words + W_FLAGS, 2);
-        __hip_atomic_store(words + W_DONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    if (bad && lane == 0) cs_breakdown(words);      // (every lane of the wavefront has seen the same pivots)
     if (col_b)      // lane i writes row i of the inverse, plane by plane: n consecutive doubles per plane
         for (int c = 0; c < bs; ++c) minv[(size_t)c * P.N + b0 + lane] = c < n ? a[lane * ld + bs + c] : 0.0;
 }
@@ -395,19 +361,10 @@ __global__ void __launch_bounds__(kBlock) k_cs_final(int N, const double *__rest
 
 struct fd_csc_solver {
     fd_ctx *ctx = nullptr;
-    int64_t N = 0, nnz = 0;
-    int nlong = 0, reach = 0, window = 1, batch = fdjac::kCsBatchDefault;
-    int *d_colptr = nullptr, *d_rowval = nullptr, *d_row_ptr = nullptr, *d_row_col = nullptr, *d_row_slot = nullptr, *d_order = nullptr,
-        *d_long = nullptr, *d_diag = nullptr;
+    fdjac::CscLists L;                 // (fdjac_csc_pattern.hip)
+    fdjac::CscSolveState S;
+    int window = 1;
     double *d_vec = nullptr;           // ten vectors of N doubles
-    double *d_part = nullptr;          // the tiles' sums: 2 x ceil(N / 256)
-    double *d_scal = nullptr;
-    int *d_words = nullptr;
-    fdjac::CsRecord *h_rec = nullptr;  // pinned: one record per batch in flight (two)
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    double rtol = 1e-10;
-    int max_iterations = 500, keep = 0;
-    bool solved = false;
     int pc_kind = FD_CSC_PRECOND_JACOBI, pc_bs = 0;      // what the next solve uses
     double *d_minv = nullptr;          // block Jacobi: minv_bs planes of N doubles (allocated by the first solve that needs them)
     size_t minv_cap = 0;               // doubles allocated
@@ -418,26 +375,40 @@ using namespace fdjac;
 
 static void csc_solver_free(fd_csc_solver *s)
 {
-    void *ptrs[] = {s->d_colptr, s->d_rowval, s->d_row_ptr, s->d_row_col, s->d_row_slot, s->d_order, s->d_long, s->d_diag,
-                    s->d_vec, s->d_part, s->d_scal, s->d_words, s->d_minv};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    if (s->h_rec) (void)hipHostFree(s->h_rec);
-    for (hipEvent_t e : s->ev) if (e) (void)hipEventDestroy(e);
+    csc_lists_free(&s->L);
+    s->S.free();
+    if (s->d_vec) (void)hipFree(s->d_vec);
+    if (s->d_minv) (void)hipFree(s->d_minv);
     delete s;
 }
 
 static CsPat csc_pat(const fd_csc_solver *s)
 {
+    const CscLists &L = s->L;
     CsPat P;
-    P.N = (int)s->N; P.nnz = (int)s->nnz; P.nlong = s->nlong; P.reach = s->reach; P.window = s->window;
-    P.colptr = s->d_colptr; P.rowval = s->d_rowval; P.row_ptr = s->d_row_ptr; P.row_col = s->d_row_col; P.row_slot = s->d_row_slot;
-    P.order = s->d_order; P.long_rows = s->d_long; P.diag = s->d_diag;
+    P.N = (int)L.N; P.nnz = (int)L.nnz; P.nlong = L.nlong_r; P.reach = L.reach; P.window = s->window;
+    P.colptr = L.colptr; P.rowval = L.rowval; P.row_ptr = L.row_ptr; P.row_col = L.row_col; P.row_slot = L.row_slot;
+    P.order = L.row_order; P.long_rows = L.long_rows; P.diag = L.diag;
     return P;
 }
 static size_t csc_win_bytes(const fd_csc_solver *s, size_t elem)
 {
     if (!s->window) return 0;
-    return (size_t)(kBlock + 2 * s->reach) * elem;
+    return (size_t)(kBlock + 2 * s->L.reach) * elem;
+}
+
+static int csc_solver_init(fd_csc_solver *s, fd_ctx *ctx, int64_t N, const void *colptr, const void *rowval, int idx_bytes, int idx_base, int idx_kind)
+{
+    const char *who = "csc solver";
+    const int rc = csc_lists_build(ctx, who, N, N, colptr, rowval, idx_bytes, idx_base, idx_kind, CSC_WANT_DIAG, &s->L);
+    if (rc != FD_OK) return rc;
+    s->ctx = ctx;
+    if (const char *v = test_switch("FDJAC_CSC_WINDOW")) s->window = atoi(v) != 0;
+    // the LDS window of v only when the measured reach allows it: every column a tile's rows can name then lies inside the window;
+    // a wider pattern would stage 2 * kCsWinHalo elements per tile to serve the near-diagonal gathers alone
+    if (s->L.reach > kCsWinHalo) s->window = 0;
+    CSC_TRY(who, hipMalloc((void **)&s->d_vec, sizeof(double) * 10 * (size_t)N));
+    return s->S.create(who, ctx->stream, S_NSCAL, 2 * ((N + kBlock - 1) / kBlock));
 }
 
 int fd_csc_solver_create(fd_ctx *ctx, int64_t N, const void *colptr, const void *rowval, int idx_bytes, int idx_base, int idx_kind,
@@ -445,140 +416,14 @@ int fd_csc_solver_create(fd_ctx *ctx, int64_t N, const void *colptr, const void 
 {
     FD_REQUIRE(out != nullptr, FD_ERR_ARG, "NULL argument");
     *out = nullptr;
-    if (!ctx) {      // (no context can exist without a device: say which of the two is the matter)
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { (void)hipGetLastError(); FD_REQUIRE(false, FD_ERR_NODEVICE, "no HIP device"); }
-        FD_REQUIRE(false, FD_ERR_ARG, "ctx is NULL");
-    }
-    FD_REQUIRE(colptr != nullptr, FD_ERR_ARG, "colptr is NULL");
-    FD_REQUIRE(N >= 1 && N < ((int64_t)1 << 31) - 4096, FD_ERR_ARG, "N = %lld", (long long)N);
-    FD_REQUIRE(idx_bytes == 4 || idx_bytes == 8, FD_ERR_ARG, "idx_bytes = %d (4 or 8)", idx_bytes);
-    FD_REQUIRE(idx_base == 0 || idx_base == 1, FD_ERR_ARG, "idx_base = %d (0 or 1)", idx_base);
-    FD_REQUIRE(idx_kind == FD_HOST || idx_kind == FD_DEVICE, FD_ERR_ARG, "idx_kind = %d", idx_kind);
-    FD_HIP_CHECK(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    // nnz from the two ends of colptr
-    int64_t ends[2] = {0, 0};
-    for (int k = 0; k < 2; ++k) {
-        const char *src = (const char *)colptr + (size_t)(k ? N : 0) * idx_bytes;
-        int64_t v64 = 0; int32_t v32 = 0;
-        void *dst = idx_bytes == 8 ? (void *)&v64 : (void *)&v32;
-        if (idx_kind == FD_DEVICE) { FD_HIP_CHECK(hipStreamSynchronize(st)); FD_HIP_CHECK(hipMemcpy(dst, src, idx_bytes, hipMemcpyDeviceToHost)); }
-        else std::memcpy(dst, src, idx_bytes);
-        ends[k] = idx_bytes == 8 ? v64 : (int64_t)v32;
-    }
-    const int64_t nnz = ends[1] - ends[0];
-    FD_REQUIRE(ends[0] == idx_base, FD_ERR_SHAPE, "colptr[first] = %lld, expected the index base %d", (long long)ends[0], idx_base);
-    FD_REQUIRE(nnz >= 0 && nnz < ((int64_t)1 << 31) - 4096, FD_ERR_SHAPE, "colptr[last] - colptr[first] = %lld entries (0 <= nnz < 2^31)", (long long)nnz);
-    FD_REQUIRE(nnz == 0 || rowval != nullptr, FD_ERR_ARG, "rowval is NULL");
-
     fd_csc_solver *s = new (std::nothrow) fd_csc_solver();
     FD_REQUIRE(s != nullptr, FD_ERR_NOMEM, "out of host memory");
-    s->ctx = ctx; s->N = N; s->nnz = nnz;
-    if (const char *v = test_switch("FDJAC_CSC_WINDOW")) s->window = atoi(v) != 0;
-    if (const char *v = test_switch("FDJAC_CSC_BATCH")) { const int b = atoi(v); if (b >= 1 && b <= 64) s->batch = b; }
-    const int64_t npad = (N + kBlock - 1) / kBlock * kBlock, nz1 = nnz > 0 ? nnz : 1;
-    const int64_t nscan = (N + kCsScanTile - 1) / kCsScanTile + 2;
-    const int64_t npart = 2 * ((N + kBlock - 1) / kBlock);
-    void *raw_cp = nullptr, *raw_rv = nullptr;
-    int *ecol = nullptr, *rcnt = nullptr, *bsum = nullptr, *tmp = nullptr, *misc = nullptr;
-    int rc = FD_OK;
-    unsigned err = 0;
-    int host_misc[4] = {0, 0, 0, 0};      // err, reach, nlong, long cursor
-    auto fail = [&](int code) {
-        void *t[] = {raw_cp, raw_rv, ecol, rcnt, bsum, tmp, misc};
-        (void)hipStreamSynchronize(st);
-        for (void *p : t) if (p) (void)hipFree(p);
-        if (code != FD_OK) csc_solver_free(s);
-        return code;
-    };
-#define CS_TRY(expr)                                                                                              \
-    do {                                                                                                          \
-        hipError_t _e = (expr);                                                                                   \
-        if (_e != hipSuccess) {                                                                                   \
-            set_error("csc solver: %s failed: %s", #expr, hipGetErrorString(_e));                                 \
-            return fail(_e == hipErrorOutOfMemory ? FD_ERR_NOMEM : FD_ERR_HIP);                                   \
-        }                                                                                                         \
-    } while (0)
-    CS_TRY(hipMalloc((void **)&s->d_colptr, sizeof(int) * (size_t)(N + 1)));
-    CS_TRY(hipMalloc((void **)&s->d_rowval, sizeof(int) * (size_t)nz1));
-    CS_TRY(hipMalloc((void **)&s->d_row_ptr, sizeof(int) * (size_t)(N + 1)));
-    CS_TRY(hipMalloc((void **)&s->d_row_col, sizeof(int) * (size_t)nz1));
-    CS_TRY(hipMalloc((void **)&s->d_row_slot, sizeof(int) * (size_t)nz1));
-    CS_TRY(hipMalloc((void **)&s->d_order, sizeof(int) * (size_t)npad));
-    CS_TRY(hipMalloc((void **)&s->d_diag, sizeof(int) * (size_t)N));
-    CS_TRY(hipMalloc((void **)&ecol, sizeof(int) * (size_t)nz1));
-    CS_TRY(hipMalloc((void **)&rcnt, sizeof(int) * (size_t)N));
-    CS_TRY(hipMalloc((void **)&bsum, sizeof(int) * (size_t)nscan));
-    CS_TRY(hipMalloc((void **)&misc, sizeof(int) * 4));
-    const void *cp = colptr, *rv = rowval;
-    if (idx_kind == FD_HOST) {
-        CS_TRY(hipMalloc(&raw_cp, (size_t)idx_bytes * (size_t)(N + 1)));
-        CS_TRY(hipMemcpyAsync(raw_cp, colptr, (size_t)idx_bytes * (size_t)(N + 1), hipMemcpyHostToDevice, st));
-        cp = raw_cp;
-        if (nnz > 0) {
-            CS_TRY(hipMalloc(&raw_rv, (size_t)idx_bytes * (size_t)nnz));
-            CS_TRY(hipMemcpyAsync(raw_rv, rowval, (size_t)idx_bytes * (size_t)nnz, hipMemcpyHostToDevice, st));
-            rv = raw_rv;
-        }
+    const int rc = csc_solver_init(s, ctx, N, colptr, rowval, idx_bytes, idx_base, idx_kind);
+    if (rc != FD_OK) {
+        if (s->ctx) (void)hipStreamSynchronize(s->ctx->stream);
+        csc_solver_free(s);
+        return rc;
     }
-    CS_TRY(hipMemsetAsync(misc, 0, sizeof(int) * 4, st));
-    CS_TRY(hipMemsetAsync(rcnt, 0, sizeof(int) * (size_t)N, st));
-    CS_TRY(hipMemsetAsync(s->d_diag, 0xFF, sizeof(int) * (size_t)N, st));
-    hipLaunchKernelGGL(k_cs_colptr, dim3(csc_grid(N + 1, kBlock)), dim3(kBlock), 0, st, cp, idx_bytes, idx_base, N, nnz, s->d_colptr, (unsigned *)misc);
-    CS_TRY(hipGetLastError());
-    CS_TRY(hipMemcpyAsync(host_misc, misc, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
-    CS_TRY(hipStreamSynchronize(st));
-    err = (unsigned)host_misc[0];
-    if (err & CS_BAD_COLPTR) { set_error("csc solver: colptr is not a monotone sequence from the index base to nnz + base"); return fail(FD_ERR_SHAPE); }
-    if (nnz > 0) {
-        hipLaunchKernelGGL(k_cs_entries, dim3(csc_grid(nnz, kBlock)), dim3(kBlock), 0, st, rv, idx_bytes, idx_base, (const int *)s->d_colptr, N, nnz,
-                           s->d_rowval, ecol, rcnt, s->d_diag, misc + 1, (unsigned *)misc);
-        CS_TRY(hipGetLastError());
-    }
-    CS_TRY(hipMemcpyAsync(host_misc, misc, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
-    CS_TRY(hipStreamSynchronize(st));
-    err = (unsigned)host_misc[0];
-    if (err & CS_BAD_ROW) { set_error("csc solver: rowval holds a row outside the %lld x %lld matrix", (long long)N, (long long)N); return fail(FD_ERR_SHAPE); }
-    if (err & CS_BAD_ORDER) { set_error("csc solver: the rows of a column are not strictly ascending"); return fail(FD_ERR_SHAPE); }
-    s->reach = host_misc[1];
-    // the LDS window of v only when the measured reach allows it: every column a tile's rows can name then lies inside the window;
-    // a wider pattern would stage 2 * kCsWinHalo elements per tile to serve the near-diagonal gathers alone
-    if (s->reach > kCsWinHalo) s->window = 0;
-    rc = csc_exscan(st, rcnt, N, s->d_row_ptr, bsum);
-    if (rc != FD_OK) return fail(rc);
-    CS_TRY(hipMemsetAsync(rcnt, 0, sizeof(int) * (size_t)N, st));
-    if (nnz > 0) {
-        hipLaunchKernelGGL(k_cs_fill, dim3(csc_grid(nnz, kBlock)), dim3(kBlock), 0, st, (const int *)s->d_rowval, nnz, (const int *)s->d_row_ptr, rcnt, s->d_row_slot);
-        CS_TRY(hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_cs_sort_short, dim3((unsigned)((N + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, (const int *)s->d_row_ptr, N, s->d_row_slot,
-                       (const int *)ecol, s->d_row_col, misc + 2);
-    hipLaunchKernelGGL(k_cs_order, dim3((unsigned)((N + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, (const int *)s->d_row_ptr, N, s->d_order);
-    CS_TRY(hipGetLastError());
-    CS_TRY(hipMemcpyAsync(host_misc, misc, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
-    CS_TRY(hipStreamSynchronize(st));
-    s->nlong = host_misc[2];
-    if (s->nlong > 0) {
-        CS_TRY(hipMalloc((void **)&s->d_long, sizeof(int) * (size_t)s->nlong));
-        CS_TRY(hipMalloc((void **)&tmp, sizeof(int) * (size_t)nz1));
-        hipLaunchKernelGGL(k_cs_list_long, dim3((unsigned)((N + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, (const int *)s->d_row_ptr, N, s->d_long, misc + 3);
-        hipLaunchKernelGGL(k_cs_sort_long, dim3((unsigned)s->nlong), dim3(kBlock), 0, st, (const int *)s->d_row_ptr, (const int *)s->d_long, s->d_row_slot, tmp,
-                           (const int *)ecol, s->d_row_col);
-        CS_TRY(hipGetLastError());
-    }
-    CS_TRY(hipMalloc((void **)&s->d_vec, sizeof(double) * 10 * (size_t)N));
-    CS_TRY(hipMalloc((void **)&s->d_part, sizeof(double) * (size_t)npart));
-    CS_TRY(hipMalloc((void **)&s->d_scal, sizeof(double) * S_NSCAL));
-    CS_TRY(hipMalloc((void **)&s->d_words, sizeof(int) * W_NWORDS));
-    CS_TRY(hipHostMalloc((void **)&s->h_rec, sizeof(CsRecord) * 2, hipHostMallocDefault));
-    CS_TRY(hipEventCreateWithFlags(&s->ev[0], hipEventDisableTiming));
-    CS_TRY(hipEventCreateWithFlags(&s->ev[1], hipEventDisableTiming));
-    CS_TRY(hipMemsetAsync(s->d_scal, 0, sizeof(double) * S_NSCAL, st));
-    CS_TRY(hipMemsetAsync(s->d_words, 0, sizeof(int) * W_NWORDS, st));
-    CS_TRY(hipStreamSynchronize(st));
-#undef CS_TRY
-    (void)fail(FD_OK);
     *out = s;
     return FD_OK;
 }
@@ -595,16 +440,13 @@ int fd_csc_solver_destroy(fd_csc_solver *s)
 int fd_csc_solver_set_options(fd_csc_solver *s, double rtol, int max_iterations)
 {
     FD_REQUIRE(s != nullptr, FD_ERR_ARG, "solver is NULL");
-    FD_REQUIRE(rtol >= 0.0 && rtol < 1.0, FD_ERR_ARG, "rtol = %g (0 <= rtol < 1)", rtol);
-    FD_REQUIRE(max_iterations >= 1, FD_ERR_ARG, "max_iterations = %d", max_iterations);
-    s->rtol = rtol; s->max_iterations = max_iterations;
-    return FD_OK;
+    return s->S.set_options(rtol, max_iterations);
 }
 
 int fd_csc_solver_set_policy(fd_csc_solver *s, int keep_unconverged)
 {
     FD_REQUIRE(s != nullptr, FD_ERR_ARG, "solver is NULL");
-    s->keep = keep_unconverged ? 1 : 0;
+    s->S.keep = keep_unconverged ? 1 : 0;
     return FD_OK;
 }
 
@@ -625,7 +467,7 @@ int fd_csc_solver_block_inverses(fd_csc_solver *s, const void **inv_dev, int64_t
     FD_REQUIRE(s != nullptr, FD_ERR_ARG, "solver is NULL");
     FD_REQUIRE(s->minv_bs > 0, FD_ERR_UNSUPPORTED, "no block-Jacobi solve has run on this solver");
     if (inv_dev) *inv_dev = s->d_minv;
-    if (nblocks) *nblocks = (s->N + s->minv_bs - 1) / s->minv_bs;
+    if (nblocks) *nblocks = (s->L.N + s->minv_bs - 1) / s->minv_bs;
     if (block_size) *block_size = s->minv_bs;
     return FD_OK;
 }
@@ -635,12 +477,12 @@ int fd_csc_solver_row_lists(fd_csc_solver *s, const void **row_ptr, const void *
                             int64_t *nnz_out, int64_t *long_rows_out)
 {
     FD_REQUIRE(s != nullptr, FD_ERR_ARG, "solver is NULL");
-    if (row_ptr) *row_ptr = s->d_row_ptr;
-    if (row_col) *row_col = s->d_row_col;
-    if (row_slot) *row_slot = s->d_row_slot;
-    if (diag_slot) *diag_slot = s->d_diag;
-    if (nnz_out) *nnz_out = s->nnz;
-    if (long_rows_out) *long_rows_out = s->nlong;
+    if (row_ptr) *row_ptr = s->L.row_ptr;
+    if (row_col) *row_col = s->L.row_col;
+    if (row_slot) *row_slot = s->L.row_slot;
+    if (diag_slot) *diag_slot = s->L.diag;
+    if (nnz_out) *nnz_out = s->L.nnz;
+    if (long_rows_out) *long_rows_out = s->L.nlong_r;
     return FD_OK;
 }
 
@@ -649,20 +491,20 @@ static void csc_product(fd_csc_solver *s, double alpha, double beta, const real_
 {
     hipStream_t st = s->ctx->stream;
     const CsPat P = csc_pat(s);
-    const int ntile = (int)((s->N + kBlock - 1) / kBlock);
-    if (s->nlong > 0)
-        hipLaunchKernelGGL((k_cs_long<TV>), dim3((unsigned)s->nlong), dim3(kBlock), 0, st, P, alpha, beta, nz, v, y, guarded ? (const int *)s->d_words : (const int *)nullptr);
+    const int ntile = (int)((s->L.N + kBlock - 1) / kBlock);
+    if (P.nlong > 0)
+        hipLaunchKernelGGL((k_cs_long<TV>), dim3((unsigned)P.nlong), dim3(kBlock), 0, st, P, alpha, beta, nz, v, y, guarded ? (const int *)s->S.d_words : (const int *)nullptr);
     hipLaunchKernelGGL((k_cs_rows<TV, MODE>), dim3(MODE == 0 ? fd_xcd_grid(ntile) : (unsigned)ntile), dim3(kBlock), csc_win_bytes(s, sizeof(TV)), st, P, alpha, beta,
-                       nz, v, y, c, s->d_scal, s->d_words, s->d_part);
+                       nz, v, y, c, s->S.d_scal, s->S.d_words, s->S.d_part);
 }
 
 int fd_csc_matvec_async(fd_csc_solver *s, double alpha, double beta, const void *nzval, const void *v, void *y, int transpose)
 {
-    FD_REQUIRE(s && v && y && (nzval || s->nnz == 0), FD_ERR_ARG, "NULL argument");
+    FD_REQUIRE(s && v && y && (nzval || s->L.nnz == 0), FD_ERR_ARG, "NULL argument");
     FD_REQUIRE(v != y, FD_ERR_ARG, "y must not be v");
     FD_HIP_CHECK(hipSetDevice(s->ctx->device));
     if (transpose) {
-        const int nb = (int)((s->N + kBlock - 1) / kBlock);
+        const int nb = (int)((s->L.N + kBlock - 1) / kBlock);
         hipLaunchKernelGGL(k_cs_cols, dim3(fd_xcd_grid(nb)), dim3(kBlock), 0, s->ctx->stream, csc_pat(s), alpha, beta, (const real_t *)nzval, (const real_t *)v, (real_t *)y);
     } else {
         csc_product<real_t, 0>(s, alpha, beta, (const real_t *)nzval, (const real_t *)v, (real_t *)y, nullptr, false);
@@ -673,10 +515,11 @@ int fd_csc_matvec_async(fd_csc_solver *s, double alpha, double beta, const void 
 
 int fd_csc_solve_async(fd_csc_solver *s, double alpha, double beta, const void *nzval, const void *b, void *y)
 {
-    FD_REQUIRE(s && b && y && (nzval || s->nnz == 0), FD_ERR_ARG, "NULL argument");
+    FD_REQUIRE(s && b && y && (nzval || s->L.nnz == 0), FD_ERR_ARG, "NULL argument");
     FD_HIP_CHECK(hipSetDevice(s->ctx->device));
     hipStream_t st = s->ctx->stream;
-    const int N = (int)s->N;
+    CscSolveState &S = s->S;
+    const int N = (int)s->L.N;
     const real_t *nz = (const real_t *)nzval;
     CsVecs V;
     double **vp[] = {&V.r, &V.rhat, &V.p, &V.v, &V.s, &V.t, &V.ph, &V.sh, &V.y, &V.d};
@@ -692,66 +535,48 @@ int fd_csc_solve_async(fd_csc_solver *s, double alpha, double beta, const void *
         if (e != hipSuccess) { (void)hipGetLastError(); FD_REQUIRE(false, FD_ERR_NOMEM, "block Jacobi: %d planes of %d doubles: %s", bs, N, hipGetErrorString(e)); }
         s->minv_cap = (size_t)bs * (size_t)N;
     }
-    FD_HIP_CHECK(hipMemsetAsync(s->d_words, 0, sizeof(int) * W_NWORDS, st));
+    FD_HIP_CHECK(hipMemsetAsync(S.d_words, 0, sizeof(int) * W_NWORDS, st));
     if (bs > 0) {
         const int nblk = (N + bs - 1) / bs;
-        hipLaunchKernelGGL(k_cs_init<1>, dim3(gv), dim3(kBlock), 0, st, P, V, alpha, beta, nz, (const real_t *)b, s->rtol, s->d_scal, s->d_words, s->d_part);
+        hipLaunchKernelGGL(k_cs_init<1>, dim3(gv), dim3(kBlock), 0, st, P, V, alpha, beta, nz, (const real_t *)b, S.rtol, S.d_scal, S.d_words, S.d_part);
         hipLaunchKernelGGL(k_cs_binv, dim3((unsigned)((nblk + kCsBinvWaves - 1) / kCsBinvWaves)), dim3(kCsBinvWaves * 64),
-                           sizeof(double) * (size_t)kCsBinvWaves * (size_t)(bs * (2 * bs + 1) + bs), st, P, bs, alpha, beta, nz, s->d_minv, s->d_words);
+                           sizeof(double) * (size_t)kCsBinvWaves * (size_t)(bs * (2 * bs + 1) + bs), st, P, bs, alpha, beta, nz, s->d_minv, S.d_words);
         s->minv_bs = bs;
     } else {
-        hipLaunchKernelGGL(k_cs_init<0>, dim3(gv), dim3(kBlock), 0, st, P, V, alpha, beta, nz, (const real_t *)b, s->rtol, s->d_scal, s->d_words, s->d_part);
+        hipLaunchKernelGGL(k_cs_init<0>, dim3(gv), dim3(kBlock), 0, st, P, V, alpha, beta, nz, (const real_t *)b, S.rtol, S.d_scal, S.d_words, S.d_part);
     }
-    // the iterations, in batches; the record of batch k is read while batch k + 1 is already enqueued (its kernels leave at once
-    // when the solve is done), so the device never waits for the host
-    int enq = 0, nb = 0;
-    bool stop = false;
-    while (!stop) {
-        const int todo = s->max_iterations - enq < s->batch ? s->max_iterations - enq : s->batch;
-        for (int it = 0; it < todo; ++it) {
-            if (bs > 0) {
-                hipLaunchKernelGGL(k_cs_p<1>, dim3(gv), dim3(kBlock), 0, st, N, V, (const double *)s->d_scal, (const int *)s->d_words);
-                hipLaunchKernelGGL(k_cs_bapply<0>, dim3(gv), dim3(kBlock), 0, st, N, bs, (const double *)s->d_minv, (const double *)V.p, V.ph, (const int *)s->d_words);
-            } else {
-                hipLaunchKernelGGL(k_cs_p<0>, dim3(gv), dim3(kBlock), 0, st, N, V, (const double *)s->d_scal, (const int *)s->d_words);
-            }
-            csc_product<double, 1>(s, alpha, beta, nz, V.ph, V.v, V.rhat, true);
-            if (bs > 0) {
-                hipLaunchKernelGGL(k_cs_s<1>, dim3(gv), dim3(kBlock), 0, st, N, V, s->d_scal, s->d_words, s->d_part);
-                hipLaunchKernelGGL(k_cs_bapply<1>, dim3(gv), dim3(kBlock), 0, st, N, bs, (const double *)s->d_minv, (const double *)V.s, V.sh, (const int *)s->d_words);
-            } else {
-                hipLaunchKernelGGL(k_cs_s<0>, dim3(gv), dim3(kBlock), 0, st, N, V, s->d_scal, s->d_words, s->d_part);
-            }
-            csc_product<double, 2>(s, alpha, beta, nz, V.sh, V.t, V.s, true);
-            hipLaunchKernelGGL(k_cs_update, dim3(gv), dim3(kBlock), 0, st, N, V, s->d_scal, s->d_words, s->d_part);
+    const int rc = S.run(st, [&] {      // one iteration: 5 launches (+ 2 with long rows, + 2 with block Jacobi)
+        if (bs > 0) {
+            hipLaunchKernelGGL(k_cs_p<1>, dim3(gv), dim3(kBlock), 0, st, N, V, (const double *)S.d_scal, (const int *)S.d_words);
+            hipLaunchKernelGGL(k_cs_bapply<0>, dim3(gv), dim3(kBlock), 0, st, N, bs, (const double *)s->d_minv, (const double *)V.p, V.ph, (const int *)S.d_words);
+        } else {
+            hipLaunchKernelGGL(k_cs_p<0>, dim3(gv), dim3(kBlock), 0, st, N, V, (const double *)S.d_scal, (const int *)S.d_words);
         }
-        enq += todo;
-        FD_HIP_CHECK(hipGetLastError());
-        FD_HIP_CHECK(hipMemcpyAsync(&s->h_rec[nb & 1], s->d_words, sizeof(CsRecord), hipMemcpyDeviceToHost, st));
-        FD_HIP_CHECK(hipEventRecord(s->ev[nb & 1], st));
-        if (nb >= 1) {
-            FD_HIP_CHECK(hipEventSynchronize(s->ev[(nb - 1) & 1]));
-            stop = s->h_rec[(nb - 1) & 1].done != 0;
+        csc_product<double, 1>(s, alpha, beta, nz, V.ph, V.v, V.rhat, true);
+        if (bs > 0) {
+            hipLaunchKernelGGL(k_cs_s<1>, dim3(gv), dim3(kBlock), 0, st, N, V, S.d_scal, S.d_words, S.d_part);
+            hipLaunchKernelGGL(k_cs_bapply<1>, dim3(gv), dim3(kBlock), 0, st, N, bs, (const double *)s->d_minv, (const double *)V.s, V.sh, (const int *)S.d_words);
+        } else {
+            hipLaunchKernelGGL(k_cs_s<0>, dim3(gv), dim3(kBlock), 0, st, N, V, S.d_scal, S.d_words, S.d_part);
         }
-        ++nb;
-        if (enq >= s->max_iterations) stop = true;
-    }
-    hipLaunchKernelGGL(k_cs_final, dim3((unsigned)((N + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, N, (const double *)V.y, (real_t *)y, s->d_words, s->keep);
+        csc_product<double, 2>(s, alpha, beta, nz, V.sh, V.t, V.s, true);
+        hipLaunchKernelGGL(k_cs_update, dim3(gv), dim3(kBlock), 0, st, N, V, S.d_scal, S.d_words, S.d_part);
+    });
+    if (rc != FD_OK) return rc;
+    hipLaunchKernelGGL(k_cs_final, dim3((unsigned)((N + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, N, (const double *)V.y, (real_t *)y, S.d_words, S.keep);
     FD_HIP_CHECK(hipGetLastError());
-    s->solved = true;
+    S.solved = true;
     return FD_OK;
 }
 
 int fd_csc_solver_status(fd_csc_solver *s, int *flags_out, int64_t *iterations_out, double *resid_out, double *bnorm_out)
 {
     FD_REQUIRE(s != nullptr, FD_ERR_ARG, "solver is NULL");
-    FD_HIP_CHECK(hipSetDevice(s->ctx->device));
-    FD_HIP_CHECK(hipStreamSynchronize(s->ctx->stream));
     int w[W_NWORDS];
     double sc[S_NSCAL];
-    FD_HIP_CHECK(hipMemcpy(w, s->d_words, sizeof w, hipMemcpyDeviceToHost));
-    FD_HIP_CHECK(hipMemcpy(sc, s->d_scal, sizeof sc, hipMemcpyDeviceToHost));
-    if (flags_out) *flags_out = s->solved ? w[W_FINAL] : 0;
+    const int rc = s->S.read_status(s->ctx, w, sc);
+    if (rc != FD_OK) return rc;
+    if (flags_out) *flags_out = w[W_FINAL];
     if (iterations_out) *iterations_out = w[W_ITERS];
     if (resid_out) *resid_out = std::sqrt(sc[S_RNORM2]);
     if (bnorm_out) *bnorm_out = std::sqrt(sc[S_BNORM2]);

@@ -66,6 +66,57 @@ def test_lists_equal_the_model(idx, base, device):
         _check_lists(_lsq(colptr, rowval, M, N, idx=idx, base=base, device=device), rl)
 
 
+def shared_builder_case():
+    """One SQUARE pattern for both consumers of the shared builder: N = 300 (two tiles of 256 rows), row 137 and column 201 of 40 entries
+    (> 32: long), row 50 and column 60 empty, no diagonal entry in column 100.  The numpy models alone already agree on it (asserted)."""
+    if "shared" not in _odd:
+        N, long_row, long_col, empty_row, empty_col, no_diag = 300, 137, 201, 50, 60, 100
+        entries = {(r, j) for j in range(N) for r in (j - 1, j, j + 2) if 0 <= r < N and r != long_row and j != long_col}
+        entries |= {(long_row, 5 + 7 * k) for k in range(40)} | {(4 + 7 * k, long_col) for k in range(40)}      # (they share (137, 201))
+        entries = sorted((j, r) for r, j in entries if r != empty_row and j != empty_col and (r, j) != (no_diag, no_diag))
+        cols, rowval = np.array([e[0] for e in entries]), np.array([e[1] for e in entries], dtype=np.int64)
+        colptr = np.concatenate([[0], np.cumsum(np.bincount(cols, minlength=N))]).astype(np.int64)
+        sq, rect = SM.RowLists(colptr, rowval, N), LM.RectLists(colptr, rowval, N, N)
+        for name in ("row_ptr", "row_col", "row_slot"):
+            assert np.array_equal(getattr(sq, name), getattr(rect, name))
+        assert sq.nlong == rect.nlong == 1 and sq.lens[long_row] == 40 and sq.lens[empty_row] == 0
+        assert rect.long_cols.tolist() == [long_col] and rect.col_lens[long_col] == 40 and rect.col_lens[empty_col] == 0
+        assert sq.diag[no_diag] == -1 and rect.col_lens[no_diag] > 0 and (sq.diag >= 0).sum() == N - 5      # (and 50, 60, 137, 201)
+        _odd["shared"] = (colptr, rowval, N, sq, rect)
+    return _odd["shared"]
+
+
+@pytest.mark.parametrize("idx,base,device,dtype", [
+    (np.int32, 0, False, np.float64), (np.int32, 0, True, np.float64), (np.int32, 1, False, np.float64), (np.int32, 1, True, np.float32),
+    (np.int64, 0, False, np.float64), (np.int64, 0, True, np.float64), (np.int64, 1, False, np.float64), (np.int64, 1, True, np.float64)])
+def test_both_consumers_get_the_same_lists_from_the_shared_builder(idx, base, device, dtype):
+    colptr, rowval, N, sq, rect = shared_builder_case()
+    cp, rv = (colptr + base).astype(idx), (rowval + base).astype(idx)
+    if device:
+        cp, rv = _dev(cp), _dev(rv)
+    solver = fd.CscSolver((cp, rv, N), dtype=dtype, idx_base=base)
+    lsq = fd.CscLeastSquares((cp, rv, N, N), dtype=dtype, idx_base=base)
+    s_ptr, s_col, s_slot, s_diag, s_nlong = solver.row_lists()
+    l_ptr, l_col, l_slot, l_nlong = lsq.row_lists()
+    for got_s, got_l, name in ((s_ptr, l_ptr, "row_ptr"), (s_col, l_col, "row_col"), (s_slot, l_slot, "row_slot")):
+        assert torch.equal(got_s, got_l), name
+        assert np.array_equal(got_s.cpu().numpy(), getattr(sq, name)) and np.array_equal(got_l.cpu().numpy(), getattr(rect, name)), name
+    assert np.array_equal(s_diag.cpu().numpy(), sq.diag) and int(s_diag[100]) == -1
+    assert s_nlong == 1 and l_nlong == 1
+    assert lsq.long_columns().cpu().numpy().tolist() == [201]
+    rng = np.random.default_rng(33)
+    nz, v = rng.uniform(-1, 1, rowval.size).astype(dtype), rng.uniform(-1, 1, N).astype(dtype)
+    Jd, vd = _dev(nz), _dev(v)
+    for transpose in (False, True):
+        y = torch.full((N,), float("nan"), dtype=Jd.dtype, device="cuda")
+        solver.matvec(Jd, vd, y, 0.5, -1.25, transpose=transpose)
+        want = (SM.matvec_t if transpose else SM.matvec)(sq, 0.5, -1.25, nz, v)
+        assert _same_bits(y.cpu().numpy(), want), ("solver", transpose)
+        y = torch.full((N,), float("nan"), dtype=Jd.dtype, device="cuda")
+        lsq.matvec(Jd, vd, y, transpose=transpose)
+        assert _same_bits(y.cpu().numpy(), LM.matvec(rect, nz, v, transpose)), ("lsq", transpose)
+
+
 def test_a_bad_pattern_is_an_error_not_a_fault():
     colptr, rowval, nz, M, N, b, rl = odd_case()
     assert M < N

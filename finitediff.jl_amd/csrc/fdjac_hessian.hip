@@ -381,9 +381,10 @@ int fd_hessian_async(fd_hess_plan *p, fd_objective *o, const void *x, double rel
 {
     if (int rc = require_device()) return rc;
     if (int rc = check_pair(p, o)) return rc;
-    FD_REQUIRE(x && H, FD_ERR_ARG, "NULL x or H");
+    FD_REQUIRE(x, FD_ERR_ARG, "NULL x or H");
     FD_HIP_CHECK(hipSetDevice(p->ctx->device));
     if (int rc = build_pattern(p)) return rc;
+    FD_REQUIRE(H || hess_out_len(p) == 0, FD_ERR_ARG, "NULL x or H");      // (a CSC destination of no entries has no address)
     if (!(relstep > 0)) relstep = 0x1p-13;                       // default_relstep(Val(:hcentral), Float64) = eps(Float64)^(1/4)
     if (absstep < 0) absstep = relstep;
     hipStream_t s = p->ctx->stream;
@@ -415,10 +416,11 @@ int fd_hessian(fd_hess_plan *p, fd_objective *o, const void *x, int x_kind, doub
 {
     if (int rc = require_device()) return rc;
     if (int rc = check_pair(p, o)) return rc;
-    FD_REQUIRE(x && H, FD_ERR_ARG, "NULL x or H");
+    FD_REQUIRE(x, FD_ERR_ARG, "NULL x or H");
     FD_REQUIRE((x_kind == FD_HOST || x_kind == FD_DEVICE) && (out_kind == FD_HOST || out_kind == FD_DEVICE), FD_ERR_ARG, "bad memory kind");
     FD_HIP_CHECK(hipSetDevice(p->ctx->device));
     if (int rc = build_pattern(p)) return rc;
+    FD_REQUIRE(H || hess_out_len(p) == 0, FD_ERR_ARG, "NULL x or H");
     hipStream_t s = p->ctx->stream;
     const void *xd = x;
     if (x_kind == FD_HOST) {
@@ -435,7 +437,7 @@ int fd_hessian(fd_hess_plan *p, fd_objective *o, const void *x, int x_kind, doub
         Hd = p->d_outstage;
     }
     if (int rc = fd_hessian_async(p, o, xd, relstep, absstep, Hd)) return rc;
-    if (out_kind == FD_HOST) FD_HIP_CHECK(hipMemcpyAsync(H, Hd, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (out_kind == FD_HOST && n > 0) FD_HIP_CHECK(hipMemcpyAsync(H, Hd, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
     FD_HIP_CHECK(hipStreamSynchronize(s));
     return FD_OK;
 }

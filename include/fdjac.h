@@ -873,6 +873,7 @@ const char *fd_f_compile_log(void);
  *                          ONE of the entry pass (a lane per upper entry of P, both slots stored).  e_i = max(relstep |x_i|, absstep)
  *                          serves the diagonal and the off-diagonal entries; i < j always differences (i, j) and mirrors it (the
  *                          formula is not bit-symmetric; the reference mirrors the upper triangle).  Sums over rows ascend in r.
+ *                          No row reads anything: no launch, H = +0.0 -- a FD_HESS_CSC destination then has no entries and H may be NULL.
  *   fd_gradient_async      fdtype FD_FORWARD (e_j = max(relstep |x_j|, absstep) * dir, relstep <= 0: sqrt(eps)): the rows pass + ONE
  *                          launch, a lane per column; FD_CENTRAL (dir ignored, relstep <= 0: cbrt(eps)): that launch alone.
  *                          FD_COMPLEX: FD_ERR_UNSUPPORTED.  A column no row touches has the empty sum +0.0 before the division.

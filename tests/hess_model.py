@@ -17,9 +17,12 @@ FWD_RELSTEP = float(np.sqrt(np.finfo(np.float64).eps))
 CEN_RELSTEP = float(np.cbrt(np.finfo(np.float64).eps))
 
 
-def step(x, relstep, absstep):
-    """max(relstep * |x|, absstep) with Julia's max: a NaN on either side is the result (src/epsilons.jl:74-77)."""
-    a = np.float64(relstep) * np.abs(x)
+def step(x, relstep, absstep, fault=None):
+    """max(relstep * |x|, absstep) with Julia's max: a NaN on either side is the result (src/epsilons.jl:74-77).
+    (fault: a perturbed model of tests/test_hessian_cpu.py -- "fmax": C's fmax, which drops a NaN; "no_abs": relstep * x.)"""
+    a = np.float64(relstep) * (np.asarray(x, np.float64) if fault == "no_abs" else np.abs(x))
+    if fault == "fmax":
+        return np.fmax(a, np.float64(absstep))
     return np.where((a > absstep) | (a != a), a, np.float64(absstep))
 
 
@@ -42,11 +45,15 @@ def support(M, N, colptr=None, rowval=None):
     return np.array(cp, np.int64), np.array(rv, np.int64)
 
 
-def _point(x, ii, jj, vi, vj):
-    """the lanes' points: x with coordinate ii -> vi, then jj -> vj (jj overrides ii when equal), as fd_pair_point"""
+def _point(x, ii, jj, vi, vj, fault=None):
+    """the lanes' points: x with coordinate ii -> vi, then jj -> vj (jj overrides ii when equal), as fd_pair_point
+    (fault "vi_over_vj": ii overrides jj)"""
     def get(k):
         k = np.asarray(k, np.int64)
         v = x[k]
+        if fault == "vi_over_vj":
+            v = np.where(k == jj, vj, v)
+            return np.where(k == ii, vi, v)
         v = np.where(k == ii, vi, v)
         return np.where(k == jj, vj, v)
     return get
@@ -70,12 +77,27 @@ def _row_triples(M, N, cp, rv):
     return r[o], i[o], j[o]
 
 
-def hessian_entries(phi, x, M, N, colptr=None, rowval=None, relstep=None, absstep=None):
-    """The contract's upper entries of P: (i, j, H_ij), i <= j, sorted by (j, i)."""
+FAULTS = ("desc_rows", "four_last", "diag_assoc", "fmax", "no_abs", "dir_quot", "vi_over_vj", "diag_empty")
+
+
+def hessian_entries(phi, x, M, N, colptr=None, rowval=None, relstep=None, absstep=None, fault=None):
+    """The contract's upper entries of P: (i, j, H_ij), i <= j, sorted by (j, i).  fault: None, or one of FAULTS -- the model perturbed
+    in one place, to count the cases that would notice (tests/test_hessian_cpu.py); "desc_rows": every sum in descending r;
+    "four_last": 4 (e_i e_j); "diag_assoc": (phi+ + phi-) - 2 phi; "diag_empty": a diagonal entry (an empty sum) for a column no row
+    reads; "fmax" / "no_abs": see step; "vi_over_vj": see _point; "dir_quot" is the gradient's."""
     relstep, absstep = _defaults(relstep, absstep, HESS_RELSTEP)
     x = np.asarray(x, np.float64)
     cp, rv = support(M, N, colptr, rowval)
-    fx = phi(np.arange(M, dtype=np.int64), _point(x, -1, -1, 0.0, 0.0))
+    _pt = _point if fault != "vi_over_vj" else (lambda *a: _point(*a, fault=fault))
+    if fault == "diag_empty":
+        fi, fj, h = hessian_entries(phi, x, M, N, cp, rv, relstep, absstep)
+        unread = np.flatnonzero(np.diff(cp) == 0)
+        e = step(x[unread], relstep, absstep)
+        with np.errstate(all="ignore"):
+            fi, fj, h = np.concatenate([fi, unread]), np.concatenate([fj, unread]), np.concatenate([h, np.zeros(unread.size) / (e * e)])
+        o = np.lexsort((fi, fj))
+        return fi[o], fj[o], h[o]
+    fx = phi(np.arange(M, dtype=np.int64), _pt(x, -1, -1, 0.0, 0.0))
     r, i, j = _row_triples(M, N, cp, rv)
     if r.size == 0:
         return np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0)
@@ -83,7 +105,9 @@ def hessian_entries(phi, x, M, N, colptr=None, rowval=None, relstep=None, absste
     new[1:] = (i[1:] != i[:-1]) | (j[1:] != j[:-1])
     ent = np.cumsum(new) - 1                     # entry of every triple
     pos = np.arange(r.size) - np.flatnonzero(new)[ent]      # its place in the entry's ascending row list
-    ei_all = step(x, relstep, absstep)
+    if fault == "desc_rows":
+        pos = (np.bincount(ent)[ent] - 1) - pos
+    ei_all = step(x, relstep, absstep, fault)
     ei, ej = ei_all[i], ei_all[j]
     xi, xj = x[i], x[j]
     xip, xim, xjp, xjm = xi + ei, xi - ei, xj + ej, xj - ej
@@ -91,16 +115,16 @@ def hessian_entries(phi, x, M, N, colptr=None, rowval=None, relstep=None, absste
     t = np.empty(r.size)
     if diag.any():
         d = diag
-        fp = phi(r[d], _point(x, i[d], i[d], xip[d], xip[d]))
-        fm = phi(r[d], _point(x, i[d], i[d], xim[d], xim[d]))
-        t[d] = (fp - 2.0 * fx[r[d]]) + fm
+        fp = phi(r[d], _pt(x, i[d], i[d], xip[d], xip[d]))
+        fm = phi(r[d], _pt(x, i[d], i[d], xim[d], xim[d]))
+        t[d] = (fp - 2.0 * fx[r[d]]) + fm if fault != "diag_assoc" else (fp + fm) - 2.0 * fx[r[d]]
     if (~diag).any():
         o = ~diag
         a, b = i[o], j[o]
-        pp = phi(r[o], _point(x, a, b, xip[o], xjp[o]))
-        pm = phi(r[o], _point(x, a, b, xip[o], xjm[o]))
-        mp = phi(r[o], _point(x, a, b, xim[o], xjp[o]))
-        mm = phi(r[o], _point(x, a, b, xim[o], xjm[o]))
+        pp = phi(r[o], _pt(x, a, b, xip[o], xjp[o]))
+        pm = phi(r[o], _pt(x, a, b, xip[o], xjm[o]))
+        mp = phi(r[o], _pt(x, a, b, xim[o], xjp[o]))
+        mm = phi(r[o], _pt(x, a, b, xim[o], xjm[o]))
         t[o] = ((pp - pm) - mp) + mm
     nent = int(ent[-1]) + 1
     s = np.zeros(nent)
@@ -110,7 +134,7 @@ def hessian_entries(phi, x, M, N, colptr=None, rowval=None, relstep=None, absste
     fi, fj = i[new], j[new]
     e_i, e_j = ei_all[fi], ei_all[fj]
     with np.errstate(all="ignore"):
-        h = np.where(fi == fj, s / (e_i * e_i), s / ((4.0 * e_i) * e_j))
+        h = np.where(fi == fj, s / (e_i * e_i), s / ((4.0 * e_i) * e_j if fault != "four_last" else 4.0 * (e_i * e_j)))
     return fi, fj, h
 
 
@@ -125,17 +149,21 @@ def hessian(phi, x, M, N, colptr=None, rowval=None, relstep=None, absstep=None):
     return H, mask
 
 
-def gradient(phi, x, M, N, fdtype, colptr=None, rowval=None, relstep=None, absstep=None, dir=1.0):
-    """The contract's gradient: forward (step times dir) or central, per-row differences summed in ascending r (empty: +0.0)."""
+def gradient(phi, x, M, N, fdtype, colptr=None, rowval=None, relstep=None, absstep=None, dir=1.0, fault=None):
+    """The contract's gradient: forward (step times dir) or central, per-row differences summed in ascending r (empty: +0.0).
+    A column no row reads holds +0.0 / e: -0.0 forward with dir = -1, NaN where e is NaN or 0.  fault: as hessian_entries;
+    "dir_quot": dir multiplies the forward quotient, not the step."""
     relstep, absstep = _defaults(relstep, absstep, FWD_RELSTEP if fdtype == "forward" else CEN_RELSTEP)
     x = np.asarray(x, np.float64)
     cp, rv = support(M, N, colptr, rowval)
-    e = step(x, relstep, absstep)
-    if fdtype == "forward":
+    e = step(x, relstep, absstep, fault)
+    if fdtype == "forward" and fault != "dir_quot":
         e = e * np.float64(dir)
     j = np.repeat(np.arange(N, dtype=np.int64), np.diff(cp))
     r = rv
     pos = np.arange(r.size) - cp[j]
+    if fault == "desc_rows":
+        pos = (np.diff(cp)[j] - 1) - pos
     xp, xm = x[j] + e[j], x[j] - e[j]
     fp = phi(r, _point(x, j, j, xp, xp))
     if fdtype == "forward":
@@ -148,6 +176,8 @@ def gradient(phi, x, M, N, fdtype, colptr=None, rowval=None, relstep=None, absst
         sel = pos == p
         s[j[sel]] = t[sel] if p == 0 else s[j[sel]] + t[sel]
     with np.errstate(all="ignore"):
+        if fdtype == "forward" and fault == "dir_quot":
+            return (s / e) * np.float64(dir)
         return s / e if fdtype == "forward" else s / (2.0 * e)
 
 
@@ -373,6 +403,55 @@ def randrows_support(M, N, ncols):
             cols[c].append(r)
     colptr = np.concatenate([[0], np.cumsum([len(c) for c in cols])]).astype(np.int64)
     return colptr, np.array([r for c in cols for r in c], np.int64)
+
+
+# any support, given as DATA: the functor holds S by rows (row_ptr int64, row_col int32 ascending per row, both on the device); row r
+# with columns c_0 < ... < c_{L-1} is the left-to-right sum over t of (a b + 0.5 a a) / (2 + b b), a = X(c_t), b = X(c_{(t+1) mod L});
+# L = 0: +0.0.  Only + - * /, so numpy restates it exactly.  params = the two pointers; one source, one compilation for every pattern.
+LISTROWS_SRC = r"""
+struct ListRows {
+    const long long *rp;
+    const int *rc;
+    template <class P> __device__ real_t operator()(long long r, const P &X) const
+    {
+        const long long q0 = rp[r], L = rp[r + 1] - q0;
+        real_t s = 0;
+        for (long long t = 0; t < L; ++t) {
+            const real_t a = X(rc[q0 + t]), b = X(rc[q0 + (t + 1 < L ? t + 1 : 0)]);
+            s = s + (a * b + 0.5 * a * a) / (2.0 + b * b);
+        }
+        return s;
+    }
+};
+"""
+
+
+def rows_of(M, N, colptr, rowval):
+    """S by rows, (row_ptr int64 [M + 1], row_col int32, columns ascending per row), from 0-based CSC with unique rows per column"""
+    colptr, rowval = np.asarray(colptr, np.int64), np.asarray(rowval, np.int64)
+    cols = np.repeat(np.arange(N, dtype=np.int64), np.diff(colptr))
+    order = np.lexsort((cols, rowval))
+    rp = np.zeros(M + 1, np.int64)
+    np.add.at(rp, rowval + 1, 1)
+    return np.cumsum(rp), cols[order].astype(np.int32)
+
+
+def phi_listrows(row_ptr, row_col):
+    rp, rc = np.asarray(row_ptr, np.int64), np.asarray(row_col, np.int64)
+
+    def phi(r, get):
+        r = np.asarray(r, np.int64)
+        q0 = rp[r]
+        L = rp[r + 1] - q0
+        s = np.zeros(r.shape)
+        with np.errstate(all="ignore"):
+            for t in range(int(L.max()) if r.size else 0):
+                on = t < L
+                t1 = np.where(t + 1 < L, t + 1, 0)
+                a, b = get(rc[np.where(on, q0 + t, 0)]), get(rc[np.where(on, q0 + t1, 0)])
+                s = np.where(on, s + (a * b + 0.5 * a * a) / (2.0 + b * b), s)
+        return s
+    return phi
 
 
 # the reference's own test objectives (tests/golden/hessian_known_answers.json): per = 0: M = 1, f itself; per = 1: M = n, one

@@ -585,8 +585,8 @@ class BandedSolver:
 
 
 class _CscConsumer:
-    """What CscSolver and CscLeastSquares share: the marshalling of a pattern's indices and the calls that differ only in the C prefix."""
-    _prefix = None      # "fd_csc_solver" / "fd_csc_lsq": <prefix>_create, _destroy, _set_options, _set_policy
+    """What CscSolver, CscLeastSquares and CscTrustRegion share: the marshalling of a pattern's indices and the calls that differ only in the C prefix."""
+    _prefix = None      # "fd_csc_solver" / "fd_csc_lsq" / "fd_csc_tr": <prefix>_create, _destroy, _set_options, _set_policy
     _noun = None        # in "the <noun> takes device arrays"
 
     def _create(self, pattern, ctx, dtype, idx_base, square):
@@ -753,6 +753,44 @@ class CscLeastSquares(_CscConsumer):
         _l.check(self.Lt.fd_csc_lsq_long_columns(self.handle, C.byref(p), C.byref(n)))
         self.ctx.synchronize()
         return self._ints(p.value, n.value)
+
+
+class CscTrustRegion(_CscConsumer):
+    """fd_csc_tr: the trust-region consumer.  For a symmetric H (N x N, both triangles stored) in ``SparseMatrixCSC`` storage -- the nzval a
+    ``HessianCache`` with ``dest="csc"`` has just written, left on the device -- ``matvec`` enqueues y = (H + lam*I) v and ``step`` enqueues
+    the Steihaug-Toint truncated-CG solution of min g.y + 1/2 y.(H + lam*I) y, ||y||_W <= radius, W = I (``norm="I"``) or diag(|H_jj| + lam)
+    (``norm="diag"``, which also preconditions), whose scalars never leave the device.  ``pattern`` is a ``SparseMatrixCSC`` /
+    ``DevicePatternCSC`` or ``(colptr, rowval, N)`` with numpy arrays or CUDA tensors of int32 / int64 (``idx_base``-based).  Symmetric
+    values are the caller's contract.  Float64 only.  A step that does not finish within ``max_iterations`` (``status()`` flags bit 0) or
+    breaks down (bit 1) fills y and r_out with NaN unless ``set_policy(True)``; a step that ends on the boundary is a success."""
+
+    NORMS = {"I": 0, "diag": 1}
+
+    _prefix, _noun = "fd_csc_tr", "consumer"
+
+    def __init__(self, pattern, ctx=None, idx_base=1):
+        _M, self.N = self._create(pattern, ctx, np.float64, idx_base, square=True)
+
+    def matvec(self, H, v, y, lam=0.0):
+        """Enqueue y = (H + lam*I) v on the context's stream (fd_csc_tr_matvec_async)."""
+        _l.check(self.Lt.fd_csc_tr_matvec_async(self.handle, float(lam), self._vals(H), self._dev(v, "v"), self._dev(y, "y")))
+
+    def step(self, nzval, g, y, radius, lam=0.0, norm="I", r_out=None):
+        """Enqueue the trust-region step into y on the context's stream (fd_csc_tr_step_async); ``radius`` > 0 or ``float("inf")``;
+        ``r_out`` (N elements) receives the recurred model gradient g + (H + lam*I) y."""
+        kind = self.NORMS.get(norm, norm)
+        _l.check(self.Lt.fd_csc_tr_step_async(self.handle, float(lam), float(radius), int(kind), self._vals(nzval), self._dev(g, "g"),
+                                              self._dev(y, "y"), None if r_out is None else self._dev(r_out, "r_out")))
+
+    def status(self):
+        """Synchronises.  {"flags": bit 0 the iterations ran out | bit 1 breakdown, "exit": 0 inside / 1 boundary / 2 negative curvature
+        to the boundary / 3 negative curvature without a boundary, "iterations", "resid": the recurred ||g + (H + lam*I) y||_2,
+        "g_norm": ||g||_2, "step_norm": ||y||_W, "pred": -q(y)}."""
+        f, e, it = C.c_int(), C.c_int(), C.c_int64()
+        r, gn, sn, pr = C.c_double(), C.c_double(), C.c_double(), C.c_double()
+        _l.check(self.Lt.fd_csc_tr_status(self.handle, C.byref(f), C.byref(e), C.byref(it), C.byref(r), C.byref(gn), C.byref(sn), C.byref(pr)))
+        return {"flags": f.value, "exit": e.value, "iterations": it.value, "resid": r.value, "g_norm": gn.value, "step_norm": sn.value,
+                "pred": pr.value}
 
 
 class BlockTridiagSolver:

@@ -1,8 +1,8 @@
-// Shared by the consumers on SparseMatrixCSC storage (fdjac_cscsolve.hip, fdjac_csclsq.hip).  CREATE lives in fdjac_csc_pattern.hip: it
+// Shared by the consumers on SparseMatrixCSC storage (fdjac_cscsolve.hip, fdjac_csclsq.hip, fdjac_csctr.hip).  CREATE lives in fdjac_csc_pattern.hip: it
 // touches indices only, so it is compiled once, with the Float64 build, and both element builds call it through the declarations below
 // (CscLists, csc_lists_build, csc_lists_free).  Here: the constants, the device helpers of the iteration kernels (index loads, the ordered
 // sums block_sum and the ticket that lets the last-arriving workgroup finish a dot, the breakdown store) and CscSolveState, the host
-// side of a solve that both consumers share: its device words and scalars, the batch loop and the status read-back.
+// side of a solve that the consumers share: its device words and scalars, the batch loop and the status read-back.
 #pragma once
 #include "fdjac_internal.h"
 #include "fdjac_device.h"

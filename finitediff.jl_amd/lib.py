@@ -85,6 +85,7 @@ EXPORTS = (
     "fd_csc_solver_create", "fd_csc_solver_destroy", "fd_csc_matvec_async", "fd_csc_solver_set_options", "fd_csc_solver_set_policy", "fd_csc_solve_async", "fd_csc_solver_status", "fd_csc_solver_row_lists",
     "fd_csc_solver_set_preconditioner", "fd_csc_solver_block_inverses",
     "fd_csc_lsq_create", "fd_csc_lsq_destroy", "fd_csc_lsq_matvec_async", "fd_csc_lsq_set_options", "fd_csc_lsq_set_policy", "fd_csc_lsq_solve_async", "fd_csc_lsq_status", "fd_csc_lsq_row_lists", "fd_csc_lsq_long_columns",
+    "fd_csc_tr_create", "fd_csc_tr_destroy", "fd_csc_tr_set_options", "fd_csc_tr_set_policy", "fd_csc_tr_matvec_async", "fd_csc_tr_step_async", "fd_csc_tr_status",
     "fd_objective_compile", "fd_objective_destroy", "fd_objective_counts", "fd_hess_plan_create", "fd_hess_plan_destroy",
     "fd_hess_plan_info", "fd_hess_plan_pattern", "fd_hessian_async", "fd_hessian", "fd_gradient_async", "fd_gradient",
 )
@@ -300,6 +301,13 @@ def load():
     L.fd_csc_lsq_status.argtypes = [vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(dbl), C.POINTER(dbl)]
     L.fd_csc_lsq_row_lists.argtypes = [vp, pp, pp, pp, C.POINTER(i64), C.POINTER(i64)]
     L.fd_csc_lsq_long_columns.argtypes = [vp, pp, C.POINTER(i64)]
+    L.fd_csc_tr_create.argtypes = [vp, i64, vp, vp, i32, i32, i32, pp]
+    L.fd_csc_tr_destroy.argtypes = [vp]
+    L.fd_csc_tr_set_options.argtypes = [vp, dbl, i32]
+    L.fd_csc_tr_set_policy.argtypes = [vp, i32]
+    L.fd_csc_tr_matvec_async.argtypes = [vp, dbl, vp, vp, vp]
+    L.fd_csc_tr_step_async.argtypes = [vp, dbl, dbl, i32, vp, vp, vp, vp]
+    L.fd_csc_tr_status.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64), C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl)]
     L.fd_tridiag_solver_create.argtypes = [vp, i64, i64, i64, i32, pp]
     L.fd_tridiag_solver_destroy.argtypes = [vp]
     L.fd_tridiag_solver_status.argtypes = [vp, C.POINTER(i32)]

@@ -787,6 +787,47 @@ int fd_csc_lsq_row_lists(fd_csc_lsq *lsq, const void **row_ptr, const void **row
                          int64_t *long_rows_out);
 int fd_csc_lsq_long_columns(fd_csc_lsq *lsq, const void **long_cols, int64_t *count_out);
 
+/* ---- the TRUST-REGION consumer: (H + lambda I) v and the Steihaug-Toint step for a SYMMETRIC H (N x N) in SparseMatrixCSC storage ----
+ * The pattern is that of a Hessian plan's CSC destination (fd_hess_plan_pattern): BOTH triangles stored; colptr (N + 1) and rowval (nnz),
+ * Int32 or Int64, base 0 or 1, on the host or on the device, exactly as fd_csc_solver_create takes them and validated in the same way (a
+ * bad pattern is FD_ERR_SHAPE).  Symmetry is NOT checked: symmetric values are the caller's contract (fd_hessian_async writes them so).
+ * nzval, v, g, y and r_out are DEVICE arrays of Float64: there is no Float32 build of this consumer, as there is none of the Hessian.
+ *   fd_csc_tr_matvec_async   y = (H + lambda I) v, row-wise, no atomics; y must not be v.  Defined summation orders.
+ *   fd_csc_tr_step_async     approximately  min q(y) = g.y + 1/2 y.(H + lambda I) y  subject to  ||y||_W <= radius  by the Steihaug-Toint
+ *                         truncated conjugate-gradient method from y0 = 0: W = I (FD_CSC_TR_NORM_IDENTITY, no preconditioner) or
+ *                         W = diag(m), m_j = |H_jj| + lambda (FD_CSC_TR_NORM_DIAG; the same m preconditions the iteration),
+ *                         ||y||_W^2 = sum w_j y_j^2.  It stops inside the region once ||g + (H + lambda I) y||_2 <= rtol * ||g||_2
+ *                         (fd_csc_tr_set_options: rtol, default 1e-10; max_iterations, default 500), on the boundary when the next
+ *                         iterate would leave the region, or on the boundary along a direction of non-positive curvature.  Every scalar
+ *                         stays on the device; the iterations are enqueued in batches and the call waits only for one 16-byte record per
+ *                         batch, one batch behind the device.  g = 0: y = 0, no iteration.  radius = +Inf (or radius^2 = +Inf in
+ *                         Float64): no boundary.  r_out may be NULL; otherwise it receives the recurred model gradient
+ *                         g + (H + lambda I) y.  y or r_out may be g.  lambda < 0 or not finite, radius <= 0 or NaN, another norm_kind,
+ *                         or a NULL nzval, g or y is FD_ERR_ARG, and nothing is launched.
+ *   fd_csc_tr_status      synchronises.  flags bit 0: the iterations ran out; bit 1: breakdown (with FD_CSC_TR_NORM_DIAG an m_j that is
+ *                         zero or not finite -- the diagonal entry that is not stored and that lambda does not lift --, p.(H + lambda I)p
+ *                         or r.z not finite, or exit 3).  exit: 0 converged inside the region, 1 stopped on the boundary, 2 non-positive
+ *                         curvature followed to the boundary, 3 non-positive curvature without a boundary (y is the last iterate, bit 1
+ *                         is set).  A boundary exit (1, 2) is a success: flags 0.  exit is 0 after the other failures.  Then the
+ *                         iterations of the last step, the recurred ||g + (H + lambda I) y||_2, ||g||_2, ||y||_W and the predicted
+ *                         reduction pred = -q(y) = -1/2 sum y_j (g_j + r_j).  After bit 0 or bit 1, y and r_out are NaN, unless
+ *                         fd_csc_tr_set_policy(tr, 1): then they are the last iterate's.  The four scalars describe the last iterate
+ *                         either way.  Any out pointer may be NULL.
+ * Everything is enqueued on the context's stream; fd_csc_tr_create and fd_csc_tr_status synchronise it.  Without a device
+ * fd_csc_tr_create is FD_ERR_NODEVICE. */
+#define FD_CSC_TR_NORM_IDENTITY  0
+#define FD_CSC_TR_NORM_DIAG      1
+typedef struct fd_csc_tr fd_csc_tr;
+int fd_csc_tr_create(fd_ctx *ctx, int64_t N, const void *colptr, const void *rowval, int idx_bytes, int idx_base, int idx_kind,
+                     fd_csc_tr **out);
+int fd_csc_tr_destroy(fd_csc_tr *tr);
+int fd_csc_tr_set_options(fd_csc_tr *tr, double rtol, int max_iterations);
+int fd_csc_tr_set_policy(fd_csc_tr *tr, int keep_unconverged);
+int fd_csc_tr_matvec_async(fd_csc_tr *tr, double lambda, const void *nzval, const void *v, void *y);
+int fd_csc_tr_step_async(fd_csc_tr *tr, double lambda, double radius, int norm_kind, const void *nzval, const void *g, void *y, void *r_out);
+int fd_csc_tr_status(fd_csc_tr *tr, int *flags_out, int *exit_out, int64_t *iterations_out, double *resid_out, double *g_norm_out,
+                     double *step_norm_out, double *pred_out);
+
 /* ---- the consumer for block-banded Jacobians: (alpha*I + beta*J) y = b for a BLOCK-TRIDIAGONAL J (round 6) ---------------------------
  * J = nblk x nblk dense blocks of block_size x block_size (<= 32), block bandwidths (1, 1), in BlockBandedMatrix data as a
  * fd_plan_create_blockbanded plan of uniform block sizes fills it (block column J's in-band blocks stacked into one column-major

@@ -680,7 +680,8 @@ class CscSolver(_CscConsumer):
 
     def set_preconditioner(self, kind="jacobi", block_size=None):
         """``"jacobi"`` (the default: the diagonal) or ``"block_jacobi"`` with ``block_size`` in 2..32: the inverses of the diagonal blocks
-        alpha*I + beta*J[k*bs:(k+1)*bs, k*bs:(k+1)*bs], gathered and inverted by every solve (fd_csc_solver_set_preconditioner)."""
+        alpha*I + beta*J[k*bs:(k+1)*bs, k*bs:(k+1)*bs], gathered and inverted by every solve (fd_csc_solver_set_preconditioner).
+        Block ILU(0) on blocks of up to 1024 rows has entry points of its own: ``set_block_ilu``, ``ilu_levels``, ``ilu_factors``."""
         kinds = {"jacobi": 0, "block_jacobi": 1}
         if kind not in kinds:
             raise ValueError("kind must be 'jacobi' or 'block_jacobi'")
@@ -697,6 +698,31 @@ class CscSolver(_CscConsumer):
         self.ctx.synchronize()
         view = _DevView(p.value, bs.value * self.N, False)
         return torch.as_tensor(view, device="cuda:%d" % self.ctx.device).clone().reshape(bs.value, self.N)
+
+    def set_block_ilu(self, block_size):
+        """Block ILU(0) for the following solves (fd_csc_solver_set_block_ilu): block Jacobi over the uniform ranges of ``block_size``
+        rows (2..1024) with the ILU(0) factors of every block on its own stored pattern, factored by every solve.  Builds the level
+        schedule and synchronises; ``set_preconditioner`` switches back."""
+        _l.check(self.Lt.fd_csc_solver_set_block_ilu(self.handle, int(block_size)))
+
+    def ilu_levels(self):
+        """The schedule's levels as int32 CUDA tensors (copies) and their maxima: (lev_fwd, lev_bwd, max_fwd, max_bwd)."""
+        pf, pb, mf, mb = C.c_void_p(), C.c_void_p(), C.c_int(), C.c_int()
+        _l.check(self.Lt.fd_csc_solver_ilu_levels(self.handle, C.byref(pf), C.byref(pb), C.byref(mf), C.byref(mb)))
+        return self._ints(pf.value, self.N), self._ints(pb.value, self.N), mf.value, mb.value
+
+    def ilu_factors(self):
+        """Synchronises.  The factors of the last block-ILU solve as float64 CUDA tensors (copies): lu (nnz, indexed like
+        ``row_lists()``'s row_col: l below the diagonal, u above and on it, +0.0 outside the row's block) and u (N, the diagonal);
+        and the block size."""
+        import torch
+        pl, pu, nb, bs, nnz = C.c_void_p(), C.c_void_p(), C.c_int64(), C.c_int(), C.c_int64()
+        _l.check(self.Lt.fd_csc_solver_ilu_factors(self.handle, C.byref(pl), C.byref(pu), C.byref(nb), C.byref(bs)))
+        _l.check(self.Lt.fd_csc_solver_row_lists(self.handle, None, None, None, None, C.byref(nnz), None))
+        self.ctx.synchronize()
+        dev = "cuda:%d" % self.ctx.device
+        lu = torch.as_tensor(_DevView(pl.value, nnz.value, False), device=dev).clone() if nnz.value else torch.empty(0, dtype=torch.float64, device=dev)
+        return lu, torch.as_tensor(_DevView(pu.value, self.N, False), device=dev).clone(), bs.value
 
     def row_lists(self):
         """The solver's lists as int32 CUDA tensors (copies): row_ptr, row_col, row_slot, diag_slot; and the number of long rows."""

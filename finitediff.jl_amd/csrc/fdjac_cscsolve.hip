@@ -26,17 +26,37 @@
 // from +0.0, one multiply and one add per term; the block's x values go through LDS.  The vector kernels then skip the division
 // (their PC = 1 instances), so an iteration is 7 launches (+ 2 with long rows) instead of 5; kind 0 runs the PC = 0 instances, which
 // are the code of before.  tests/csc_block_model.py restates all of it.
+//
+// BLOCK ILU(0) (fd_csc_solver_set_block_ilu).  The same uniform ranges with bs in 2..1024; M = diag(L_k U_k), the ILU(0) factors of
+// B_k on its own stored pattern (the diagonal always part of it), applied on the right like the inverses above.  An in-block entry is
+// a stored entry whose row and column lie in one block: a contiguous run of the row's sorted list.  The schedule (built on the host when
+// the preconditioner is selected) holds per row the run's bounds and the diagonal's split, the levels lev_f (0 without an in-block lower
+// entry, else 1 + the largest level of those entries' columns) and lev_b (likewise over the upper entries), and per block the rows by
+// (level, row).  ONE workgroup owns one block; a barrier separates the levels; nothing waits on another workgroup.
+//   factor (k_cs_ilu_factor, once per solve, behind k_cs_init<1>): row i, one lane, IKJ: w_j = beta nzval (off the diagonal), d = alpha +
+//     beta nzval or alpha; for every in-block (i, k), k < i ascending: l = w_k / u_k, w_k = l; for every in-block (k, j) of row k, j > k
+//     ascending, f its final value: j == i: d = d - l f; else if (i, j) is stored in-block: w_j = w_j - l f (one multiply, one
+//     subtraction; anything else is dropped); u_i = d, zero or not finite: breakdown (flag bit 1, done), the arithmetic goes on.
+//     lu (nnz doubles, indexed like the row lists): l at the lower positions, the final values at the upper ones, u_i at a stored
+//     diagonal's, +0.0 outside the block; u (N doubles): the diagonal.  The order of the rows inside a level does not matter: a row
+//     reads only rows of lower levels.
+//   apply (k_cs_ilu_apply): the block's x in LDS; forward, levels ascending: t = x_i, t = t - l_ik z_k (k ascending), z_i = t; backward:
+//     t = z_i, t = t - u_ij z_j (j ascending), z_i = t / u_i.
+// An iteration is 7 launches (+ 2 with long rows) as with block Jacobi.  tests/csc_ilu_model.py restates all of it.
 #include "fdjac_internal.h"
 #include "fdjac_device.h"
 #include "fdjac_csc_common.h"
 #include <cmath>
 #include <new>
+#include <vector>
 
 namespace fdjac {
 
 constexpr int kCsWinHalo = 1920;       // the LDS window of v (the tile's 256 rows + the reach on either side) is used up to this reach
 constexpr int kCsBsMax = 32;           // the largest block of the block-Jacobi preconditioner
 constexpr int kCsBinvWaves = 2;        // blocks (one wavefront each) per workgroup of k_cs_binv: 2 x (32 x 65 + 32) doubles = 33 KiB at bs = 32
+constexpr int kCsIluBsMax = FD_CSC_ILU_BS_MAX;      // the largest block of block ILU(0): its x / z fill 8 KiB of LDS
+constexpr int kCsPcIlu = 2;            // pc_kind of block ILU(0): the solver's own, fd_csc_solver_set_preconditioner does not take it
 // scalars of a solve, in device memory: doubles ...
 enum { S_RHO = 0, S_RHO_OLD, S_ALPHA, S_OMEGA, S_BNORM2, S_TOL2, S_RNORM2, S_SNORM2, S_NSCAL };      // (the words and the record: fdjac_csc_common.h)
 
@@ -347,6 +367,93 @@ __global__ void __launch_bounds__(kBlock) k_cs_bapply(int N, int bs, const doubl
         out[i] = acc;
     }
 }
+// ---- block ILU(0) ------------------------------------------------------------------------------------------------------------------------
+struct CsIlu {                         // the schedule as the kernels see it (device, Int32)
+    int bs;
+    const int4 *run;                   // per row, positions in the row lists: the first in-block entry, the first with column >= row,
+                                       // the first with column > row, the end of the in-block run
+    const int *ord_f, *ord_b;          // block k's rows by (level, row) at [k bs, k bs + n)
+    const int *off_f, *off_b;          // block k at k (bs + 1): level L's rows are ord[k bs + off[L] .. k bs + off[L + 1])
+    const int *nlev_f, *nlev_b;        // levels per block
+};
+// factor: one workgroup per block, level by level (the forward levels: row i reads the rows k of its in-block lower entries), thread t
+// takes rows t, t + 256, ... of the level, one lane per row.  lu and u are written and read by the same workgroup across its barriers:
+// plain pointers, so that every read is a vector load behind the barrier's fence.
+__global__ void __launch_bounds__(kBlock) k_cs_ilu_factor(CsPat P, CsIlu I, double alpha, double beta, const real_t *__restrict__ nz,
+                                                          double *lu, double *u, int *words)
+{
+    const int b0 = blockIdx.x * I.bs, nlev = I.nlev_f[blockIdx.x];
+    const int *off = I.off_f + (size_t)blockIdx.x * (I.bs + 1);
+    bool bad = false;
+    for (int L = 0; L < nlev; ++L) {
+        for (int t = off[L] + threadIdx.x; t < off[L + 1]; t += kBlock) {
+            const int i = I.ord_f[b0 + t];
+            const int4 r = I.run[i];
+            const bool stored = r.z > r.y;                                    // the diagonal has a slot
+            double d = alpha;
+            for (int p = r.x; p < r.w; ++p) {
+                const double w = beta * (double)nz[P.row_slot[p]];
+                if (stored && p == r.y) d = alpha + w;
+                else lu[p] = w;
+            }
+            for (int p = r.x; p < r.y; ++p) {
+                const int k = P.row_col[p];
+                const double l = lu[p] / u[k];
+                lu[p] = l;
+                const int4 rk = I.run[k];
+                int pi = p + 1;                                               // row i's entry that (k, j) may meet: both lists ascend
+                for (int q = rk.z; q < rk.w; ++q) {
+                    const int j = P.row_col[q];
+                    const double f = lu[q];
+                    if (j == i) { d = d - l * f; continue; }
+                    while (pi < r.w && P.row_col[pi] < j) ++pi;
+                    if (pi < r.w && P.row_col[pi] == j) lu[pi] = lu[pi] - l * f;
+                }
+            }
+            u[i] = d;
+            if (stored) lu[r.y] = d;
+            bad = bad || cs_bad_pivot(d);
+        }
+        __syncthreads();
+    }
+    if (bad) cs_breakdown(words);
+}
+// z = (L U)^-1 x per block: x through LDS, the forward levels (level 0 has nothing to subtract), the backward levels, then out
+template <int WHICH>      // 0: ph from p; 1: sh from s (not needed once the half step has converged)
+__global__ void __launch_bounds__(kBlock) k_cs_ilu_apply(CsPat P, CsIlu I, const double *__restrict__ lu, const double *__restrict__ u,
+                                                         const double *__restrict__ x, double *__restrict__ out, const int *words)
+{
+    __shared__ double s_z[kCsIluBsMax];
+    if (cs_word(words, W_DONE) || (WHICH == 1 && cs_word(words, W_EARLY))) return;
+    const int b0 = blockIdx.x * I.bs, n = P.N - b0 < I.bs ? P.N - b0 : I.bs;
+    for (int t = threadIdx.x; t < n; t += kBlock) s_z[t] = x[b0 + t];
+    __syncthreads();
+    const int *off = I.off_f + (size_t)blockIdx.x * (I.bs + 1);
+    int nlev = I.nlev_f[blockIdx.x];
+    for (int L = 1; L < nlev; ++L) {
+        for (int t = off[L] + threadIdx.x; t < off[L + 1]; t += kBlock) {
+            const int i = I.ord_f[b0 + t];
+            const int4 r = I.run[i];
+            double acc = s_z[i - b0];
+            for (int p = r.x; p < r.y; ++p) acc = acc - lu[p] * s_z[P.row_col[p] - b0];
+            s_z[i - b0] = acc;
+        }
+        __syncthreads();
+    }
+    off = I.off_b + (size_t)blockIdx.x * (I.bs + 1);
+    nlev = I.nlev_b[blockIdx.x];
+    for (int L = 0; L < nlev; ++L) {
+        for (int t = off[L] + threadIdx.x; t < off[L + 1]; t += kBlock) {
+            const int i = I.ord_b[b0 + t];
+            const int4 r = I.run[i];
+            double acc = s_z[i - b0];
+            for (int p = r.z; p < r.w; ++p) acc = acc - lu[p] * s_z[P.row_col[p] - b0];
+            s_z[i - b0] = acc / u[i];
+        }
+        __syncthreads();
+    }
+    for (int t = threadIdx.x; t < n; t += kBlock) out[b0 + t] = s_z[t];
+}
 // the end: bit 0 when the iterations ran out; y, or NaN after a failure unless the caller keeps the last iterate
 __global__ void __launch_bounds__(kBlock) k_cs_final(int N, const double *__restrict__ yacc, real_t *__restrict__ y, int *words, int keep)
 {
@@ -369,6 +476,11 @@ struct fd_csc_solver {
     double *d_minv = nullptr;          // block Jacobi: minv_bs planes of N doubles (allocated by the first solve that needs them)
     size_t minv_cap = 0;               // doubles allocated
     int minv_bs = 0;                   // the block size of the last block-Jacobi solve, 0: none yet
+    // block ILU(0): the schedule of block size ilu_bs (0: none built) and the factor lu (nnz doubles) | u (N doubles)
+    int ilu_bs = 0, ilu_max_f = 0, ilu_max_b = 0;
+    bool ilu_factored = false;         // a block-ILU solve has run on this schedule
+    int *d_ilu_int = nullptr;          // run (4 N) | lev_f | lev_b | ord_f | ord_b (N each) | off_f | off_b (nblk (bs + 1) each) | nlev_f | nlev_b (nblk each)
+    double *d_ilu = nullptr;
 };
 
 using namespace fdjac;
@@ -379,6 +491,8 @@ static void csc_solver_free(fd_csc_solver *s)
     s->S.free();
     if (s->d_vec) (void)hipFree(s->d_vec);
     if (s->d_minv) (void)hipFree(s->d_minv);
+    if (s->d_ilu_int) (void)hipFree(s->d_ilu_int);
+    if (s->d_ilu) (void)hipFree(s->d_ilu);
     delete s;
 }
 
@@ -472,6 +586,123 @@ int fd_csc_solver_block_inverses(fd_csc_solver *s, const void **inv_dev, int64_t
     return FD_OK;
 }
 
+// ---- block ILU(0): the schedule, on the host from the solver's row lists (not on the hot path) ------------------------------------
+static size_t ilu_nblk(const fd_csc_solver *s, int bs) { return (size_t)((s->L.N + bs - 1) / bs); }
+static size_t ilu_ints(const fd_csc_solver *s, int bs) { return 8 * (size_t)s->L.N + 2 * ilu_nblk(s, bs) * (size_t)(bs + 1) + 2 * ilu_nblk(s, bs); }
+static CsIlu csc_ilu(const fd_csc_solver *s)
+{
+    const size_t N = (size_t)s->L.N, nblk = ilu_nblk(s, s->ilu_bs), no = nblk * (size_t)(s->ilu_bs + 1);
+    const int *p = s->d_ilu_int;
+    CsIlu I;
+    I.bs = s->ilu_bs;
+    I.run = (const int4 *)p;
+    I.ord_f = p + 6 * N; I.ord_b = p + 7 * N;
+    I.off_f = p + 8 * N; I.off_b = p + 8 * N + no;
+    I.nlev_f = p + 8 * N + 2 * no; I.nlev_b = p + 8 * N + 2 * no + nblk;
+    return I;
+}
+static int ilu_build(fd_csc_solver *s, int bs)
+{
+    const size_t N = (size_t)s->L.N, nnz = (size_t)s->L.nnz, nblk = ilu_nblk(s, bs), no = nblk * (size_t)(bs + 1);
+    std::vector<int> row_ptr(N + 1), row_col(nnz), h(ilu_ints(s, bs), 0);
+    FD_HIP_CHECK(hipMemcpy(row_ptr.data(), s->L.row_ptr, sizeof(int) * (N + 1), hipMemcpyDeviceToHost));
+    if (nnz) FD_HIP_CHECK(hipMemcpy(row_col.data(), s->L.row_col, sizeof(int) * nnz, hipMemcpyDeviceToHost));
+    int *run = h.data(), *lev_f = run + 4 * N, *lev_b = run + 5 * N, *ord_f = run + 6 * N, *ord_b = run + 7 * N;
+    int *off_f = run + 8 * N, *off_b = off_f + no, *nlev_f = off_b + no, *nlev_b = nlev_f + nblk;
+    for (size_t i = 0; i < N; ++i) {        // the run of row i and the diagonal's split
+        const int b0 = (int)(i / bs) * bs, b1 = b0 + bs;
+        int p = row_ptr[i];
+        const int e = row_ptr[i + 1];
+        while (p < e && row_col[p] < b0) ++p;
+        run[4 * i] = p;
+        while (p < e && row_col[p] < (int)i) ++p;
+        run[4 * i + 1] = p;
+        if (p < e && row_col[p] == (int)i) ++p;
+        run[4 * i + 2] = p;
+        while (p < e && row_col[p] < b1) ++p;
+        run[4 * i + 3] = p;
+    }
+    int max_f = 0, max_b = 0;
+    for (size_t i = 0; i < N; ++i) {
+        int lev = 0;
+        for (int p = run[4 * i]; p < run[4 * i + 1]; ++p) lev = lev > lev_f[row_col[p]] + 1 ? lev : lev_f[row_col[p]] + 1;
+        lev_f[i] = lev;
+        max_f = max_f > lev ? max_f : lev;
+    }
+    for (size_t i = N; i-- > 0;) {
+        int lev = 0;
+        for (int p = run[4 * i + 2]; p < run[4 * i + 3]; ++p) lev = lev > lev_b[row_col[p]] + 1 ? lev : lev_b[row_col[p]] + 1;
+        lev_b[i] = lev;
+        max_b = max_b > lev ? max_b : lev;
+    }
+    for (int dir = 0; dir < 2; ++dir) {     // per block a counting sort by level: the rows of a level stay ascending
+        const int *lev = dir ? lev_b : lev_f;
+        int *ord = dir ? ord_b : ord_f, *off = dir ? off_b : off_f, *nlev = dir ? nlev_b : nlev_f;
+        for (size_t k = 0; k < nblk; ++k) {
+            const size_t b0 = k * (size_t)bs, n = N - b0 < (size_t)bs ? N - b0 : (size_t)bs;
+            int *o = off + k * (size_t)(bs + 1), nl = 0;
+            for (size_t i = b0; i < b0 + n; ++i) { ++o[lev[i] + 1]; nl = nl > lev[i] + 1 ? nl : lev[i] + 1; }      // (a level is below n)
+            for (int L = 0; L < nl; ++L) o[L + 1] += o[L];
+            std::vector<int> cur(o, o + nl);
+            for (size_t i = b0; i < b0 + n; ++i) ord[b0 + cur[lev[i]]++] = (int)i;
+            nlev[k] = nl;
+        }
+    }
+    if (s->d_ilu_int) (void)hipFree(s->d_ilu_int);
+    if (s->d_ilu) (void)hipFree(s->d_ilu);
+    s->d_ilu_int = nullptr; s->d_ilu = nullptr; s->ilu_bs = 0; s->ilu_factored = false;
+    const char *who = "block ILU";
+    CSC_TRY(who, hipMalloc((void **)&s->d_ilu_int, sizeof(int) * h.size()));
+    CSC_TRY(who, hipMalloc((void **)&s->d_ilu, sizeof(double) * (nnz + N)));
+    CSC_TRY(who, hipMemcpy(s->d_ilu_int, h.data(), sizeof(int) * h.size(), hipMemcpyHostToDevice));
+    CSC_TRY(who, hipMemset(s->d_ilu, 0, sizeof(double) * (nnz + N)));      // +0.0 at every position outside a block: no kernel writes there
+    CSC_TRY(who, hipDeviceSynchronize());
+    s->ilu_bs = bs; s->ilu_max_f = max_f; s->ilu_max_b = max_b;
+    return FD_OK;
+}
+
+int fd_csc_solver_set_block_ilu(fd_csc_solver *s, int block_size)
+{
+    FD_REQUIRE(s != nullptr, FD_ERR_ARG, "solver is NULL");
+    FD_REQUIRE(block_size >= 2 && block_size <= kCsIluBsMax, FD_ERR_ARG, "block_size = %d (2 .. %d)", block_size, kCsIluBsMax);
+    FD_HIP_CHECK(hipSetDevice(s->ctx->device));
+    FD_HIP_CHECK(hipStreamSynchronize(s->ctx->stream));
+    if (s->ilu_bs != block_size) {
+        const int rc = ilu_build(s, block_size);
+        if (rc != FD_OK) {               // the preconditioner of before stays selected; block ILU of another size has lost its schedule
+            if (s->pc_kind == kCsPcIlu) { s->pc_kind = FD_CSC_PRECOND_JACOBI; s->pc_bs = 0; }
+            return rc;
+        }
+    }
+    s->pc_kind = kCsPcIlu;
+    s->pc_bs = block_size;
+    return FD_OK;
+}
+
+// the levels of the schedule, for the tests: N Int32 each, owned by the solver
+int fd_csc_solver_ilu_levels(fd_csc_solver *s, const void **lev_fwd_dev, const void **lev_bwd_dev, int *max_fwd, int *max_bwd)
+{
+    FD_REQUIRE(s != nullptr, FD_ERR_ARG, "solver is NULL");
+    FD_REQUIRE(s->ilu_bs > 0, FD_ERR_UNSUPPORTED, "block ILU is not set on this solver");
+    if (lev_fwd_dev) *lev_fwd_dev = s->d_ilu_int + 4 * (size_t)s->L.N;
+    if (lev_bwd_dev) *lev_bwd_dev = s->d_ilu_int + 5 * (size_t)s->L.N;
+    if (max_fwd) *max_fwd = s->ilu_max_f;
+    if (max_bwd) *max_bwd = s->ilu_max_b;
+    return FD_OK;
+}
+
+// the factors of the last block-ILU solve, for the tests: lu (nnz doubles, indexed like the row lists) and u (N doubles)
+int fd_csc_solver_ilu_factors(fd_csc_solver *s, const void **lu_dev, const void **u_dev, int64_t *nblocks, int *block_size)
+{
+    FD_REQUIRE(s != nullptr, FD_ERR_ARG, "solver is NULL");
+    FD_REQUIRE(s->ilu_bs > 0 && s->ilu_factored, FD_ERR_UNSUPPORTED, "no block-ILU solve has run on this solver");
+    if (lu_dev) *lu_dev = s->d_ilu;
+    if (u_dev) *u_dev = s->d_ilu + (size_t)s->L.nnz;
+    if (nblocks) *nblocks = (int64_t)ilu_nblk(s, s->ilu_bs);
+    if (block_size) *block_size = s->ilu_bs;
+    return FD_OK;
+}
+
 // the solver's lists, for the tests and for callers that want the pattern by rows: device pointers that live as long as the solver
 int fd_csc_solver_row_lists(fd_csc_solver *s, const void **row_ptr, const void **row_col, const void **row_slot, const void **diag_slot,
                             int64_t *nnz_out, int64_t *long_rows_out)
@@ -536,7 +767,15 @@ int fd_csc_solve_async(fd_csc_solver *s, double alpha, double beta, const void *
         s->minv_cap = (size_t)bs * (size_t)N;
     }
     FD_HIP_CHECK(hipMemsetAsync(S.d_words, 0, sizeof(int) * W_NWORDS, st));
-    if (bs > 0) {
+    const bool ilu = s->pc_kind == kCsPcIlu;
+    const CsIlu I = ilu ? csc_ilu(s) : CsIlu();
+    const unsigned gi = ilu ? (unsigned)ilu_nblk(s, s->ilu_bs) : 0u;
+    double *lu = s->d_ilu, *u = ilu ? s->d_ilu + (size_t)s->L.nnz : nullptr;
+    if (ilu) {
+        hipLaunchKernelGGL(k_cs_init<1>, dim3(gv), dim3(kBlock), 0, st, P, V, alpha, beta, nz, (const real_t *)b, S.rtol, S.d_scal, S.d_words, S.d_part);
+        hipLaunchKernelGGL(k_cs_ilu_factor, dim3(gi), dim3(kBlock), 0, st, P, I, alpha, beta, nz, lu, u, S.d_words);
+        s->ilu_factored = true;
+    } else if (bs > 0) {
         const int nblk = (N + bs - 1) / bs;
         hipLaunchKernelGGL(k_cs_init<1>, dim3(gv), dim3(kBlock), 0, st, P, V, alpha, beta, nz, (const real_t *)b, S.rtol, S.d_scal, S.d_words, S.d_part);
         hipLaunchKernelGGL(k_cs_binv, dim3((unsigned)((nblk + kCsBinvWaves - 1) / kCsBinvWaves)), dim3(kCsBinvWaves * 64),
@@ -545,15 +784,21 @@ int fd_csc_solve_async(fd_csc_solver *s, double alpha, double beta, const void *
     } else {
         hipLaunchKernelGGL(k_cs_init<0>, dim3(gv), dim3(kBlock), 0, st, P, V, alpha, beta, nz, (const real_t *)b, S.rtol, S.d_scal, S.d_words, S.d_part);
     }
-    const int rc = S.run(st, [&] {      // one iteration: 5 launches (+ 2 with long rows, + 2 with block Jacobi)
-        if (bs > 0) {
+    const int rc = S.run(st, [&] {      // one iteration: 5 launches (+ 2 with long rows, + 2 with block Jacobi or block ILU)
+        if (ilu) {
+            hipLaunchKernelGGL(k_cs_p<1>, dim3(gv), dim3(kBlock), 0, st, N, V, (const double *)S.d_scal, (const int *)S.d_words);
+            hipLaunchKernelGGL(k_cs_ilu_apply<0>, dim3(gi), dim3(kBlock), 0, st, P, I, (const double *)lu, (const double *)u, (const double *)V.p, V.ph, (const int *)S.d_words);
+        } else if (bs > 0) {
             hipLaunchKernelGGL(k_cs_p<1>, dim3(gv), dim3(kBlock), 0, st, N, V, (const double *)S.d_scal, (const int *)S.d_words);
             hipLaunchKernelGGL(k_cs_bapply<0>, dim3(gv), dim3(kBlock), 0, st, N, bs, (const double *)s->d_minv, (const double *)V.p, V.ph, (const int *)S.d_words);
         } else {
             hipLaunchKernelGGL(k_cs_p<0>, dim3(gv), dim3(kBlock), 0, st, N, V, (const double *)S.d_scal, (const int *)S.d_words);
         }
         csc_product<double, 1>(s, alpha, beta, nz, V.ph, V.v, V.rhat, true);
-        if (bs > 0) {
+        if (ilu) {
+            hipLaunchKernelGGL(k_cs_s<1>, dim3(gv), dim3(kBlock), 0, st, N, V, S.d_scal, S.d_words, S.d_part);
+            hipLaunchKernelGGL(k_cs_ilu_apply<1>, dim3(gi), dim3(kBlock), 0, st, P, I, (const double *)lu, (const double *)u, (const double *)V.s, V.sh, (const int *)S.d_words);
+        } else if (bs > 0) {
             hipLaunchKernelGGL(k_cs_s<1>, dim3(gv), dim3(kBlock), 0, st, N, V, S.d_scal, S.d_words, S.d_part);
             hipLaunchKernelGGL(k_cs_bapply<1>, dim3(gv), dim3(kBlock), 0, st, N, bs, (const double *)s->d_minv, (const double *)V.s, V.sh, (const int *)S.d_words);
         } else {

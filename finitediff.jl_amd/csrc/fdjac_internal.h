@@ -76,6 +76,9 @@
 #define fd_csc_solver_row_lists fd32_csc_solver_row_lists
 #define fd_csc_solver_set_preconditioner fd32_csc_solver_set_preconditioner
 #define fd_csc_solver_block_inverses fd32_csc_solver_block_inverses
+#define fd_csc_solver_set_block_ilu fd32_csc_solver_set_block_ilu
+#define fd_csc_solver_ilu_levels fd32_csc_solver_ilu_levels
+#define fd_csc_solver_ilu_factors fd32_csc_solver_ilu_factors
 #define fd_csc_matvec_async fd32_csc_matvec_async
 #define fd_csc_solve_async fd32_csc_solve_async
 #define fd_csc_solver_status fd32_csc_solver_status

@@ -729,10 +729,30 @@ int fd_banded_solve_async(fd_banded_solver *solver, double alpha, double beta, c
  *                         Layout: block_size PLANES of N doubles; plane c, element i holds Minv[i - b0, c] of the block that starts at
  *                         b0 = (i / bs)*bs, i.e. column c of every block's inverse at its global row; a shorter last block leaves 0 in
  *                         the planes c >= its length.  Any out pointer may be NULL.  The layout may change with the solver.
+ *   fd_csc_solver_set_block_ilu  BLOCK ILU(0): block Jacobi over the same uniform ranges with block_size in 2..FD_CSC_ILU_BS_MAX, and
+ *                         inside each block the ILU(0) factors L_k U_k of B_k on its own stored pattern (the diagonal is always part of
+ *                         it; fill is dropped; no pivoting, no reordering) instead of a dense inverse.  The call builds the schedule
+ *                         (per block the rows by dependency level, forward and backward) from the solver's row lists and SYNCHRONISES;
+ *                         it selects block ILU(0) for the following solves until fd_csc_solver_set_preconditioner (kind 0 or 1) switches
+ *                         back; another block_size rebuilds the schedule.  Every solve factors the blocks in ONE launch (one workgroup
+ *                         per block, IKJ, a row per lane, a barrier per level); a pivot u_i that is zero or not finite is a breakdown
+ *                         (bit 1, no iteration).  Each iteration takes 7 launches (+ 2 with long rows), two of them the triangular
+ *                         solves z = U^-1 L^-1 x per block.  Every order is fixed: the same bits every call.  Buffers:
+ *                         nnz + N doubles and 8 N + 2 (nblocks (block_size + 2)) Int32, freed with the solver.  A block_size outside
+ *                         the range is FD_ERR_ARG.
+ *   fd_csc_solver_ilu_levels  DIAGNOSTIC ONLY, valid once block ILU is set (FD_ERR_UNSUPPORTED before): device pointers, owned by the solver,
+ *                         to the forward and backward level of every row (N Int32 each; 0: the row has no in-block lower / upper entry,
+ *                         else 1 + the largest level among those entries' columns) and the largest of each.
+ *   fd_csc_solver_ilu_factors  DIAGNOSTIC ONLY: device pointers, owned by the solver, to the factors of the last block-ILU solve
+ *                         (FD_ERR_UNSUPPORTED before the first): lu, nnz doubles indexed like row_col / row_slot of
+ *                         fd_csc_solver_row_lists (l_ik at the in-block lower positions, the final u_ij at the upper ones, u_ii at a
+ *                         stored diagonal's, +0.0 at every position outside the row's block), and u, the N diagonals u_ii.  Any out
+ *                         pointer may be NULL.  The layout may change with the solver.
  * Everything is enqueued on the context's stream; fd_csc_solver_create and fd_csc_solver_status synchronise it.  Without a device
  * fd_csc_solver_create is FD_ERR_NODEVICE. */
 #define FD_CSC_PRECOND_JACOBI        0   /* the default */
 #define FD_CSC_PRECOND_BLOCK_JACOBI  1
+#define FD_CSC_ILU_BS_MAX            1024   /* the largest block of fd_csc_solver_set_block_ilu */
 typedef struct fd_csc_solver fd_csc_solver;
 int fd_csc_solver_create(fd_ctx *ctx, int64_t N, const void *colptr, const void *rowval, int idx_bytes, int idx_base, int idx_kind,
                          fd_csc_solver **out);
@@ -746,6 +766,9 @@ int fd_csc_solver_row_lists(fd_csc_solver *solver, const void **row_ptr, const v
                             int64_t *nnz_out, int64_t *long_rows_out);
 int fd_csc_solver_set_preconditioner(fd_csc_solver *solver, int kind, int block_size);
 int fd_csc_solver_block_inverses(fd_csc_solver *solver, const void **inv_dev, int64_t *nblocks, int *block_size);
+int fd_csc_solver_set_block_ilu(fd_csc_solver *solver, int block_size);
+int fd_csc_solver_ilu_levels(fd_csc_solver *solver, const void **lev_fwd_dev, const void **lev_bwd_dev, int *max_fwd, int *max_bwd);
+int fd_csc_solver_ilu_factors(fd_csc_solver *solver, const void **lu_dev, const void **u_dev, int64_t *nblocks, int *block_size);
 
 /* ---- the LEAST-SQUARES consumer: J v, J^T v and the damped Gauss-Newton step for a RECTANGULAR J (M x N) in SparseMatrixCSC storage ----
  * The pattern is that of a CSC plan that holds every column: colptr (N + 1) and rowval (nnz), Int32 or Int64, base 0 or 1, on the host or
@@ -1043,6 +1066,9 @@ int fd32_csc_solver_row_lists(fd32_csc_solver *solver, const void **row_ptr, con
                             int64_t *nnz_out, int64_t *long_rows_out);
 int fd32_csc_solver_set_preconditioner(fd32_csc_solver *solver, int kind, int block_size);
 int fd32_csc_solver_block_inverses(fd32_csc_solver *solver, const void **inv_dev, int64_t *nblocks, int *block_size);
+int fd32_csc_solver_set_block_ilu(fd32_csc_solver *solver, int block_size);
+int fd32_csc_solver_ilu_levels(fd32_csc_solver *solver, const void **lev_fwd_dev, const void **lev_bwd_dev, int *max_fwd, int *max_bwd);
+int fd32_csc_solver_ilu_factors(fd32_csc_solver *solver, const void **lu_dev, const void **u_dev, int64_t *nblocks, int *block_size);
 typedef struct fd32_csc_lsq fd32_csc_lsq;
 int fd32_csc_lsq_create(fd_ctx *ctx, int64_t M, int64_t N, const void *colptr, const void *rowval, int idx_bytes, int idx_base, int idx_kind,
                       fd32_csc_lsq **out);

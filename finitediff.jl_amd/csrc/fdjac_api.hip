@@ -502,6 +502,7 @@ int fd_plan_info(const fd_plan *p, int key, int64_t *value)
     case FD_INFO_STORE_CSC:
         *value = p->store_csc_ok ? p->sc_entries : 0;
         break;
+    case FD_INFO_STORE_LAUNCH: *value = p->store_launch; break;
     case FD_INFO_LAZY_DIFF:
         *value = (p->lazy_fn && (p->lazy_caps & FD_LAZY_CAP_DIFF) && p->lazy_diff && p->fdtype != FD_COMPLEX && p->kind != K_DENSE) ? 1 : 0;
         break;
@@ -1068,8 +1069,10 @@ static int jacobian_enqueue(fd_plan *p, fd_f_launch f, void *fctx, const real_t 
             lp.imag_only = lp.is_complex;
             lp.store = &sc;
             lp.store_kind = FD_STORE_CSC;
+            store_launch_note() = FD_STORE_LAUNCH_NONE;
             const int rc = p->lazy_fn(fctx, p->d_FX, &lp, p->ldf, p->row0, p->row1, (void *)s);
             FD_REQUIRE(rc == 0 || rc == FD_LAZY_DECLINED, FD_ERR_CALLBACK, "lazy f! launcher (column store) returned %d", rc);
+            p->store_launch = rc == 0 ? store_launch_note() : FD_STORE_LAUNCH_NONE;
             if (rc == 0) {
                 p->fcalls_last += (int64_t)B * p->pts + ((own_base && !diff_base_counted) ? 1 : 0);      // (f(x): once, inside the launch)
                 if (own_base) diff_base_counted = true;

@@ -275,6 +275,7 @@ struct SparseF {
     template <class P> __device__ __forceinline__ real_t operator()(long long r, const P &X) const { return row<real_t>(r, X); }
     // the residual is SEPARABLE on its pattern (include/fdjac_device.h): entry (r, j)'s term -- the one `row` adds, the same bits
     static constexpr bool fd_separable = true;
+    static constexpr bool fd_zero_sign_blind = true;      // phi(-0.0) = phi(+0.0) = +0.0: v + (q v) v
     template <typename T> __device__ __forceinline__ T term(long long r, long long j, T v) const
     {
         return ((real_t)1 + kEighth * (real_t)(int)((r + 3 * j) & 7)) * (v + (kQuarter * v) * v);
@@ -844,12 +845,14 @@ static int functor_family_lazy(BuiltinF *b, const fd_lazy_points *lp, hipStream_
             const SparseF f = {b->d_srow, b->d_scol};
             hipLaunchKernelGGL((k_csc_store_cols_cplx<CT, SparseF>), dim3(g), dim3(kBlock), 0, s, f, x, eps, c_lo, c_hi, st);
         }
+        store_launch_note() = FD_STORE_LAUNCH_FAMILY;
         return hipGetLastError() == hipSuccess ? 0 : 4;
     }
 #define FD_COLS(FT, fobj)                                                                                                                  \
     do {                                                                                                                                   \
         if (lp->pts == 2) hipLaunchKernelGGL((fd_csc_store_cols<real_t, CT, 1, FT>), dim3(g), dim3(kBlock), 0, s, fobj, x, eps, c_lo, c_hi, st); \
         else hipLaunchKernelGGL((fd_csc_store_cols<real_t, CT, 0, FT>), dim3(g), dim3(kBlock), 0, s, fobj, x, eps, c_lo, c_hi, st);              \
+        store_launch_note() = FD_STORE_LAUNCH_COLS;                                                                                        \
     } while (0)
     if (b->family == FD_F_LAP7) {
         const Lap7F f = {(int)b->prm[0], (int)b->prm[1], (int)b->prm[2], fd_magic31((uint32_t)(b->prm[0] * b->prm[1])), fd_magic31((uint32_t)b->prm[0])};
@@ -858,6 +861,7 @@ static int functor_family_lazy(BuiltinF *b, const fd_lazy_points *lp, hipStream_
             else hipLaunchKernelGGL((k_f_lap7_store_cols<CT, 0>), dim3(g), dim3(kBlock), 0, s, f, x, eps, c_lo, c_hi, st);
             // (every launch visits all local columns: one that counted no mismatch has verified the pattern)
             if (st.note) hipLaunchKernelGGL(k_lap7_note, dim3(1), dim3(1), 0, s, st.note, lap7_note_key(f, st));
+            store_launch_note() = FD_STORE_LAUNCH_FAMILY;
         } else {
             FD_COLS(Lap7F, f);
         }
@@ -910,12 +914,14 @@ static int functor_family_lazy(BuiltinF *b, const fd_lazy_points *lp, hipStream_
                 if (lp->pts == 2) hipLaunchKernelGGL((fd_csc_store_ents<real_t, CT, 1, SparseF>), dim3(gr), dim3(kBlock), lds_e, s, f, x, eps, c_lo, c_hi, st, (int)reach);
                 else hipLaunchKernelGGL((fd_csc_store_ents<real_t, CT, 0, SparseF>), dim3(gr), dim3(kBlock), lds_e, s, f, x, eps, c_lo, c_hi, st, (int)reach);
                 b->row_stores.fetch_add(1);
+                store_launch_note() = FD_STORE_LAUNCH_ENTS;
                 return hipGetLastError() == hipSuccess ? 0 : 4;
             }
             const size_t lds_g = fd_csc_rows_lds_bytes<real_t>(reach, lp->ncolors, cap_r);
             if (lp->pts == 2) hipLaunchKernelGGL((fd_csc_store_rows<real_t, CT, 1, SparseF>), dim3(gr), dim3(kBlock), lds_g, s, f, x, eps, c_lo, c_hi, st, (int)reach, cap_r);
             else hipLaunchKernelGGL((fd_csc_store_rows<real_t, CT, 0, SparseF>), dim3(gr), dim3(kBlock), lds_g, s, f, x, eps, c_lo, c_hi, st, (int)reach, cap_r);
             b->row_stores.fetch_add(1);
+            store_launch_note() = FD_STORE_LAUNCH_ROWS;
             return hipGetLastError() == hipSuccess ? 0 : 4;
         }
         if (verdict != 1) {                    // a column kernel
@@ -930,16 +936,18 @@ static int functor_family_lazy(BuiltinF *b, const fd_lazy_points *lp, hipStream_
                     const unsigned long long gate = (rows && verdict == 0) ? key : 0ull;
                     if (lp->pts == 2) hipLaunchKernelGGL((k_f_sparse_store_sorted<CT, 1>), dim3(g), dim3(kBlock), lds_s, s, f, x, eps, c_lo, c_hi, st, (int)reach, cap, gate);
                     else hipLaunchKernelGGL((k_f_sparse_store_sorted<CT, 0>), dim3(g), dim3(kBlock), lds_s, s, f, x, eps, c_lo, c_hi, st, (int)reach, cap, gate);
+                    store_launch_note() = FD_STORE_LAUNCH_FAMILY;
                     done = true;
                 } else if (lds <= 64 * 1024) {
                     if (lp->pts == 2) hipLaunchKernelGGL((fd_csc_store_cols_win<real_t, CT, 1, SparseF>), dim3(g), dim3(kBlock), lds, s, f, x, eps, c_lo, c_hi, st, (int)reach, (int)sb, cap);
                     else hipLaunchKernelGGL((fd_csc_store_cols_win<real_t, CT, 0, SparseF>), dim3(g), dim3(kBlock), lds, s, f, x, eps, c_lo, c_hi, st, (int)reach, (int)sb, cap);
+                    store_launch_note() = FD_STORE_LAUNCH_COLS_WIN;
                     done = true;
                 }
             }
             if (!done) FD_COLS(SparseF, f);
         }
-        if (verdict == 1) b->row_stores.fetch_add(1);
+        if (verdict == 1) { b->row_stores.fetch_add(1); store_launch_note() = FD_STORE_LAUNCH_FAMILY; }      // (k_f_sparse_store_rows below stores)
         if (rows && verdict != 2) {
             const long long row_lo = std::max<long long>(0, st.col_begin - reach), row_hi = std::min<long long>(st.M, st.col_end + reach);
             const unsigned gr = fd_xcd_grid((row_hi - row_lo + kBlock - 1) / kBlock);

@@ -332,6 +332,10 @@ RtcResult rtc_compile(const std::string &src, const char *program, const std::ve
 // the FD_* code of a result, with the error text set: no hiprtc FD_ERR_UNSUPPORTED, compile / link FD_ERR_ARG, create / load FD_ERR_HIP
 int rtc_error(const RtcResult &r, const char *what);
 std::string &rtc_log();                      // the calling thread's fd_f_compile_log()
+// the calling thread's FD_STORE_LAUNCH_*: written by the library's column-store launchers, read by fd_jacobian (FD_INFO_STORE_LAUNCH);
+// ONE variable for both element types (the Float32 instantiation renames this namespace: the C name is shared)
+extern "C" int *fdjac_store_launch_note_(void);
+inline int &store_launch_note() { return *fdjac_store_launch_note_(); }
 bool rtc_is_type_name(const char *s);        // a functor / terms argument: identifier characters, "::", "<, >" and blanks only
 // the translation unit: the embedded include/fdjac_device.h, "typedef <real> real_t;", body, "#define <define>", tail
 std::string rtc_source(const char *real, const std::string &body, const std::string &define, const std::string &tail);
@@ -553,6 +557,7 @@ struct fd_plan {
     int eps_mode = 0;              // FD_EPS_COMPUTE / FD_EPS_PRECOMPUTED
     int64_t partial_cap = 0;       // doubles allocated behind d_partial
     int64_t fcalls_last = 0;
+    int store_launch = 0;          // FD_INFO_STORE_LAUNCH
     double relstep_last = 0, absstep_last = 0;
 
     fd_fingerprint fp;                          // FD_PLAN_FINGERPRINT: what fd_plan_matches compares against

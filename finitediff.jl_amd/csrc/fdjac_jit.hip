@@ -297,6 +297,7 @@ static int jit_launch_lazy(void *fctx, void *fx, const fd_lazy_points *lp, int64
         if (hipModuleLaunchKernel(j->m->cplx.store[stc.color_bytes == 4 ? 1 : 0], (unsigned)(8 * ((nb + 7) / 8)), 1, 1, 256, 1, 1, 0, (hipStream_t)stream, args,
                                   nullptr) != hipSuccess) return 4;
         j->launches += 1;
+        store_launch_note() = FD_STORE_LAUNCH_FAMILY;
         return 0;
     }
     fd_csc_store st = *(const fd_csc_store *)lp->store;
@@ -325,6 +326,7 @@ static int jit_launch_lazy(void *fctx, void *fx, const fd_lazy_points *lp, int64
             if (hipModuleLaunchKernel(j->m->store_ents[cb][central], gr, 1, 1, 256, 1, 1, (unsigned)lds_e, (hipStream_t)stream, args, nullptr) != hipSuccess) return 4;
             j->launches += 1;
             j->row_stores += 1;
+            store_launch_note() = FD_STORE_LAUNCH_ENTS;
             return 0;
         }
         const size_t lds_r = j->elem_bytes == 8 ? fd_csc_rows_lds_bytes<double>(reach, lp->ncolors, cap) : fd_csc_rows_lds_bytes<float>(reach, lp->ncolors, cap);
@@ -334,6 +336,7 @@ static int jit_launch_lazy(void *fctx, void *fx, const fd_lazy_points *lp, int64
             if (hipModuleLaunchKernel(j->m->store_rows[cb][central], gr, 1, 1, 256, 1, 1, (unsigned)lds_r, (hipStream_t)stream, args, nullptr) != hipSuccess) return 4;
             j->launches += 1;
             j->row_stores += 1;
+            store_launch_note() = FD_STORE_LAUNCH_ROWS;
             return 0;
         }
     }
@@ -344,9 +347,11 @@ static int jit_launch_lazy(void *fctx, void *fx, const fd_lazy_points *lp, int64
         int ireach = (int)reach, sb = 0, cap = 0;
         void *args[] = {(void *)j->params.data(), (void *)&x, (void *)&eps, &c_lo, &c_hi, &st, &ireach, &sb, &cap};
         if (hipModuleLaunchKernel(j->m->store_win[cb][central], g, 1, 1, 256, 1, 1, (unsigned)lds, (hipStream_t)stream, args, nullptr) != hipSuccess) return 4;
+        store_launch_note() = FD_STORE_LAUNCH_COLS_WIN;
     } else {
         void *args[] = {(void *)j->params.data(), (void *)&x, (void *)&eps, &c_lo, &c_hi, &st};
         if (hipModuleLaunchKernel(j->m->store[cb][central], g, 1, 1, 256, 1, 1, 0, (hipStream_t)stream, args, nullptr) != hipSuccess) return 4;
+        store_launch_note() = FD_STORE_LAUNCH_COLS;
     }
     j->launches += 1;
     return 0;

@@ -19,6 +19,7 @@ static const char kDeviceHeader[] =
 
 static thread_local std::string t_log;
 std::string &rtc_log() { return t_log; }
+static thread_local int t_store_launch = 0;
 
 struct Hiprtc {
     void *handle = nullptr;
@@ -220,3 +221,4 @@ int rtc_error(const RtcResult &r, const char *what)
 }  // namespace fdjac
 
 extern "C" const char *fd_f_compile_log(void) { return fdjac::t_log.c_str(); }
+extern "C" int *fdjac_store_launch_note_(void) { return &fdjac::t_store_launch; }

@@ -317,7 +317,20 @@ enum fd_plan_info_key {
     FD_INFO_LAZY_STORE = 32,          /* 1 if a FD_LAZY_CAP_STORE launcher stores the Jacobian of this plan itself (exact band, cyclic colours; FDJAC_LAZY_STORE=0: never) */
     FD_INFO_LAZY_DIFF = 29,           /* 1 if the plan asks a FD_LAZY_CAP_DIFF launcher for differences (FDJAC_LAZY_DIFF=0: never) */
     FD_INFO_BUILT_ON_DEVICE = 27,     /* 1 if the pattern was compiled by the device plan builder */
-    FD_INFO_STORE_CSC = 33            /* number of local entries of the compact pattern copy of FD_PLAN_STORE_CSC, 0 = none */
+    FD_INFO_STORE_CSC = 33,           /* number of local entries of the compact pattern copy of FD_PLAN_STORE_CSC, 0 = none */
+    FD_INFO_STORE_LAUNCH = 34         /* which kernel the plan's last column-store launch (store_kind = FD_STORE_CSC) ran: FD_STORE_LAUNCH_* below; read-only */
+};
+/* FD_INFO_STORE_LAUNCH: the kernel a launcher of the LIBRARY (built-in families, runtime-compiled functors) enqueued for the last batch of
+   colours it stored through a fd_csc_store -- a launcher chooses silently between them (colouring verified or not, the pattern's reach,
+   LDS, the plan's row lists), all store the same bits.  A launcher compiled apart from the library reports nothing: NONE. */
+enum fd_store_launch {
+    FD_STORE_LAUNCH_NONE = 0,         /* no such launch yet, it was declined, or the launcher is not the library's */
+    FD_STORE_LAUNCH_COLS = 1,         /* fd_csc_store_cols */
+    FD_STORE_LAUNCH_COLS_WIN = 2,     /* fd_csc_store_cols_win */
+    FD_STORE_LAUNCH_ROWS = 3,         /* fd_csc_store_rows */
+    FD_STORE_LAUNCH_ENTS = 4,         /* fd_csc_store_ents */
+    FD_STORE_LAUNCH_FAMILY = 5        /* a kernel of the built-in family's own (the 7-point column kernel; FD_F_SPARSE: its entry-balanced column
+                                         kernel, or its own row-wise kernel on a plan without row lists), the complex-step column store */
 };
 /* Kernel variants are chosen when the plan is created (the FDJAC_* environment switches of DESIGN.md section 5 are
    read there, not per process and not per launch -- except FDJAC_COLRANGE_VEC, which only re-vectorises the same work);

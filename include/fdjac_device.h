@@ -944,8 +944,13 @@ __global__ void __launch_bounds__(256) fd_csc_store_cols_win(F f, const T *__res
  * reach = st.reach (1 .. 700), M == N >= 2, every column local, cap = entries of a 256-row tile kept in LDS (a tile with more reads the
  * rest from memory).  The window of x and of the colours, the step sizes and the tile's run of the row lists are requested up front --
  * every load of the prologue in flight at once -- and parked in LDS; the loops after the barrier touch memory only to store. */
+/* a terms functor whose term(r, j, -0.0) and term(r, j, +0.0) have the same bits may say so (static constexpr bool fd_zero_sign_blind =
+   true): the row-wise kernels then compile without the test for -0.0 and without fd_csc_rows_signed_zero (below) */
+template <class F, class = void> struct fd_zero_sign_blind { static constexpr bool value = false; };
+template <class F> struct fd_zero_sign_blind<F, decltype((void)F::fd_zero_sign_blind, void())> { static constexpr bool value = F::fd_zero_sign_blind; };
 template <class TF> struct fd_sep_rows {
     static constexpr bool fd_separable = true;
+    static constexpr bool fd_zero_sign_blind = ::fd_zero_sign_blind<TF>::value;
     TF t;
     const int *row_ptr, *row_col;
     template <class T> __device__ T term(long long r, long long j, T v) const { return t.term(r, j, v); }
@@ -985,6 +990,46 @@ template <typename T> __host__ __device__ inline size_t fd_csc_rows_lds_bytes(lo
     const size_t xlen = (size_t)(256 + 2 * reach + 2);
     return sizeof(T) * (xlen + 2 * (size_t)ncolors) + 4 * (2 * (size_t)cap + xlen) + 64;
 }
+/* A row that reads a coordinate x_i = -0.0.  The colour's point holds x_i + 0.0 = +0.0 there on the plus side (fd_colour_point,
+   fd_column_point, the hand-over path's k_perturb alike) and x_i itself on the minus side and in f(x): a term that sees the sign of a
+   zero (w / v, copysign) has TWO plain values, and "prefix carried, suffix added" from one set of plain terms would not give the bits of
+   the full evaluation.  Such a row is rare and takes this plain form: every entry's sums formed left to right from the terms of its own
+   point.  col_of / slot_of: the column / slot of the tile's i-th entry. */
+template <typename T> __device__ inline bool fd_is_neg_zero(T v) { return v == (T)0 && __builtin_signbit(v); }
+template <typename T, int MODE, class F, class CJ, class CQ>
+__device__ inline void fd_csc_rows_signed_zero(const F &f, long long r, int b0, int L, const CJ &col_of, const CQ &slot_of, const FD_LDS_PTR(T) s_x,
+                                                                  const FD_LDS_PTR(int) s_c, const FD_LDS_PTR(T) s_h, const FD_LDS_PTR(T) s_y, int w0, int c_lo, int c_hi,
+                                                                  T *out, bool given, T fx_given)
+{
+    T fx = 0;
+    for (int u = 0; u < L; ++u) {
+        const int j = col_of(b0 + u);
+        const T t = f.term(r, (long long)j, (T)s_x[(unsigned)(j - w0)]);
+        fx = u == 0 ? t : fx + t;
+    }
+    for (int k = 0; k < L; ++k) {
+        const int j = col_of(b0 + k), q = slot_of(b0 + k);
+        const unsigned off = (unsigned)(j - w0);
+        const int c = s_c[off];
+        if (c < 0) {
+            if (c_lo == 0) out[q] = (T)0;
+        } else if (c >= c_lo && c < c_hi) {
+            const T h = s_h[c - c_lo], y = s_y[c - c_lo];
+            T sp = 0, sm = 0;
+            for (int u = 0; u < L; ++u) {
+                const int ju = col_of(b0 + u);
+                const T vu = s_x[(unsigned)(ju - w0)];
+                const T tp = f.term(r, (long long)ju, u == k ? vu + h : vu + (T)0);
+                sp = u == 0 ? tp : sp + tp;
+                if (MODE == 1) {
+                    const T tm = f.term(r, (long long)ju, u == k ? vu - h : vu);
+                    sm = u == 0 ? tm : sm + tm;
+                }
+            }
+            out[q] = fd_div_shared<T>(sp - (MODE == 1 ? sm : given ? fx_given : fx), MODE == 1 ? 2 * h : h, y);
+        }
+    }
+}
 /* one row of 1 .. RL entries in REGISTERS, every loop unrolled and predicated */
 template <typename T, int MODE, int RL, class F>
 __device__ __attribute__((always_inline)) inline void fd_csc_rows_regs(const F &f, long long r, int b0, int L, const FD_LDS_PTR(int) s_j, const FD_LDS_PTR(int) s_q, const FD_LDS_PTR(T) s_x,
@@ -996,10 +1041,18 @@ __device__ __attribute__((always_inline)) inline void fd_csc_rows_regs(const F &
 #pragma unroll
     for (int u = 0; u < RL; ++u) { const int i = b0 + (u < L ? u : L - 1); jj[u] = s_j[i]; qq[u] = s_q[i]; }
     T fx = 0;
+    bool nz = false;                                                   /* a -0.0 among the row's coordinates: fd_csc_rows_signed_zero */
 #pragma unroll
     for (int u = 0; u < RL; ++u) {
-        tt[u] = f.term(r, (long long)jj[u], (T)s_x[(unsigned)(jj[u] - w0)]);
+        const T vu = s_x[(unsigned)(jj[u] - w0)];
+        nz = nz || (!fd_zero_sign_blind<F>::value && fd_is_neg_zero(vu));
+        tt[u] = f.term(r, (long long)jj[u], vu);
         fx = u == 0 ? tt[0] : (u < L ? fx + tt[u] : fx);
+    }
+    if (nz) {
+        fd_csc_rows_signed_zero<T, MODE>(f, r, b0, L, [&](int i) -> int { return s_j[i]; }, [&](int i) -> int { return s_q[i]; }, s_x, s_c, s_h, s_y, w0, c_lo, c_hi,
+                                         out, given, fx_given);
+        return;
     }
     T pre = 0;
 #pragma unroll
@@ -1112,10 +1165,18 @@ __global__ void __launch_bounds__(256, 4) fd_csc_store_rows(F f, const T *__rest
         }
         if (L == 0) return;
         T fx = 0;
+        bool nz = false;
         for (int u = 0; u < L; ++u) {
             const int j = s_j[b0 + u];
-            const T t = f.term(r, (long long)j, (T)s_x[(unsigned)(j - (int)w0)]);
+            const T vu = s_x[(unsigned)(j - (int)w0)];
+            nz = nz || (!fd_zero_sign_blind<F>::value && fd_is_neg_zero(vu));
+            const T t = f.term(r, (long long)j, vu);
             fx = u == 0 ? t : fx + t;
+        }
+        if (nz) {
+            fd_csc_rows_signed_zero<T, MODE>(f, r, b0, L, [&](int i) -> int { return s_j[i]; }, [&](int i) -> int { return s_q[i]; }, s_x, s_c, s_h, s_y, (int)w0, c_lo,
+                                             c_hi, out, given, fx_given);
+            return;
         }
         T pre = 0;
         for (int k = 0; k < L; ++k) {
@@ -1151,10 +1212,17 @@ __global__ void __launch_bounds__(256, 4) fd_csc_store_rows(F f, const T *__rest
     auto col_of = [&](int i) -> int { return i < nst ? (int)s_j[i] : st.row_col[A0 + i]; };
     auto slot_of = [&](int i) -> int { return i < nst ? (int)s_q[i] : st.row_slot[A0 + i]; };
     T fx = 0;
+    bool nz = false;
     for (int u = 0; u < L; ++u) {
         const int j = col_of(b0 + u);
-        const T t = f.term(r, (long long)j, (T)s_x[(unsigned)(j - (int)w0)]);
+        const T vu = s_x[(unsigned)(j - (int)w0)];
+        nz = nz || (!fd_zero_sign_blind<F>::value && fd_is_neg_zero(vu));
+        const T t = f.term(r, (long long)j, vu);
         fx = u == 0 ? t : fx + t;
+    }
+    if (nz) {
+        fd_csc_rows_signed_zero<T, MODE>(f, r, b0, L, col_of, slot_of, s_x, s_c, s_h, s_y, (int)w0, c_lo, c_hi, out, given, fx_given);
+        return;
     }
     T pre = 0;
     for (int k = 0; k < L; ++k) {
@@ -1267,15 +1335,18 @@ __global__ void __launch_bounds__(256) fd_csc_store_ents(F f, const T *__restric
 #pragma unroll
         for (int u = 0; u < NE; ++u) fxg[u] = 0;
     }
+    int nz = 0;                                                        /* a -0.0 among the tile's coordinates (see fd_csc_rows_signed_zero) */
 #pragma unroll
     for (int u = 0; u < NE; ++u) {
         if (u * 256 < nst) {
             const int i = u * 256 + tid;
-            const T t = f.term((long long)rr[u], (long long)ej[u], (T)s_x[(unsigned)(ej[u] - w0)]);
-            if (i < nst) s_t[i] = t;
+            const T vu = s_x[(unsigned)(ej[u] - w0)];
+            const T t = f.term((long long)rr[u], (long long)ej[u], vu);
+            if (i < nst) { s_t[i] = t; nz |= (!fd_zero_sign_blind<F>::value && fd_is_neg_zero(vu)) ? 1 : 0; }
         }
     }
-    __syncthreads();
+    if (fd_zero_sign_blind<F>::value) __syncthreads();
+    else nz = __syncthreads_or(nz);
     /* 2: every entry's quotient */
     T *out = (T *)st.out;
 #pragma unroll
@@ -1291,6 +1362,22 @@ __global__ void __launch_bounds__(256) fd_csc_store_ents(F f, const T *__restric
         const long long r = rr[u];
         const T h = s_h[c - c_lo], y = s_y[c - c_lo], v = s_x[off];
         const T tp = f.term(r, (long long)ej[u], v + h), tm = MODE == 1 ? f.term(r, (long long)ej[u], v - h) : (T)0;
+        if (nz) {
+            /* the tile holds a -0.0: s_t has the terms of x itself (the minus side, f(x)); the plus side's unperturbed terms are those of
+               x + 0.0, formed here from the row's own list (rare: the one place this kernel reads the lists again) */
+            const int a0 = st.row_ptr[r];
+            T sp = 0, sm = 0, sa = 0;
+            for (int uu = 0; uu < L; ++uu) {
+                const int ju = st.row_col[a0 + uu];
+                const T tv = s_t[b + uu], tz = f.term(r, (long long)ju, (T)s_x[(unsigned)(ju - w0)] + (T)0);
+                const bool me = uu == k;
+                sp = uu == 0 ? (me ? tp : tz) : sp + (me ? tp : tz);
+                if (MODE == 1) sm = uu == 0 ? (me ? tm : tv) : sm + (me ? tm : tv);
+                if (MODE == 0 && !given) sa = uu == 0 ? tv : sa + tv;
+            }
+            out[eq[u]] = fd_div_shared<T>(sp - (MODE == 1 ? sm : given ? fxg[u] : sa), MODE == 1 ? 2 * h : h, y);
+            continue;
+        }
         const T t0 = s_t[b];
         T sp = k == 0 ? tp : t0, sm = k == 0 ? tm : t0, sa = t0;
         for (int uu = 1; uu < L; ++uu) {

@@ -108,9 +108,9 @@ def colouring(pname, kind):
     raise ValueError(kind)
 
 
-def operands(family, pname, colors, dtype, seed):
-    """(x, relstep, absstep) of the family on the pattern's columns."""
-    N = pattern(pname)[1]
+def operands(family, pname, colors, dtype, seed, N=None):
+    """(x, relstep, absstep) of the family on the pattern's columns (N given: a pattern of another table, tests/exact_store_cases.py)."""
+    N = pattern(pname)[1] if N is None else N
     C = int(colors.max())
     if family not in ("nan_inf", "few_huge", "cancel"):
         return _operands(family, N, C, dtype, seed)

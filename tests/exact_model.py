@@ -100,6 +100,21 @@ def stencil5_f(x, nx, ny, nl):
     return v.reshape(-1)
 
 
+def lap7_f(x, nx, ny, nz):
+    """FD_F_LAP7 (lap7_row in csrc/fdjac_functor_f.hip) in x's element type, real or complex: the six neighbours added in the order
+    down, south, west, east, north, up (0 outside the grid), minus 6 times the centre, plus (centre * centre) * east."""
+    T = x.dtype.type
+    g = x.reshape(nz, ny, nx)
+    d, s, w, e, n, u = (np.zeros_like(g) for _ in range(6))
+    d[1:] = g[:-1]
+    u[:-1] = g[1:]
+    s[:, 1:] = g[:, :-1]
+    n[:, :-1] = g[:, 1:]
+    w[:, :, 1:] = g[:, :, :-1]
+    e[:, :, :-1] = g[:, :, 1:]
+    return (((((((d + s) + w) + e) + n) + u) - T(6) * g) + (g * g) * e).reshape(-1)
+
+
 def sparse_f(M, N, colptr, rowval, dtype=F64):
     """FD_F_SPARSE (SparseF::row) in the element type: f_r = sum over the entries (r, j) of row r, ascending j, left to right, of
     w * (v + (q * v) * v) with v = x_j, w = 1 + ((r + 3 j) & 7) / 8 and q = 1 / 4 in the element type (both exact); the first term is
@@ -139,7 +154,8 @@ def sparse_f(M, N, colptr, rowval, dtype=F64):
 
 
 def fixture(family, *prm):
-    """f(x) -> f(x) in x's dtype, for the rational built-in families ("sparse", M, N, colptr, rowval: the residual of any pattern)."""
+    """f(x) -> f(x) in x's dtype, for the rational built-in families ("sparse", M, N, colptr, rowval: the residual of any pattern;
+    "lap7", nx, ny, nz: the 7-point family)."""
     if family == "sparse":
         M, N, colptr, rowval = prm
         fs = {}
@@ -152,6 +168,9 @@ def fixture(family, *prm):
         return f
     if family in ("tridiag", "tridiag_nl"):
         return lambda x: tridiag_f(x, family == "tridiag_nl")
+    if family == "lap7":
+        nx, ny, nz = prm
+        return lambda x: lap7_f(np.asarray(x), nx, ny, nz)
     if family in ("lap5", "lap5_nl"):
         nx, ny = prm
         return lambda x: stencil5_f(x, nx, ny, family == "lap5_nl")

@@ -383,3 +383,113 @@ def test_general_cases_keep_most_stored_values_finite(case):
         assert np.isfinite(eps).all() and (want == 0).all()
     if case["family"] in ("tiny_1e-200", "subnormal") and case["dtype"] == "f64":
         assert scaled.any()
+
+
+# ---- the cases of tests/test_gpu_exact_store.py (the storing routes of general patterns), evaluated with the model alone ----------------
+import exact_store_cases as S
+
+_SKEYS = {}
+for _c in S.CASES:
+    _SKEYS.setdefault(S.model_key(_c), _c)
+
+
+def test_lap7_fixture_against_a_point_by_point_restatement():
+    # FD_F_LAP7 (lap7_row, csrc/fdjac_functor_f.hip) one grid point at a time in Python floats -- IEEE doubles, the kernel's order:
+    # ((((((d + s) + w) + e) + n) + u) - 6 c) + (c c) e, a neighbour outside the grid is 0 -- on the three grids of the store cases
+    for name, (nx, ny, nz) in S.LAP7.items():
+        N = nx * ny * nz
+        rng = np.random.default_rng(N)
+        x = rng.random(N) - 0.25
+        x[rng.random(N) < 0.1] = -0.0
+        got = X.fixture("lap7", nx, ny, nz)(x)
+        want = np.empty(N)
+        at = lambda i, j, l: float(x[i + nx * (j + ny * l)]) if (0 <= i < nx and 0 <= j < ny and 0 <= l < nz) else 0.0
+        for k in range(N):
+            i, j, l = k % nx, (k // nx) % ny, k // (nx * ny)
+            c, e = at(i, j, l), at(i + 1, j, l)
+            want[k] = ((((((at(i, j, l - 1) + at(i, j - 1, l)) + at(i - 1, j, l)) + e) + at(i, j + 1, l)) + at(i, j, l + 1)) - 6.0 * c) + (c * c) * e
+        assert got.dtype == np.float64 and X.same_bits(got, want).all(), name
+        g32 = X.fixture("lap7", nx, ny, nz)(x.astype(np.float32))
+        assert g32.dtype == np.float32 and np.allclose(g32, want, rtol=1e-4, atol=1e-5)
+        # the pattern of the cases is the row's own support, the grid's seven colours are valid for it
+        M, N2, colptr, rowval = S.pattern(name)
+        assert (M, N2) == (N, N) and color_model.valid(M, colptr, rowval, S.colouring(name, "greedy"))
+
+
+def test_store_patterns_and_colourings_are_what_their_names_say():
+    M, N, colptr, rowval = S.pattern("ragged400")
+    cnt = np.bincount(rowval - 1, minlength=M)
+    assert (cnt == 0).any() and (np.diff(colptr) == 0).any() and (cnt == 1).any() and cnt.max() == 40 > 32
+    M, N, colptr, rowval = S.pattern("rows12")
+    tiles = np.add.reduceat(np.bincount(rowval - 1, minlength=M), np.arange(0, M, 256))
+    assert M == N == 3000 and tiles[:-1].min() > 3072, tiles           # (every full tile overflows the staged run)
+    for pname in ("random_band", "ragged400", "rows12", "lap7_33x4x9"):
+        M, N, colptr, rowval = S.pattern(pname)
+        for kind in ("greedy", "many", "none5") + (("small",) if pname in S.LAP7 else ("invalid6",)):
+            c = S.colouring(pname, kind)
+            assert color_model.valid(M, colptr, rowval, c) == (kind != "invalid6"), (pname, kind)
+        assert S.colouring(pname, "many").max() > 8 and (S.colouring(pname, "none5") == 0).sum() == 5
+        assert not color_model.valid(M, colptr, rowval, S.colouring(pname, "ones"))
+    fams = {(c["route"], c["fdtype"], c["dir"]) for c in S.CASES if c["family"] == "signed_zeros"}
+    for route in ("cols", "win", "rows", "ents", "lap7", "jit", "terms", "terms_ents"):
+        assert (route, "forward", -1.0) in fams, route                # signed zeros meet dir = -1 on every route
+        have = {c["family"] for c in S.CASES if c["route"] == route and c["dtype"] == "f64"}
+        assert have >= set(S.FAMILIES64), (route, set(S.FAMILIES64) - have)
+
+
+@pytest.mark.parametrize("case", list(_SKEYS.values()), ids=[c["id"] for c in _SKEYS.values()])
+def test_store_cases_keep_most_stored_values_finite_and_reach_their_edge(case):
+    """The finite share (exact_general.MIN_FINITE) and, for the families named after an edge of the division, that the case reaches it:
+    the quotients sorted by the fall-back rules of fd_div_shared on the model's own numerators and divisors (S.div_sides).
+
+    rule3 is the three-argument form every store route calls: it looks at |a y| and |a| only.  rule4, the four-argument form (no route
+    calls it; restated because the operand families were cut for it), also tests the divisor.  What each family must populate:
+      eps_2p100_in    forward: the divisor is 2^100 itself -- product under both rules.  central: the divisor is 2^101 -- rule4 divides
+      eps_2p100_out   the divisor lies just outside 2^100: rule3 still takes the product (forward), rule4 divides -- the two rules part here
+      eps_2m100_*     x + eps is absorbed: every numerator is 0 -- both rules divide (0 lies below 2^-900)
+      num_2p800       numerators from below 2^800 to above 2^900: rule3 populated on BOTH sides; the step 1e136 is outside rule4's range
+      num_2m900       every numerator non-zero and below 2^-900, the quotients of order 1: rule3 divides (its lower edge, with a
+                      numerator at which a wrong condition would show -- the zero numerators of eps_2m100_* divide to 0 either way)
+      tiny / subnorm. step sizes near 1e-108 / 1e-168: product under rule3, division under rule4 (|b| < 2^-100)
+    Across these families both sides of both rules are populated (asserted by test_store_cases_populate_both_sides_of_the_division)."""
+    want, eps, scaled = S.model(case)
+    assert want.size > 0
+    frac = float(np.isfinite(want).mean())
+    assert frac >= S.MIN_FINITE, (case["id"], frac)
+    fam, fwd = case["family"], case["fdtype"] == "forward"
+    if fam == "nan_inf":
+        assert np.isnan(eps).any() and frac < 1.0
+    if fam == "cancel":
+        assert np.isfinite(eps).all() and (want == 0).all()
+    if fam in ("tiny_1e-200", "subnormal") and case["dtype"] == "f64":
+        assert scaled.any()
+    if fam in S.DIV_FAMILIES:
+        assert case["dtype"] == "f64"
+        d = S.div_sides(case)
+        (p3, d3), (p4, d4) = d["rule3"], d["rule4"]
+        assert p3 + d3 == p4 + d4 > 0
+        if fam == "eps_2p100_in":
+            assert d["b"] == ((2.0 ** 100,) * 2 if fwd else (2.0 ** 101,) * 2)
+            assert (p3 > 0 and p4 == p3 and d4 == d3) if fwd else (p4 == 0 and d4 > 0), d
+        elif fam == "eps_2p100_out":
+            assert 2.0 ** 100 < d["b"][0] < 2.0 ** 100 * (1 + 2.0 ** -39) or not fwd
+            assert p4 == 0 and d4 > 0 and (p3 > 0 or not fwd), d
+        elif fam in ("eps_2m100_in", "eps_2m100_out"):
+            assert p3 == 0 and d3 > 0 and p4 == 0 and (want == 0).all(), d
+        elif fam == "num_2p800":
+            assert p3 > 0 and d3 > 0 and p4 == 0 and frac == 1.0, d
+        elif fam == "num_2m900":
+            assert p3 == 0 and d3 > 0 and p4 == 0 and frac == 1.0 and (want != 0).all() and (np.abs(want) > 0.4).all() and (np.abs(want) < 40).all(), d
+        else:
+            assert p3 > 0 and d3 == 0 and p4 == 0 and d["b"][1] < 2.0 ** -100, d
+
+
+def test_store_cases_populate_both_sides_of_the_division():
+    tot = {"rule3": [0, 0], "rule4": [0, 0]}
+    for case in _SKEYS.values():
+        if case["family"] in S.DIV_FAMILIES and case["route"] in ("cols", "lap7"):
+            d = S.div_sides(case)
+            for k in tot:
+                tot[k][0] += d[k][0]
+                tot[k][1] += d[k][1]
+    assert all(min(v) > 0 for v in tot.values()), tot

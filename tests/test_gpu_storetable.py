@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import exact_model
 import finitediff_jl_amd as fd
 from finitediff_jl_amd import patterns as P
 
@@ -34,17 +35,8 @@ def stencil7_csc(nx, ny, nz):
 
 
 def lap7_np(fx, xx, nx, ny, nz):
-    """FD_F_LAP7 in numpy, the kernel's operation order (real or complex)."""
-    X = xx.reshape(nz, ny, nx)
-    Z = np.zeros_like(X)
-    d, s, w, e, n, u = (Z.copy() for _ in range(6))
-    d[1:] = X[:-1]
-    u[:-1] = X[1:]
-    s[:, 1:] = X[:, :-1]
-    n[:, :-1] = X[:, 1:]
-    w[:, :, 1:] = X[:, :, :-1]
-    e[:, :, :-1] = X[:, :, 1:]
-    fx[:] = (((((((d + s) + w) + e) + n) + u) - 6 * X) + (X * X) * e).reshape(-1)
+    """FD_F_LAP7 in numpy, the kernel's operation order (real or complex): the exact model's fixture (tests/exact_model.py)."""
+    fx[:] = exact_model.fixture("lap7", nx, ny, nz)(xx)
 
 
 def sparse_np_factory(M, N, colptr, rowval):

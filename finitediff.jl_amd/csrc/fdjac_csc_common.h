@@ -1,11 +1,17 @@
 // Shared by the consumers on SparseMatrixCSC storage (fdjac_cscsolve.hip, fdjac_csclsq.hip, fdjac_csctr.hip).  CREATE lives in fdjac_csc_pattern.hip: it
 // touches indices only, so it is compiled once, with the Float64 build, and both element builds call it through the declarations below
-// (CscLists, csc_lists_build, csc_lists_free).  Here: the constants, the device helpers of the iteration kernels (index loads, the ordered
-// sums block_sum and the ticket that lets the last-arriving workgroup finish a dot, the breakdown store) and CscSolveState, the host
-// side of a solve that the consumers share: its device words and scalars, the batch loop and the status read-back.
+// (CscLists, csc_lists_build, csc_lists_free).  Here: the constants, CsView (the pattern as the kernels see it), the device helpers of the
+// iteration kernels (index loads, the ordered sums block_sum and the ticket that lets the last-arriving workgroup finish a dot, the
+// breakdown store), THE PRODUCT SCAFFOLD that every consumer's product is made of (cs_gather_sum: a short line's sum, eight gathers ahead;
+// cs_strided_sum and k_cs_long: a long line by one workgroup; cs_tile_lines: a tile of 256 lines across LDS into line order), and the host
+// side that the consumers share: CscSolveState (a solve's device words and scalars, the batch loop, the status read-back) and CscHandle
+// (what every consumer's handle holds, with its create / destroy sequence).
 #pragma once
 #include "fdjac_internal.h"
 #include "fdjac_device.h"
+#include <initializer_list>
+#include <new>
+#include <utility>
 
 // ---- the pattern, built once (fdjac_csc_pattern.hip) ---------------------------------------------------------------------------------
 // No real_t in any of it: these names stay in the Float64 build's namespace, whatever fdjac_internal.h renames for the Float32 one.
@@ -43,11 +49,23 @@ enum { W_DONE = 0, W_EARLY, W_FLAGS, W_ITERS, W_TICKET, W_FINAL, W_NWORDS = 8 };
 
 struct CsRecord { int done, early, flags, iters; };       // what the host reads per batch (the first four words)
 
+struct CsView {                        // the pattern as the kernels see it: CscLists by value (what a consumer did not ask for is NULL)
+    int M, N, nnz, nlong_r, nlong_c, reach, window;      // window: k_cs_rows stages v in LDS (the sparse solver alone)
+    const int *colptr, *rowval, *row_ptr, *row_col, *row_slot, *row_order, *long_rows, *diag, *col_order, *long_cols;
+};
+inline CsView cs_view(const CscLists &L, int window = 0)
+{
+    return CsView{(int)L.M, (int)L.N, (int)L.nnz, L.nlong_r, L.nlong_c, L.reach, window,
+                  L.colptr, L.rowval, L.row_ptr, L.row_col, L.row_slot, L.row_order, L.long_rows, L.diag, L.col_order, L.long_cols};
+}
+inline unsigned cs_tiles(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
+
 __device__ __forceinline__ int64_t cs_load(const void *p, int bytes, int64_t i)
 {
     return bytes == 8 ? ((const int64_t *)p)[i] : (int64_t)((const int32_t *)p)[i];
 }
 __device__ __forceinline__ bool cs_bad_pivot(double x) { return !(fabs(x) > 0.0 && fabs(x) < __builtin_huge_val()); }
+__device__ __forceinline__ bool cs_not_finite(double x) { return !(fabs(x) < __builtin_huge_val()); }
 __device__ __forceinline__ int cs_word(const int *w, int i) { return __hip_atomic_load(w + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void cs_breakdown(int *words)      // flag bit 1, and the solve is over
 {
@@ -92,6 +110,119 @@ __device__ __forceinline__ bool cs_finish(const double (&mine)[ND], double *part
         out[d] = cs_block_sum(acc, s_w);
     }
     return true;
+}
+
+// ---- the product scaffold --------------------------------------------------------------------------------------------------------------
+// A LINE is a row read through the row lists (ascending column) or, COLS, a column as it is stored; its entries are the positions
+// a .. a + n - 1 of those lists.  Entry p's matrix value, widened, and the index of the vector element it meets:
+template <bool COLS, typename TA>
+__device__ __forceinline__ double cs_entry(const CsView &P, const TA *nz, int p) { return (double)(COLS ? nz[p] : nz[P.row_slot[p]]); }
+template <bool COLS>
+__device__ __forceinline__ int cs_meets(const CsView &P, int p) { return COLS ? P.rowval[p] : P.row_col[p]; }
+
+// One lane's sum of a short line: acc = 0; acc += a(k) * v(k), k = 0 .. n - 1 ascending, in groups of eight whose gathers are all
+// requested before the first is used.  a(k), v(k): entry k's matrix and vector value as double.  SQ: *sq = sum a(k) * a(k), added entry
+// by entry in the same loop.  (The zero slots of a partial group are not added: x + 0.0 is not x for x = -0.0.)
+template <bool SQ = false, class FA, class FV>
+__device__ __forceinline__ double cs_gather_sum(int n, FA a, FV v, double *sq = nullptr)
+{
+    double acc = 0.0, acc2 = 0.0;
+    for (int k0 = 0; k0 < n; k0 += 8) {
+        double pa[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pv[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            if (k0 + k < n) {
+                pa[k] = a(k0 + k);
+                pv[k] = v(k0 + k);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            if (k0 + k < n) {
+                acc += pa[k] * pv[k];
+                if (SQ) acc2 += pa[k] * pa[k];
+            }
+        }
+    }
+    if (SQ) *sq = acc2;
+    return acc;
+}
+// A workgroup's sum of a long line: thread t adds entries t, t + 256, ... in that order from +0.0, then block_sum() (valid in thread 0)
+template <bool SQ = false, class FA, class FV>
+__device__ __forceinline__ double cs_strided_sum(int n, FA a, FV v, double *s_w, double *sq = nullptr)
+{
+    double acc = 0.0, acc2 = 0.0;
+    for (int k = threadIdx.x; k < n; k += kBlock) {
+        const double e = a(k);
+        acc += e * v(k);
+        if (SQ) acc2 += e * e;
+    }
+    const double t = cs_block_sum(acc, s_w);
+    if (SQ) *sq = cs_block_sum(acc2, s_w);
+    return t;
+}
+
+// The long lines of a product go first: workgroup i sums line long_rows[i] (COLS: long_cols[i]) and writes y there; the tile kernel that
+// follows takes the value from y.  What is written: the sum t (CS_LONG_SUM); alpha v_i + beta t (CS_LONG_AXPBY: the sparse solver's rows);
+// t, and g_i = sum a^2 into g (CS_LONG_SUM_G: the start of a least-squares solve).  words: NULL, or the solve whose `done` ends the kernel.
+enum { CS_LONG_SUM = 0, CS_LONG_AXPBY, CS_LONG_SUM_G };
+template <bool COLS, int EPI, typename TV>
+__global__ void __launch_bounds__(kBlock) k_cs_long(CsView P, double alpha, double beta, const real_t *__restrict__ nz, const TV *__restrict__ v,
+                                                    TV *__restrict__ y, double *__restrict__ g, const int *words)
+{
+    __shared__ double s_w[kBlock / 64];
+    if (words && cs_word(words, W_DONE)) return;
+    const int i = (COLS ? P.long_cols : P.long_rows)[blockIdx.x];
+    const int *ptr = COLS ? P.colptr : P.row_ptr;
+    const int a = ptr[i], n = ptr[i + 1] - a;
+    double tg = 0.0;
+    const double t = cs_strided_sum<EPI == CS_LONG_SUM_G>(n, [&](int k) { return cs_entry<COLS>(P, nz, a + k); },
+                                                          [&](int k) { return (double)v[cs_meets<COLS>(P, a + k)]; }, s_w, &tg);
+    if (threadIdx.x == 0) {
+        y[i] = (TV)(EPI == CS_LONG_AXPBY ? alpha * (double)v[i] + beta * t : t);
+        if (EPI == CS_LONG_SUM_G) g[i] = tg;
+    }
+}
+
+// ... enqueued for the pattern's long lines, if it has any.  alpha, beta: CS_LONG_AXPBY alone reads them; g: CS_LONG_SUM_G alone writes it
+template <bool COLS, int EPI, typename TV>
+inline void cs_launch_long(hipStream_t st, const CsView &P, const real_t *nz, const TV *v, TV *y, const int *words, double alpha = 0.0,
+                           double beta = 0.0, double *g = nullptr)
+{
+    const int n = COLS ? P.nlong_c : P.nlong_r;
+    if (n > 0) hipLaunchKernelGGL((k_cs_long<COLS, EPI, TV>), dim3((unsigned)n), dim3(kBlock), 0, st, P, alpha, beta, nz, v, y, g, words);
+}
+
+// A tile of 256 lines per workgroup: this lane's line is order[tile0 + lane] (negative: none).  A line of at most kCsLong entries is
+// summed here, entry p meeting vec(index); a longer one takes what k_cs_long left in y (G: and in g).  The value -- out(line, sum) of a
+// short line -- goes to s_out[line - tile0] (G: the sum of squares to s_g), then the barrier: behind it s_out[t] belongs to line tile0 + t.
+template <bool COLS, bool G, typename TA, typename TY, class FV, class FO>
+__device__ __forceinline__ void cs_tile_lines(const CsView &P, int tile0, const TA *nz, const TY *y, const double *g, double *s_out, double *s_g,
+                                              FV vec, FO out)
+{
+    const int i = (COLS ? P.col_order : P.row_order)[tile0 + threadIdx.x];
+    if (i >= 0) {
+        const int *ptr = COLS ? P.colptr : P.row_ptr;
+        const int a = ptr[i], n = ptr[i + 1] - a;
+        if (n <= kCsLong) {
+            double sq = 0.0;
+            const double acc = cs_gather_sum<G>(n, [&](int k) { return cs_entry<COLS>(P, nz, a + k); },
+                                                [&](int k) { return vec(cs_meets<COLS>(P, a + k)); }, &sq);
+            s_out[i - tile0] = out(i, acc);
+            if (G) s_g[i - tile0] = sq;
+        } else {
+            s_out[i - tile0] = (double)y[i];
+            if (G) s_g[i - tile0] = g[i];
+        }
+    }
+    __syncthreads();
+}
+// ... with v read from memory and the plain sum as the value
+template <bool COLS, bool G, typename TA, typename TV>
+__device__ __forceinline__ void cs_tile_lines(const CsView &P, int tile0, const TA *nz, const TV *v, const TV *y, const double *g, double *s_out,
+                                              double *s_g)
+{
+    cs_tile_lines<COLS, G>(P, tile0, nz, y, g, s_out, s_g, [&](int i) { return (double)v[i]; }, [](int, double acc) { return acc; });
 }
 
 // ---- the host side of a solve ------------------------------------------------------------------------------------------------------
@@ -147,6 +278,11 @@ struct CscSolveState {
         rtol = rtol_; max_iterations = max_iterations_;
         return FD_OK;
     }
+    int set_policy(int keep_unconverged)
+    {
+        keep = keep_unconverged ? 1 : 0;
+        return FD_OK;
+    }
     // The iterations, in batches: enqueue_iteration() launches one iteration's kernels on st.  The record of batch k is read while batch
     // k + 1 is already enqueued (its kernels leave at once when the solve is done), so the device never waits for the host.
     template <class F> int run(hipStream_t st, F enqueue_iteration)
@@ -180,5 +316,72 @@ struct CscSolveState {
         return FD_OK;
     }
 };
+
+// ---- the host handle of a consumer ---------------------------------------------------------------------------------------------------
+// What every consumer's handle (fd_csc_solver, fd_csc_lsq, fd_csc_tr) derives from.  The destructors free (the stream has been
+// synchronised; a half-built object is fine): a consumer with buffers of its own frees them in its own.
+struct CscHandle {
+    fd_ctx *ctx = nullptr;
+    CscLists L;                        // (fdjac_csc_pattern.hip)
+    CscSolveState S;
+    double *d_vec = nullptr;           // the vectors of a solve
+    CscHandle() = default;
+    CscHandle(const CscHandle &) = delete;
+    ~CscHandle()
+    {
+        csc_lists_free(&L);
+        S.free();
+        if (d_vec) (void)hipFree(d_vec);
+    }
+    // the lists, nvec doubles of vectors, the state of a solve with nscal scalars and npart partial sums
+    int init(fd_ctx *ctx_, const char *who, int64_t M, int64_t N, const void *colptr, const void *rowval, int idx_bytes, int idx_base, int idx_kind,
+             unsigned want, size_t nvec, int nscal, int64_t npart)
+    {
+        const int rc = csc_lists_build(ctx_, who, M, N, colptr, rowval, idx_bytes, idx_base, idx_kind, want, &L);
+        if (rc != FD_OK) return rc;
+        ctx = ctx_;
+        CSC_TRY(who, hipMalloc((void **)&d_vec, sizeof(double) * nvec));
+        return S.create(who, ctx->stream, nscal, npart);
+    }
+    // d_vec in slices: *first takes `second` doubles, in the order given
+    void slice(std::initializer_list<std::pair<double **, size_t>> parts) const
+    {
+        double *p = d_vec;
+        for (const auto &part : parts) { *part.first = p; p += part.second; }
+    }
+    // synchronises; the words and the scalars of the last solve, its flags and its iteration count
+    int status(int (&w)[W_NWORDS], double *scalars, int *flags_out, int64_t *iterations_out)
+    {
+        const int rc = S.read_status(ctx, w, scalars);
+        if (rc != FD_OK) return rc;
+        if (flags_out) *flags_out = w[W_FINAL];
+        if (iterations_out) *iterations_out = w[W_ITERS];
+        return FD_OK;
+    }
+};
+// create: init(handle) builds it; after a failure nothing is left allocated
+template <class H, class F> int csc_handle_create(H **out, F init)
+{
+    FD_REQUIRE(out != nullptr, FD_ERR_ARG, "NULL argument");
+    *out = nullptr;
+    H *s = new (std::nothrow) H();
+    FD_REQUIRE(s != nullptr, FD_ERR_NOMEM, "out of host memory");
+    const int rc = init(s);
+    if (rc != FD_OK) {
+        if (s->ctx) (void)hipStreamSynchronize(s->ctx->stream);
+        delete s;
+        return rc;
+    }
+    *out = s;
+    return FD_OK;
+}
+template <class H> int csc_handle_destroy(H *s)
+{
+    if (!s) return FD_OK;
+    (void)hipSetDevice(s->ctx->device);
+    (void)hipStreamSynchronize(s->ctx->stream);
+    delete s;
+    return FD_OK;
+}
 
 }  // namespace fdjac

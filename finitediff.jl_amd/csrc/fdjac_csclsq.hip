@@ -5,7 +5,8 @@
 //
 // CREATE is the shared builder's (fdjac_csc_pattern.hip), with the columns' lane order and the long columns in ascending order.
 //
-// ORDERS.  Row r of at most kCsLong entries: acc = 0; acc += nzval[slot_k] * v[col_k], k ascending (ascending column); a longer row by
+// ORDERS.  (The product scaffold -- cs_gather_sum, k_cs_long, cs_tile_lines -- is fdjac_csc_common.h's, shared with the other consumers.)
+// Row r of at most kCsLong entries: acc = 0; acc += nzval[slot_k] * v[col_k], k ascending (ascending column); a longer row by
 // one workgroup: thread t adds entries t, t + 256, ... in that order, then block_sum().  Column j of at most kCsLong entries: one lane, storage
 // order from +0.0 (g_j: acc += a * a; the product: acc += a * v[row]); a longer column by one workgroup in the same way as a long row.  No
 // LDS window of v.  A tile's results cross LDS once, so that everything behind the sums (s, z, the dots) is formed in row / column order.
@@ -26,69 +27,27 @@
 #include "fdjac_device.h"
 #include "fdjac_csc_common.h"
 #include <cmath>
-#include <new>
 
 namespace fdjac {
 
 // scalars of a least-squares solve, in device memory
 enum { LS_GAMMA = 0, LS_ALPHA, LS_BETA, LS_PI, LS_TOL2, LS_GN2, LS_G02, LS_NSCAL = 8 };
 
-struct ClPat {                         // the pattern as the kernels see it
-    int M, N, nnz, nlong_r, nlong_c;
-    const int *colptr, *rowval, *row_ptr, *row_col, *row_slot, *row_order, *long_rows, *col_order, *long_cols;
-};
 struct ClVecs { double *r, *q, *y, *p, *s, *z, *m, *g; };      // r, q: M doubles; the others: N
 
-__device__ __forceinline__ bool cl_not_finite(double x) { return !(fabs(x) < __builtin_huge_val()); }
-
 // ---- products --------------------------------------------------------------------------------------------------------------------------
-// long rows first: workgroup i sums row long_rows[i] and writes y there; the row kernel then takes those values from y
-template <typename TV>
-__global__ void __launch_bounds__(kBlock) k_cl_long_rows(ClPat P, const real_t *__restrict__ nz, const TV *__restrict__ v, TV *__restrict__ y,
-                                                         const int *words)
-{
-    __shared__ double s_w[kBlock / 64];
-    if (words && cs_word(words, W_DONE)) return;
-    const int r = P.long_rows[blockIdx.x], a = P.row_ptr[r], n = P.row_ptr[r + 1] - a;
-    double acc = 0.0;
-    for (int k = threadIdx.x; k < n; k += kBlock) acc += (double)nz[P.row_slot[a + k]] * (double)v[P.row_col[a + k]];
-    const double t = cs_block_sum(acc, s_w);
-    if (threadIdx.x == 0) y[r] = (TV)t;
-}
-
-// rows: a tile of 256 rows per workgroup, lane i takes row row_order[tile * 256 + i]; v is read from memory; the results cross LDS once so
-// that y is written -- and q.q is summed -- in row order.  MODE 0: y only.  1: q = J p of an iteration, q.q -> delta, alpha.
+// The long rows first (k_cs_long<false, CS_LONG_SUM>), then the rows: a tile of 256 rows per workgroup, lane i takes row
+// row_order[tile * 256 + i]; v is read from memory; the results cross LDS once (cs_tile_lines) so that y is written -- and q.q is
+// summed -- in row order.  MODE 0: y only.  1: q = J p of an iteration, q.q -> delta, alpha.
 template <typename TV, int MODE>
-__global__ void __launch_bounds__(kBlock) k_cl_rows(ClPat P, const real_t *__restrict__ nz, const TV *__restrict__ v, TV *__restrict__ y,
+__global__ void __launch_bounds__(kBlock) k_cl_rows(CsView P, const real_t *__restrict__ nz, const TV *__restrict__ v, TV *__restrict__ y,
                                                     double mu, double *scal, int *words, double *part)
 {
     __shared__ double s_out[kBlock];
     __shared__ double s_w[kBlock / 64];
     if (MODE != 0 && cs_word(words, W_DONE)) return;
     const int r0 = (int)blockIdx.x * kBlock;
-    const int r = P.row_order[r0 + threadIdx.x];
-    if (r >= 0) {
-        const int a = P.row_ptr[r], n = P.row_ptr[r + 1] - a;
-        if (n <= kCsLong) {
-            double acc = 0.0;
-            for (int k0 = 0; k0 < n; k0 += 8) {      // eight entries' gathers requested before the first is used
-                double pa[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pv[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    if (k0 + k < n) {
-                        pa[k] = (double)nz[P.row_slot[a + k0 + k]];
-                        pv[k] = (double)v[P.row_col[a + k0 + k]];
-                    }
-                }
-#pragma unroll
-                for (int k = 0; k < 8; ++k) if (k0 + k < n) acc += pa[k] * pv[k];
-            }
-            s_out[r - r0] = acc;
-        } else {
-            s_out[r - r0] = (double)y[r];         // k_cl_long_rows has written it
-        }
-    }
-    __syncthreads();
+    cs_tile_lines<false, false>(P, r0, nz, v, y, nullptr, s_out, nullptr);
     const int row = r0 + threadIdx.x;
     double yr = 0.0;
     if (row < P.M) {
@@ -105,34 +64,12 @@ __global__ void __launch_bounds__(kBlock) k_cl_rows(ClPat P, const real_t *__res
     }
 }
 
-// long columns first: workgroup i sums column long_cols[i] and writes y there (WITH_G: and g_j = sum a^2 into g); the column kernel then
-// takes those values from y / g
-template <typename TV, int WITH_G>
-__global__ void __launch_bounds__(kBlock) k_cl_long_cols(ClPat P, const real_t *__restrict__ nz, const TV *__restrict__ v, TV *__restrict__ y,
-                                                         double *__restrict__ g, const int *words)
-{
-    __shared__ double s_w[kBlock / 64];
-    if (words && cs_word(words, W_DONE)) return;
-    const int j = P.long_cols[blockIdx.x], a = P.colptr[j], n = P.colptr[j + 1] - a;
-    double acc = 0.0, accg = 0.0;
-    for (int k = threadIdx.x; k < n; k += kBlock) {
-        const double e = (double)nz[a + k];
-        acc += e * (double)v[P.rowval[a + k]];
-        if (WITH_G) accg += e * e;
-    }
-    const double t = cs_block_sum(acc, s_w);
-    if (threadIdx.x == 0) y[j] = (TV)t;
-    if (WITH_G) {
-        const double tg = cs_block_sum(accg, s_w);
-        if (threadIdx.x == 0) g[j] = tg;
-    }
-}
-
-// columns: a tile of 256 columns per workgroup, lane i takes column col_order[tile * 256 + i] (storage order from +0.0, eight entries'
-// gathers ahead); the results cross LDS once so that what follows is formed in column order.
+// The long columns first (k_cs_long<true, ...>: y_j, and with CS_LONG_SUM_G g_j = sum a^2 into V.g), then the columns: a tile of 256
+// columns per workgroup, lane i takes column col_order[tile * 256 + i] (storage order from +0.0, eight entries' gathers ahead); the
+// results cross LDS once (cs_tile_lines) so that what follows is formed in column order.
 // MODE 0: y = J^T v.   1: the start of a solve (v = r = b; y = V.s).   2: step 3 of an iteration (v = r; y = V.s).
 template <typename TV, int MODE>
-__global__ void __launch_bounds__(kBlock) k_cl_cols(ClPat P, const real_t *__restrict__ nz, const TV *v, TV *y, ClVecs V,
+__global__ void __launch_bounds__(kBlock) k_cl_cols(CsView P, const real_t *__restrict__ nz, const TV *v, TV *y, ClVecs V,
                                                     double mu, int kind, double rtol, double *scal, int *words, double *part)
 {
     __shared__ double s_out[kBlock];
@@ -140,36 +77,7 @@ __global__ void __launch_bounds__(kBlock) k_cl_cols(ClPat P, const real_t *__res
     __shared__ double s_w[kBlock / 64];
     if (MODE == 2 && cs_word(words, W_DONE)) return;
     const int j0 = (int)blockIdx.x * kBlock;
-    const int j = P.col_order[j0 + threadIdx.x];
-    if (j >= 0) {
-        const int a = P.colptr[j], n = P.colptr[j + 1] - a;
-        if (n <= kCsLong) {
-            double acc = 0.0, accg = 0.0;
-            for (int k0 = 0; k0 < n; k0 += 8) {
-                double pa[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pv[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    if (k0 + k < n) {
-                        pa[k] = (double)nz[a + k0 + k];
-                        pv[k] = (double)v[P.rowval[a + k0 + k]];
-                    }
-                }
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    if (k0 + k < n) {
-                        acc += pa[k] * pv[k];
-                        if (MODE == 1) accg += pa[k] * pa[k];
-                    }
-                }
-            }
-            s_out[j - j0] = acc;
-            if (MODE == 1) s_g[j - j0] = accg;
-        } else {
-            s_out[j - j0] = (double)y[j];         // k_cl_long_cols has written it
-            if (MODE == 1) s_g[j - j0] = V.g[j];
-        }
-    }
-    __syncthreads();
+    cs_tile_lines<true, MODE == 1>(P, j0, nz, v, y, V.g, s_out, s_g);
     const int col = j0 + threadIdx.x;
     const bool in = col < P.N;
     if (MODE == 0) {
@@ -194,7 +102,7 @@ __global__ void __launch_bounds__(kBlock) k_cl_cols(ClPat P, const real_t *__res
             int done = 0;
             if (tot[1] == 0.0) done = 1;                                             // J^T b = 0: y = 0, no iteration
             else if (cs_word(words, W_FLAGS) & 2) done = 1;                          // an m_j that is zero or not finite
-            else if (cl_not_finite(tot[0])) { atomicOr(words + W_FLAGS, 2); done = 1; }   // gamma
+            else if (cs_not_finite(tot[0])) { atomicOr(words + W_FLAGS, 2); done = 1; }   // gamma
             if (done) __hip_atomic_store(words + W_DONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     } else {
@@ -211,7 +119,7 @@ __global__ void __launch_bounds__(kBlock) k_cl_cols(ClPat P, const real_t *__res
             words[W_ITERS] = words[W_ITERS] + 1;
             if (tot[1] <= scal[LS_TOL2]) {
                 __hip_atomic_store(words + W_DONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            } else if (cl_not_finite(tot[0])) {
+            } else if (cs_not_finite(tot[0])) {
                 cs_breakdown(words);
             } else {
                 scal[LS_BETA] = tot[0] / scal[LS_GAMMA];
@@ -278,76 +186,28 @@ __global__ void __launch_bounds__(kBlock) k_cl_final(int M, int N, ClVecs V, rea
 
 }  // namespace fdjac
 
-struct fd_csc_lsq {
-    fd_ctx *ctx = nullptr;
-    fdjac::CscLists L;                 // (fdjac_csc_pattern.hip)
-    fdjac::CscSolveState S;
-    double *d_vec = nullptr;           // r, q (M doubles each), then y, p, s, z, m, g (N each)
-};
+struct fd_csc_lsq : fdjac::CscHandle {};      // d_vec: r, q (M doubles each), then y, p, s, z, m, g (N each)
 
 using namespace fdjac;
 
-static void cl_free(fd_csc_lsq *s)
-{
-    csc_lists_free(&s->L);
-    s->S.free();
-    if (s->d_vec) (void)hipFree(s->d_vec);
-    delete s;
-}
-
-static ClPat cl_pat(const fd_csc_lsq *s)
-{
-    const CscLists &L = s->L;
-    ClPat P;
-    P.M = (int)L.M; P.N = (int)L.N; P.nnz = (int)L.nnz; P.nlong_r = L.nlong_r; P.nlong_c = L.nlong_c;
-    P.colptr = L.colptr; P.rowval = L.rowval; P.row_ptr = L.row_ptr; P.row_col = L.row_col; P.row_slot = L.row_slot;
-    P.row_order = L.row_order; P.long_rows = L.long_rows; P.col_order = L.col_order; P.long_cols = L.long_cols;
-    return P;
-}
 static ClVecs cl_vecs(const fd_csc_lsq *s)
 {
     ClVecs V;
     const size_t M = (size_t)s->L.M, N = (size_t)s->L.N;
-    V.r = s->d_vec; V.q = V.r + M; V.y = V.q + M; V.p = V.y + N; V.s = V.p + N; V.z = V.s + N; V.m = V.z + N; V.g = V.m + N;
+    s->slice({{&V.r, M}, {&V.q, M}, {&V.y, N}, {&V.p, N}, {&V.s, N}, {&V.z, N}, {&V.m, N}, {&V.g, N}});
     return V;
-}
-static unsigned cl_tiles(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
-
-static int cl_init(fd_csc_lsq *s, fd_ctx *ctx, int64_t M, int64_t N, const void *colptr, const void *rowval, int idx_bytes, int idx_base, int idx_kind)
-{
-    const char *who = "csc least squares";
-    const int rc = csc_lists_build(ctx, who, M, N, colptr, rowval, idx_bytes, idx_base, idx_kind, CSC_WANT_COLUMNS, &s->L);
-    if (rc != FD_OK) return rc;
-    s->ctx = ctx;
-    CSC_TRY(who, hipMalloc((void **)&s->d_vec, sizeof(double) * (2 * (size_t)M + 6 * (size_t)N)));
-    return s->S.create(who, ctx->stream, LS_NSCAL, 3 * (((M > N ? M : N) + kBlock - 1) / kBlock));
 }
 
 int fd_csc_lsq_create(fd_ctx *ctx, int64_t M, int64_t N, const void *colptr, const void *rowval, int idx_bytes, int idx_base, int idx_kind,
                       fd_csc_lsq **out)
 {
-    FD_REQUIRE(out != nullptr, FD_ERR_ARG, "NULL argument");
-    *out = nullptr;
-    fd_csc_lsq *s = new (std::nothrow) fd_csc_lsq();
-    FD_REQUIRE(s != nullptr, FD_ERR_NOMEM, "out of host memory");
-    const int rc = cl_init(s, ctx, M, N, colptr, rowval, idx_bytes, idx_base, idx_kind);
-    if (rc != FD_OK) {
-        if (s->ctx) (void)hipStreamSynchronize(s->ctx->stream);
-        cl_free(s);
-        return rc;
-    }
-    *out = s;
-    return FD_OK;
+    return csc_handle_create(out, [&](fd_csc_lsq *s) {
+        return s->init(ctx, "csc least squares", M, N, colptr, rowval, idx_bytes, idx_base, idx_kind, CSC_WANT_COLUMNS, 2 * (size_t)M + 6 * (size_t)N,
+                       LS_NSCAL, 3 * (int64_t)cs_tiles(M > N ? M : N, kBlock));
+    });
 }
 
-int fd_csc_lsq_destroy(fd_csc_lsq *s)
-{
-    if (!s) return FD_OK;
-    (void)hipSetDevice(s->ctx->device);
-    (void)hipStreamSynchronize(s->ctx->stream);
-    cl_free(s);
-    return FD_OK;
-}
+int fd_csc_lsq_destroy(fd_csc_lsq *s) { return csc_handle_destroy(s); }
 
 int fd_csc_lsq_set_options(fd_csc_lsq *s, double rtol, int max_iterations)
 {
@@ -358,8 +218,7 @@ int fd_csc_lsq_set_options(fd_csc_lsq *s, double rtol, int max_iterations)
 int fd_csc_lsq_set_policy(fd_csc_lsq *s, int keep_unconverged)
 {
     FD_REQUIRE(s != nullptr, FD_ERR_ARG, "lsq is NULL");
-    s->S.keep = keep_unconverged ? 1 : 0;
-    return FD_OK;
+    return s->S.set_policy(keep_unconverged);
 }
 
 // the lists, for the tests and for callers that want the pattern by rows: device pointers that live as long as the consumer
@@ -387,22 +246,20 @@ template <typename TV, int MODE>
 static void cl_product_rows(fd_csc_lsq *s, const real_t *nz, const TV *v, TV *y, double mu, bool guarded)
 {
     hipStream_t st = s->ctx->stream;
-    const ClPat P = cl_pat(s);
-    if (P.nlong_r > 0)
-        hipLaunchKernelGGL((k_cl_long_rows<TV>), dim3((unsigned)P.nlong_r), dim3(kBlock), 0, st, P, nz, v, y, guarded ? (const int *)s->S.d_words : (const int *)nullptr);
-    hipLaunchKernelGGL((k_cl_rows<TV, MODE>), dim3(cl_tiles(P.M, kBlock)), dim3(kBlock), 0, st, P, nz, v, y, mu, s->S.d_scal, s->S.d_words, s->S.d_part);
+    const CsView P = cs_view(s->L);
+    cs_launch_long<false, CS_LONG_SUM>(st, P, nz, v, y, guarded ? s->S.d_words : nullptr);
+    hipLaunchKernelGGL((k_cl_rows<TV, MODE>), dim3(cs_tiles(P.M, kBlock)), dim3(kBlock), 0, st, P, nz, v, y, mu, s->S.d_scal, s->S.d_words, s->S.d_part);
 }
 // y = J^T v on the stream: the long columns, then the tiles
 template <typename TV, int MODE>
 static void cl_product_cols(fd_csc_lsq *s, const real_t *nz, const TV *v, TV *y, double mu, int kind)
 {
     hipStream_t st = s->ctx->stream;
-    const ClPat P = cl_pat(s);
+    const CsView P = cs_view(s->L);
     const ClVecs V = cl_vecs(s);
-    if (P.nlong_c > 0)
-        hipLaunchKernelGGL((k_cl_long_cols<TV, MODE == 1>), dim3((unsigned)P.nlong_c), dim3(kBlock), 0, st, P, nz, v, y, V.g,
-                           MODE == 2 ? (const int *)s->S.d_words : (const int *)nullptr);
-    hipLaunchKernelGGL((k_cl_cols<TV, MODE>), dim3(cl_tiles(P.N, kBlock)), dim3(kBlock), 0, st, P, nz, v, y, V, mu, kind, s->S.rtol, s->S.d_scal, s->S.d_words, s->S.d_part);
+    if constexpr (MODE == 1) cs_launch_long<true, CS_LONG_SUM_G>(st, P, nz, v, y, nullptr, 0.0, 0.0, V.g);
+    else cs_launch_long<true, CS_LONG_SUM>(st, P, nz, v, y, MODE == 2 ? s->S.d_words : nullptr);
+    hipLaunchKernelGGL((k_cl_cols<TV, MODE>), dim3(cs_tiles(P.N, kBlock)), dim3(kBlock), 0, st, P, nz, v, y, V, mu, kind, s->S.rtol, s->S.d_scal, s->S.d_words, s->S.d_part);
 }
 
 int fd_csc_lsq_matvec_async(fd_csc_lsq *s, const void *nzval, const void *v, void *y, int transpose)
@@ -428,9 +285,9 @@ int fd_csc_lsq_solve_async(fd_csc_lsq *s, double mu, int damping_kind, const voi
     const int M = (int)s->L.M, N = (int)s->L.N;
     const real_t *nz = (const real_t *)nzval;
     const ClVecs V = cl_vecs(s);
-    const unsigned gv = cl_tiles(N, kCsVecTile), gu = cl_tiles(M > N ? M : N, kCsVecTile);
+    const unsigned gv = cs_tiles(N, kCsVecTile), gu = cs_tiles(M > N ? M : N, kCsVecTile);
     FD_HIP_CHECK(hipMemsetAsync(S.d_words, 0, sizeof(int) * W_NWORDS, st));
-    hipLaunchKernelGGL(k_cl_start, dim3(cl_tiles(M, kCsVecTile)), dim3(kBlock), 0, st, M, (const real_t *)b, V.r);
+    hipLaunchKernelGGL(k_cl_start, dim3(cs_tiles(M, kCsVecTile)), dim3(kBlock), 0, st, M, (const real_t *)b, V.r);
     cl_product_cols<double, 1>(s, nz, V.r, V.s, mu, damping_kind);
     const int rc = S.run(st, [&] {      // one iteration: 4 launches (+ 1 with long rows, + 1 with long columns)
         cl_product_rows<double, 1>(s, nz, V.p, V.q, mu, true);
@@ -439,7 +296,7 @@ int fd_csc_lsq_solve_async(fd_csc_lsq *s, double mu, int damping_kind, const voi
         hipLaunchKernelGGL(k_cl_p, dim3(gv), dim3(kBlock), 0, st, N, damping_kind, V, S.d_scal, S.d_words, S.d_part);
     });
     if (rc != FD_OK) return rc;
-    hipLaunchKernelGGL(k_cl_final, dim3(cl_tiles(M > N ? M : N, kBlock)), dim3(kBlock), 0, st, M, N, V, (real_t *)y, (real_t *)r_out, S.d_words, S.keep);
+    hipLaunchKernelGGL(k_cl_final, dim3(cs_tiles(M > N ? M : N, kBlock)), dim3(kBlock), 0, st, M, N, V, (real_t *)y, (real_t *)r_out, S.d_words, S.keep);
     FD_HIP_CHECK(hipGetLastError());
     S.solved = true;
     return FD_OK;
@@ -450,10 +307,8 @@ int fd_csc_lsq_status(fd_csc_lsq *s, int *flags_out, int64_t *iterations_out, do
     FD_REQUIRE(s != nullptr, FD_ERR_ARG, "lsq is NULL");
     int w[W_NWORDS];
     double sc[LS_NSCAL];
-    const int rc = s->S.read_status(s->ctx, w, sc);
+    const int rc = s->status(w, sc, flags_out, iterations_out);
     if (rc != FD_OK) return rc;
-    if (flags_out) *flags_out = w[W_FINAL];
-    if (iterations_out) *iterations_out = w[W_ITERS];
     if (grad_norm_out) *grad_norm_out = std::sqrt(sc[LS_GN2]);
     if (grad0_norm_out) *grad0_norm_out = std::sqrt(sc[LS_G02]);
     return FD_OK;

@@ -5,7 +5,8 @@
 //
 // CREATE is the shared builder's (fdjac_csc_pattern.hip), with the diagonal's slots and the pattern's reach.
 //
-// ORDERS.  Row r of at most kCsLong entries: acc = 0; acc += nzval[slot_k] * v[col_k] for k ascending; y_r = alpha v_r + beta acc.
+// ORDERS.  (The product scaffold -- cs_gather_sum, k_cs_long, cs_tile_lines -- is fdjac_csc_common.h's, shared with the other consumers.)
+// Row r of at most kCsLong entries: acc = 0; acc += nzval[slot_k] * v[col_k] for k ascending; y_r = alpha v_r + beta acc.
 // A longer row is summed by ONE workgroup: thread t adds the entries k = t, t + 256, ... in that order, then block_sum().
 // block_sum(): in every wavefront x += shfl_down(x, 32), 16, 8, 4, 2, 1; then ((w0 + w1) + w2) + w3.
 // A dot over N elements: tiles of kCsVecTile (vector kernels: thread t adds elements t, t + 256, t + 512, t + 768 of its tile) or of 256
@@ -47,7 +48,6 @@
 #include "fdjac_device.h"
 #include "fdjac_csc_common.h"
 #include <cmath>
-#include <new>
 #include <vector>
 
 namespace fdjac {
@@ -60,33 +60,15 @@ constexpr int kCsPcIlu = 2;            // pc_kind of block ILU(0): the solver's 
 // scalars of a solve, in device memory: doubles ...
 enum { S_RHO = 0, S_RHO_OLD, S_ALPHA, S_OMEGA, S_BNORM2, S_TOL2, S_RNORM2, S_SNORM2, S_NSCAL };      // (the words and the record: fdjac_csc_common.h)
 
-struct CsPat {                         // the pattern as the kernels see it
-    int N, nnz, nlong, reach, window;
-    const int *colptr, *rowval, *row_ptr, *row_col, *row_slot, *order, *long_rows, *diag;
-};
-
 // ---- products --------------------------------------------------------------------------------------------------------------------------
-// long rows first: workgroup i sums row long_rows[i] and writes y there; the row kernel then takes those values from y
-template <typename TV>
-__global__ void __launch_bounds__(kBlock) k_cs_long(CsPat P, double alpha, double beta, const real_t *__restrict__ nz,
-                                                    const TV *__restrict__ v, TV *__restrict__ y, const int *words)
-{
-    __shared__ double s_w[kBlock / 64];
-    if (words && cs_word(words, W_DONE)) return;
-    const int r = P.long_rows[blockIdx.x], a = P.row_ptr[r], n = P.row_ptr[r + 1] - a;
-    double acc = 0.0;
-    for (int k = threadIdx.x; k < n; k += kBlock) acc += (double)nz[P.row_slot[a + k]] * (double)v[P.row_col[a + k]];
-    const double t = cs_block_sum(acc, s_w);
-    if (threadIdx.x == 0) y[r] = (TV)(alpha * (double)v[r] + beta * t);
-}
-
-// rows: a tile of 256 rows per workgroup, lane i takes row order[tile * 256 + i]; when the pattern's reach is at most kCsWinHalo, v
+// The long rows first (k_cs_long<false, CS_LONG_AXPBY>: y_r = alpha v_r + beta sum), then the rows.
+// rows: a tile of 256 rows per workgroup, lane i takes row row_order[tile * 256 + i] (cs_tile_lines); when the pattern's reach is at most kCsWinHalo, v
 // goes through an LDS window of the tile's rows and `reach` elements on either side (anything outside it is read from memory: the
 // bits do not depend on the window); a wider pattern reads v from memory; the results cross LDS once so that y is
 // written -- and the dots are summed -- in row order.  MODE 0: y only.  1: + dot(c, y) -> alpha (the first product of an
 // iteration).  2: + dot(y, c), dot(y, y) -> omega (the second).
 template <typename TV, int MODE>
-__global__ void __launch_bounds__(kBlock) k_cs_rows(CsPat P, double alpha, double beta, const real_t *__restrict__ nz, const TV *__restrict__ v,
+__global__ void __launch_bounds__(kBlock) k_cs_rows(CsView P, double alpha, double beta, const real_t *__restrict__ nz, const TV *__restrict__ v,
                                                     TV *__restrict__ y, const double *__restrict__ c, double *scal, int *words, double *part)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
@@ -106,31 +88,9 @@ __global__ void __launch_bounds__(kBlock) k_cs_rows(CsPat P, double alpha, doubl
         for (int i = w0 + threadIdx.x; i < w1; i += kBlock) s_v[i - w0] = v[i];
         __syncthreads();
     }
-    const int r = P.order[r0 + threadIdx.x];
-    if (r >= 0) {
-        const int a = P.row_ptr[r], n = P.row_ptr[r + 1] - a;
-        if (n <= kCsLong) {
-            double acc = 0.0;
-            for (int k0 = 0; k0 < n; k0 += 8) {      // eight entries' gathers requested before the first is used
-                double pa[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pv[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    if (k0 + k < n) {
-                        const int col = P.row_col[a + k0 + k];
-                        pa[k] = (double)nz[P.row_slot[a + k0 + k]];
-                        pv[k] = (col >= w0 && col < w1) ? (double)s_v[col - w0] : (double)v[col];
-                    }
-                }
-#pragma unroll
-                for (int k = 0; k < 8; ++k) if (k0 + k < n) acc += pa[k] * pv[k];
-            }
-            const double vr = (r >= w0 && r < w1) ? (double)s_v[r - w0] : (double)v[r];
-            s_out[r - r0] = alpha * vr + beta * acc;
-        } else {
-            s_out[r - r0] = (double)y[r];         // k_cs_long has written it
-        }
-    }
-    __syncthreads();
+    // (captures by value: that keeps the Float64 instances at 64 VGPRs)
+    const auto vec = [=](int i) { return (i >= w0 && i < w1) ? (double)s_v[i - w0] : (double)v[i]; };
+    cs_tile_lines<false, false>(P, r0, nz, y, nullptr, s_out, nullptr, vec, [=](int r, double acc) { return alpha * vec(r) + beta * acc; });
     const int row = r0 + threadIdx.x;
     double yr = 0.0;
     if (row < P.N) {
@@ -153,7 +113,7 @@ __global__ void __launch_bounds__(kBlock) k_cs_rows(CsPat P, double alpha, doubl
 }
 
 // the transposed product on the CSC arrays as they are: one lane per column, storage order
-__global__ void __launch_bounds__(kBlock) k_cs_cols(CsPat P, double alpha, double beta, const real_t *__restrict__ nz, const real_t *__restrict__ v,
+__global__ void __launch_bounds__(kBlock) k_cs_cols(CsView P, double alpha, double beta, const real_t *__restrict__ nz, const real_t *__restrict__ v,
                                                     real_t *__restrict__ y)
 {
     const int nb = (P.N + kBlock - 1) / kBlock, b = (int)fd_xcd_block(blockIdx.x, nb);
@@ -169,7 +129,7 @@ struct CsVecs { double *r, *rhat, *p, *v, *s, *t, *ph, *sh, *y, *d; };
 
 // the start: d = alpha + beta J_ii, r = rhat = b, p = v = y = 0, rho = ||b||^2  (PC = 1, block Jacobi: no d; k_cs_binv follows)
 template <int PC>
-__global__ void __launch_bounds__(kBlock) k_cs_init(CsPat P, CsVecs V, double alpha, double beta, const real_t *__restrict__ nz,
+__global__ void __launch_bounds__(kBlock) k_cs_init(CsView P, CsVecs V, double alpha, double beta, const real_t *__restrict__ nz,
                                                     const real_t *__restrict__ b, double rtol, double *scal, int *words, double *part)
 {
     __shared__ double s_w[kBlock / 64];
@@ -287,7 +247,7 @@ __global__ void __launch_bounds__(kBlock) k_cs_update(int N, CsVecs V, double *s
 // the companion; lane i < n also forms row i's factor f_i of every step.  A lane writes only its own column and column j is dead from
 // step j on (it is neither swapped nor updated: nothing reads it again), so a step needs two barriers: behind the factors and behind the
 // update.  Every loop runs to bs and every barrier is met by all threads whatever the block's length n (0: a wavefront without a block).
-__global__ void __launch_bounds__(kCsBinvWaves * 64) k_cs_binv(CsPat P, int bs, double alpha, double beta, const real_t *__restrict__ nz,
+__global__ void __launch_bounds__(kCsBinvWaves * 64) k_cs_binv(CsView P, int bs, double alpha, double beta, const real_t *__restrict__ nz,
                                                                 double *__restrict__ minv, int *words)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
@@ -379,7 +339,7 @@ struct CsIlu {                         // the schedule as the kernels see it (de
 // factor: one workgroup per block, level by level (the forward levels: row i reads the rows k of its in-block lower entries), thread t
 // takes rows t, t + 256, ... of the level, one lane per row.  lu and u are written and read by the same workgroup across its barriers:
 // plain pointers, so that every read is a vector load behind the barrier's fence.
-__global__ void __launch_bounds__(kBlock) k_cs_ilu_factor(CsPat P, CsIlu I, double alpha, double beta, const real_t *__restrict__ nz,
+__global__ void __launch_bounds__(kBlock) k_cs_ilu_factor(CsView P, CsIlu I, double alpha, double beta, const real_t *__restrict__ nz,
                                                           double *lu, double *u, int *words)
 {
     const int b0 = blockIdx.x * I.bs, nlev = I.nlev_f[blockIdx.x];
@@ -420,7 +380,7 @@ __global__ void __launch_bounds__(kBlock) k_cs_ilu_factor(CsPat P, CsIlu I, doub
 }
 // z = (L U)^-1 x per block: x through LDS, the forward levels (level 0 has nothing to subtract), the backward levels, then out
 template <int WHICH>      // 0: ph from p; 1: sh from s (not needed once the half step has converged)
-__global__ void __launch_bounds__(kBlock) k_cs_ilu_apply(CsPat P, CsIlu I, const double *__restrict__ lu, const double *__restrict__ u,
+__global__ void __launch_bounds__(kBlock) k_cs_ilu_apply(CsView P, CsIlu I, const double *__restrict__ lu, const double *__restrict__ u,
                                                          const double *__restrict__ x, double *__restrict__ out, const int *words)
 {
     __shared__ double s_z[kCsIluBsMax];
@@ -466,12 +426,8 @@ __global__ void __launch_bounds__(kBlock) k_cs_final(int N, const double *__rest
 
 }  // namespace fdjac
 
-struct fd_csc_solver {
-    fd_ctx *ctx = nullptr;
-    fdjac::CscLists L;                 // (fdjac_csc_pattern.hip)
-    fdjac::CscSolveState S;
+struct fd_csc_solver : fdjac::CscHandle {      // d_vec: ten vectors of N doubles
     int window = 1;
-    double *d_vec = nullptr;           // ten vectors of N doubles
     int pc_kind = FD_CSC_PRECOND_JACOBI, pc_bs = 0;      // what the next solve uses
     double *d_minv = nullptr;          // block Jacobi: minv_bs planes of N doubles (allocated by the first solve that needs them)
     size_t minv_cap = 0;               // doubles allocated
@@ -481,75 +437,38 @@ struct fd_csc_solver {
     bool ilu_factored = false;         // a block-ILU solve has run on this schedule
     int *d_ilu_int = nullptr;          // run (4 N) | lev_f | lev_b | ord_f | ord_b (N each) | off_f | off_b (nblk (bs + 1) each) | nlev_f | nlev_b (nblk each)
     double *d_ilu = nullptr;
+    ~fd_csc_solver()
+    {
+        if (d_minv) (void)hipFree(d_minv);
+        if (d_ilu_int) (void)hipFree(d_ilu_int);
+        if (d_ilu) (void)hipFree(d_ilu);
+    }
 };
 
 using namespace fdjac;
 
-static void csc_solver_free(fd_csc_solver *s)
-{
-    csc_lists_free(&s->L);
-    s->S.free();
-    if (s->d_vec) (void)hipFree(s->d_vec);
-    if (s->d_minv) (void)hipFree(s->d_minv);
-    if (s->d_ilu_int) (void)hipFree(s->d_ilu_int);
-    if (s->d_ilu) (void)hipFree(s->d_ilu);
-    delete s;
-}
-
-static CsPat csc_pat(const fd_csc_solver *s)
-{
-    const CscLists &L = s->L;
-    CsPat P;
-    P.N = (int)L.N; P.nnz = (int)L.nnz; P.nlong = L.nlong_r; P.reach = L.reach; P.window = s->window;
-    P.colptr = L.colptr; P.rowval = L.rowval; P.row_ptr = L.row_ptr; P.row_col = L.row_col; P.row_slot = L.row_slot;
-    P.order = L.row_order; P.long_rows = L.long_rows; P.diag = L.diag;
-    return P;
-}
 static size_t csc_win_bytes(const fd_csc_solver *s, size_t elem)
 {
     if (!s->window) return 0;
     return (size_t)(kBlock + 2 * s->L.reach) * elem;
 }
 
-static int csc_solver_init(fd_csc_solver *s, fd_ctx *ctx, int64_t N, const void *colptr, const void *rowval, int idx_bytes, int idx_base, int idx_kind)
-{
-    const char *who = "csc solver";
-    const int rc = csc_lists_build(ctx, who, N, N, colptr, rowval, idx_bytes, idx_base, idx_kind, CSC_WANT_DIAG, &s->L);
-    if (rc != FD_OK) return rc;
-    s->ctx = ctx;
-    if (const char *v = test_switch("FDJAC_CSC_WINDOW")) s->window = atoi(v) != 0;
-    // the LDS window of v only when the measured reach allows it: every column a tile's rows can name then lies inside the window;
-    // a wider pattern would stage 2 * kCsWinHalo elements per tile to serve the near-diagonal gathers alone
-    if (s->L.reach > kCsWinHalo) s->window = 0;
-    CSC_TRY(who, hipMalloc((void **)&s->d_vec, sizeof(double) * 10 * (size_t)N));
-    return s->S.create(who, ctx->stream, S_NSCAL, 2 * ((N + kBlock - 1) / kBlock));
-}
-
 int fd_csc_solver_create(fd_ctx *ctx, int64_t N, const void *colptr, const void *rowval, int idx_bytes, int idx_base, int idx_kind,
                          fd_csc_solver **out)
 {
-    FD_REQUIRE(out != nullptr, FD_ERR_ARG, "NULL argument");
-    *out = nullptr;
-    fd_csc_solver *s = new (std::nothrow) fd_csc_solver();
-    FD_REQUIRE(s != nullptr, FD_ERR_NOMEM, "out of host memory");
-    const int rc = csc_solver_init(s, ctx, N, colptr, rowval, idx_bytes, idx_base, idx_kind);
-    if (rc != FD_OK) {
-        if (s->ctx) (void)hipStreamSynchronize(s->ctx->stream);
-        csc_solver_free(s);
-        return rc;
-    }
-    *out = s;
-    return FD_OK;
+    return csc_handle_create(out, [&](fd_csc_solver *s) -> int {
+        const int rc = s->init(ctx, "csc solver", N, N, colptr, rowval, idx_bytes, idx_base, idx_kind, CSC_WANT_DIAG, 10 * (size_t)N, S_NSCAL,
+                               2 * (int64_t)cs_tiles(N, kBlock));
+        if (rc != FD_OK) return rc;
+        if (const char *v = test_switch("FDJAC_CSC_WINDOW")) s->window = atoi(v) != 0;
+        // the LDS window of v only when the measured reach allows it: every column a tile's rows can name then lies inside the window;
+        // a wider pattern would stage 2 * kCsWinHalo elements per tile to serve the near-diagonal gathers alone
+        if (s->L.reach > kCsWinHalo) s->window = 0;
+        return FD_OK;
+    });
 }
 
-int fd_csc_solver_destroy(fd_csc_solver *s)
-{
-    if (!s) return FD_OK;
-    (void)hipSetDevice(s->ctx->device);
-    (void)hipStreamSynchronize(s->ctx->stream);
-    csc_solver_free(s);
-    return FD_OK;
-}
+int fd_csc_solver_destroy(fd_csc_solver *s) { return csc_handle_destroy(s); }
 
 int fd_csc_solver_set_options(fd_csc_solver *s, double rtol, int max_iterations)
 {
@@ -560,8 +479,7 @@ int fd_csc_solver_set_options(fd_csc_solver *s, double rtol, int max_iterations)
 int fd_csc_solver_set_policy(fd_csc_solver *s, int keep_unconverged)
 {
     FD_REQUIRE(s != nullptr, FD_ERR_ARG, "solver is NULL");
-    s->S.keep = keep_unconverged ? 1 : 0;
-    return FD_OK;
+    return s->S.set_policy(keep_unconverged);
 }
 
 int fd_csc_solver_set_preconditioner(fd_csc_solver *s, int kind, int block_size)
@@ -721,11 +639,10 @@ template <typename TV, int MODE>
 static void csc_product(fd_csc_solver *s, double alpha, double beta, const real_t *nz, const TV *v, TV *y, const double *c, bool guarded)
 {
     hipStream_t st = s->ctx->stream;
-    const CsPat P = csc_pat(s);
-    const int ntile = (int)((s->L.N + kBlock - 1) / kBlock);
-    if (P.nlong > 0)
-        hipLaunchKernelGGL((k_cs_long<TV>), dim3((unsigned)P.nlong), dim3(kBlock), 0, st, P, alpha, beta, nz, v, y, guarded ? (const int *)s->S.d_words : (const int *)nullptr);
-    hipLaunchKernelGGL((k_cs_rows<TV, MODE>), dim3(MODE == 0 ? fd_xcd_grid(ntile) : (unsigned)ntile), dim3(kBlock), csc_win_bytes(s, sizeof(TV)), st, P, alpha, beta,
+    const CsView P = cs_view(s->L, s->window);
+    const unsigned ntile = cs_tiles(s->L.N, kBlock);
+    cs_launch_long<false, CS_LONG_AXPBY>(st, P, nz, v, y, guarded ? s->S.d_words : nullptr, alpha, beta);
+    hipLaunchKernelGGL((k_cs_rows<TV, MODE>), dim3(MODE == 0 ? fd_xcd_grid(ntile) : ntile), dim3(kBlock), csc_win_bytes(s, sizeof(TV)), st, P, alpha, beta,
                        nz, v, y, c, s->S.d_scal, s->S.d_words, s->S.d_part);
 }
 
@@ -735,8 +652,8 @@ int fd_csc_matvec_async(fd_csc_solver *s, double alpha, double beta, const void 
     FD_REQUIRE(v != y, FD_ERR_ARG, "y must not be v");
     FD_HIP_CHECK(hipSetDevice(s->ctx->device));
     if (transpose) {
-        const int nb = (int)((s->L.N + kBlock - 1) / kBlock);
-        hipLaunchKernelGGL(k_cs_cols, dim3(fd_xcd_grid(nb)), dim3(kBlock), 0, s->ctx->stream, csc_pat(s), alpha, beta, (const real_t *)nzval, (const real_t *)v, (real_t *)y);
+        hipLaunchKernelGGL(k_cs_cols, dim3(fd_xcd_grid(cs_tiles(s->L.N, kBlock))), dim3(kBlock), 0, s->ctx->stream, cs_view(s->L, s->window), alpha, beta,
+                           (const real_t *)nzval, (const real_t *)v, (real_t *)y);
     } else {
         csc_product<real_t, 0>(s, alpha, beta, (const real_t *)nzval, (const real_t *)v, (real_t *)y, nullptr, false);
     }
@@ -751,64 +668,57 @@ int fd_csc_solve_async(fd_csc_solver *s, double alpha, double beta, const void *
     hipStream_t st = s->ctx->stream;
     CscSolveState &S = s->S;
     const int N = (int)s->L.N;
+    const size_t n = (size_t)N;
     const real_t *nz = (const real_t *)nzval;
     CsVecs V;
-    double **vp[] = {&V.r, &V.rhat, &V.p, &V.v, &V.s, &V.t, &V.ph, &V.sh, &V.y, &V.d};
-    for (int k = 0; k < 10; ++k) *vp[k] = s->d_vec + (size_t)k * (size_t)N;
-    const CsPat P = csc_pat(s);
-    const unsigned gv = (unsigned)((N + kCsVecTile - 1) / kCsVecTile);
+    s->slice({{&V.r, n}, {&V.rhat, n}, {&V.p, n}, {&V.v, n}, {&V.s, n}, {&V.t, n}, {&V.ph, n}, {&V.sh, n}, {&V.y, n}, {&V.d, n}});
+    const CsView P = cs_view(s->L, s->window);
+    const unsigned gv = cs_tiles(N, kCsVecTile);
     const int bs = s->pc_kind == FD_CSC_PRECOND_BLOCK_JACOBI ? s->pc_bs : 0;
-    if (bs > 0 && s->minv_cap < (size_t)bs * (size_t)N) {
+    if (bs > 0 && s->minv_cap < (size_t)bs * n) {
         FD_HIP_CHECK(hipStreamSynchronize(st));
         if (s->d_minv) (void)hipFree(s->d_minv);
         s->d_minv = nullptr; s->minv_cap = 0; s->minv_bs = 0;
-        const hipError_t e = hipMalloc((void **)&s->d_minv, sizeof(double) * (size_t)bs * (size_t)N);
+        const hipError_t e = hipMalloc((void **)&s->d_minv, sizeof(double) * (size_t)bs * n);
         if (e != hipSuccess) { (void)hipGetLastError(); FD_REQUIRE(false, FD_ERR_NOMEM, "block Jacobi: %d planes of %d doubles: %s", bs, N, hipGetErrorString(e)); }
-        s->minv_cap = (size_t)bs * (size_t)N;
+        s->minv_cap = (size_t)bs * n;
     }
     FD_HIP_CHECK(hipMemsetAsync(S.d_words, 0, sizeof(int) * W_NWORDS, st));
-    const bool ilu = s->pc_kind == kCsPcIlu;
+    const bool ilu = s->pc_kind == kCsPcIlu, blocks = ilu || bs > 0;      // blocks: the PC = 1 instances of the vector kernels
     const CsIlu I = ilu ? csc_ilu(s) : CsIlu();
     const unsigned gi = ilu ? (unsigned)ilu_nblk(s, s->ilu_bs) : 0u;
-    double *lu = s->d_ilu, *u = ilu ? s->d_ilu + (size_t)s->L.nnz : nullptr;
+    const double *lu = s->d_ilu, *u = ilu ? s->d_ilu + (size_t)s->L.nnz : nullptr;
+    const double *scal = S.d_scal;
+    const int *words = S.d_words;
+    // precondition `which` (0: p -> ph; 1: s -> sh): out = M^-1 x behind the vector kernel (the diagonal: that kernel has divided already)
+    const auto apply = [&](int which, const double *x, double *out) {
+        if (ilu) hipLaunchKernelGGL(which ? k_cs_ilu_apply<1> : k_cs_ilu_apply<0>, dim3(gi), dim3(kBlock), 0, st, P, I, lu, u, x, out, words);
+        else if (bs > 0) hipLaunchKernelGGL(which ? k_cs_bapply<1> : k_cs_bapply<0>, dim3(gv), dim3(kBlock), 0, st, N, bs, (const double *)s->d_minv, x, out, words);
+    };
+    // the start: init, then factor or invert
+    if (blocks) hipLaunchKernelGGL(k_cs_init<1>, dim3(gv), dim3(kBlock), 0, st, P, V, alpha, beta, nz, (const real_t *)b, S.rtol, S.d_scal, S.d_words, S.d_part);
+    else hipLaunchKernelGGL(k_cs_init<0>, dim3(gv), dim3(kBlock), 0, st, P, V, alpha, beta, nz, (const real_t *)b, S.rtol, S.d_scal, S.d_words, S.d_part);
     if (ilu) {
-        hipLaunchKernelGGL(k_cs_init<1>, dim3(gv), dim3(kBlock), 0, st, P, V, alpha, beta, nz, (const real_t *)b, S.rtol, S.d_scal, S.d_words, S.d_part);
-        hipLaunchKernelGGL(k_cs_ilu_factor, dim3(gi), dim3(kBlock), 0, st, P, I, alpha, beta, nz, lu, u, S.d_words);
+        hipLaunchKernelGGL(k_cs_ilu_factor, dim3(gi), dim3(kBlock), 0, st, P, I, alpha, beta, nz, s->d_ilu, s->d_ilu + (size_t)s->L.nnz, S.d_words);
         s->ilu_factored = true;
     } else if (bs > 0) {
-        const int nblk = (N + bs - 1) / bs;
-        hipLaunchKernelGGL(k_cs_init<1>, dim3(gv), dim3(kBlock), 0, st, P, V, alpha, beta, nz, (const real_t *)b, S.rtol, S.d_scal, S.d_words, S.d_part);
-        hipLaunchKernelGGL(k_cs_binv, dim3((unsigned)((nblk + kCsBinvWaves - 1) / kCsBinvWaves)), dim3(kCsBinvWaves * 64),
+        hipLaunchKernelGGL(k_cs_binv, dim3(cs_tiles(cs_tiles(N, bs), kCsBinvWaves)), dim3(kCsBinvWaves * 64),
                            sizeof(double) * (size_t)kCsBinvWaves * (size_t)(bs * (2 * bs + 1) + bs), st, P, bs, alpha, beta, nz, s->d_minv, S.d_words);
         s->minv_bs = bs;
-    } else {
-        hipLaunchKernelGGL(k_cs_init<0>, dim3(gv), dim3(kBlock), 0, st, P, V, alpha, beta, nz, (const real_t *)b, S.rtol, S.d_scal, S.d_words, S.d_part);
     }
     const int rc = S.run(st, [&] {      // one iteration: 5 launches (+ 2 with long rows, + 2 with block Jacobi or block ILU)
-        if (ilu) {
-            hipLaunchKernelGGL(k_cs_p<1>, dim3(gv), dim3(kBlock), 0, st, N, V, (const double *)S.d_scal, (const int *)S.d_words);
-            hipLaunchKernelGGL(k_cs_ilu_apply<0>, dim3(gi), dim3(kBlock), 0, st, P, I, (const double *)lu, (const double *)u, (const double *)V.p, V.ph, (const int *)S.d_words);
-        } else if (bs > 0) {
-            hipLaunchKernelGGL(k_cs_p<1>, dim3(gv), dim3(kBlock), 0, st, N, V, (const double *)S.d_scal, (const int *)S.d_words);
-            hipLaunchKernelGGL(k_cs_bapply<0>, dim3(gv), dim3(kBlock), 0, st, N, bs, (const double *)s->d_minv, (const double *)V.p, V.ph, (const int *)S.d_words);
-        } else {
-            hipLaunchKernelGGL(k_cs_p<0>, dim3(gv), dim3(kBlock), 0, st, N, V, (const double *)S.d_scal, (const int *)S.d_words);
-        }
+        if (blocks) hipLaunchKernelGGL(k_cs_p<1>, dim3(gv), dim3(kBlock), 0, st, N, V, scal, words);
+        else hipLaunchKernelGGL(k_cs_p<0>, dim3(gv), dim3(kBlock), 0, st, N, V, scal, words);
+        apply(0, V.p, V.ph);
         csc_product<double, 1>(s, alpha, beta, nz, V.ph, V.v, V.rhat, true);
-        if (ilu) {
-            hipLaunchKernelGGL(k_cs_s<1>, dim3(gv), dim3(kBlock), 0, st, N, V, S.d_scal, S.d_words, S.d_part);
-            hipLaunchKernelGGL(k_cs_ilu_apply<1>, dim3(gi), dim3(kBlock), 0, st, P, I, (const double *)lu, (const double *)u, (const double *)V.s, V.sh, (const int *)S.d_words);
-        } else if (bs > 0) {
-            hipLaunchKernelGGL(k_cs_s<1>, dim3(gv), dim3(kBlock), 0, st, N, V, S.d_scal, S.d_words, S.d_part);
-            hipLaunchKernelGGL(k_cs_bapply<1>, dim3(gv), dim3(kBlock), 0, st, N, bs, (const double *)s->d_minv, (const double *)V.s, V.sh, (const int *)S.d_words);
-        } else {
-            hipLaunchKernelGGL(k_cs_s<0>, dim3(gv), dim3(kBlock), 0, st, N, V, S.d_scal, S.d_words, S.d_part);
-        }
+        if (blocks) hipLaunchKernelGGL(k_cs_s<1>, dim3(gv), dim3(kBlock), 0, st, N, V, S.d_scal, S.d_words, S.d_part);
+        else hipLaunchKernelGGL(k_cs_s<0>, dim3(gv), dim3(kBlock), 0, st, N, V, S.d_scal, S.d_words, S.d_part);
+        apply(1, V.s, V.sh);
         csc_product<double, 2>(s, alpha, beta, nz, V.sh, V.t, V.s, true);
         hipLaunchKernelGGL(k_cs_update, dim3(gv), dim3(kBlock), 0, st, N, V, S.d_scal, S.d_words, S.d_part);
     });
     if (rc != FD_OK) return rc;
-    hipLaunchKernelGGL(k_cs_final, dim3((unsigned)((N + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, N, (const double *)V.y, (real_t *)y, S.d_words, S.keep);
+    hipLaunchKernelGGL(k_cs_final, dim3(cs_tiles(N, kBlock)), dim3(kBlock), 0, st, N, (const double *)V.y, (real_t *)y, S.d_words, S.keep);
     FD_HIP_CHECK(hipGetLastError());
     S.solved = true;
     return FD_OK;

@@ -6,7 +6,8 @@
 //
 // CREATE is the shared builder's (fdjac_csc_pattern.hip), with the diagonal's slots.  Symmetry is the caller's contract: not checked.
 //
-// ORDERS.  Row r of at most kCsLong entries: acc = 0; acc += nzval[slot_k] * v[col_k], k ascending (ascending column); a longer row by
+// ORDERS.  (The product scaffold -- cs_gather_sum, k_cs_long, cs_tile_lines -- is fdjac_csc_common.h's, shared with the other consumers.)
+// Row r of at most kCsLong entries: acc = 0; acc += nzval[slot_k] * v[col_k], k ascending (ascending column); a longer row by
 // one workgroup: thread t adds entries t, t + 256, ... in that order, then block_sum().  Then q_r = acc + lambda * v_r.  No LDS window of
 // v.  A tile's results cross LDS once, so that q is written -- and p.q summed -- in row order.  The dot of the row kernel: tiles of 256
 // (element t); dots of the vector kernels: tiles of kCsVecTile (thread t adds t, t + 256, t + 512, t + 768); block_sum() per tile, the
@@ -28,7 +29,6 @@
 #include "fdjac_device.h"
 #include "fdjac_csc_common.h"
 #include <cmath>
-#include <new>
 
 namespace fdjac {
 
@@ -37,62 +37,22 @@ enum { TR_GAMMA = 0, TR_ALPHA, TR_BETA, TR_PPP, TR_PYP, TR_PYY, TR_TOL2, TR_RHO,
 constexpr int W_EXIT = W_FINAL + 1;    // the exit kind, in one of the free words
 static_assert(W_EXIT < W_NWORDS, "no free word");
 
-struct TrPat {                         // the pattern as the kernels see it
-    int N, nlong;
-    const int *row_ptr, *row_col, *row_slot, *row_order, *long_rows, *diag;
-};
 struct TrVecs { double *r, *q, *y, *p, *z, *m; };      // N doubles each
 
-__device__ __forceinline__ bool tr_not_finite(double x) { return !(fabs(x) < __builtin_huge_val()); }
-
 // ---- the product -----------------------------------------------------------------------------------------------------------------------
-// long rows first: workgroup i sums row long_rows[i] and writes the sum to y there; the row kernel then takes it from y
-__global__ void __launch_bounds__(kBlock) k_tr_long_rows(TrPat P, const double *__restrict__ nz, const double *__restrict__ v,
-                                                         double *__restrict__ y, const int *words)
-{
-    __shared__ double s_w[kBlock / 64];
-    if (words && cs_word(words, W_DONE)) return;
-    const int r = P.long_rows[blockIdx.x], a = P.row_ptr[r], n = P.row_ptr[r + 1] - a;
-    double acc = 0.0;
-    for (int k = threadIdx.x; k < n; k += kBlock) acc += nz[P.row_slot[a + k]] * v[P.row_col[a + k]];
-    const double t = cs_block_sum(acc, s_w);
-    if (threadIdx.x == 0) y[r] = t;
-}
-
-// rows: a tile of 256 rows per workgroup, lane i takes row row_order[tile * 256 + i]; v is read from memory; the sums cross LDS once so
-// that y = sum + lambda v is written -- and v.y summed -- in row order.  MODE 0: y only.  1: q = (H + lambda I) p of an iteration,
-// kappa = p.q, and the last-arriving workgroup decides the step length and the exit.
+// The long rows first (k_cs_long<false, CS_LONG_SUM>), then the rows: a tile of 256 rows per workgroup, lane i takes row
+// row_order[tile * 256 + i]; v is read from memory; the sums cross LDS once (cs_tile_lines) so that y = sum + lambda v is written -- and
+// v.y summed -- in row order.  MODE 0: y only.  1: q = (H + lambda I) p of an iteration, kappa = p.q, and the last-arriving workgroup
+// decides the step length and the exit.
 template <int MODE>
-__global__ void __launch_bounds__(kBlock) k_tr_rows(TrPat P, const double *__restrict__ nz, const double *__restrict__ v, double *__restrict__ y,
+__global__ void __launch_bounds__(kBlock) k_tr_rows(CsView P, const double *__restrict__ nz, const double *__restrict__ v, double *__restrict__ y,
                                                     double lambda, double delta2, double *scal, int *words, double *part)
 {
     __shared__ double s_out[kBlock];
     __shared__ double s_w[kBlock / 64];
     if (MODE != 0 && cs_word(words, W_DONE)) return;
     const int r0 = (int)blockIdx.x * kBlock;
-    const int r = P.row_order[r0 + threadIdx.x];
-    if (r >= 0) {
-        const int a = P.row_ptr[r], n = P.row_ptr[r + 1] - a;
-        if (n <= kCsLong) {
-            double acc = 0.0;
-            for (int k0 = 0; k0 < n; k0 += 8) {      // eight entries' gathers requested before the first is used
-                double pa[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pv[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    if (k0 + k < n) {
-                        pa[k] = nz[P.row_slot[a + k0 + k]];
-                        pv[k] = v[P.row_col[a + k0 + k]];
-                    }
-                }
-#pragma unroll
-                for (int k = 0; k < 8; ++k) if (k0 + k < n) acc += pa[k] * pv[k];
-            }
-            s_out[r - r0] = acc;
-        } else {
-            s_out[r - r0] = y[r];                 // k_tr_long_rows has written it
-        }
-    }
-    __syncthreads();
+    cs_tile_lines<false, false>(P, r0, nz, v, y, nullptr, s_out, nullptr);
     const int row = r0 + threadIdx.x;
     double vr = 0.0, yr = 0.0;
     if (row < P.N) {
@@ -107,10 +67,10 @@ __global__ void __launch_bounds__(kBlock) k_tr_rows(TrPat P, const double *__res
             const double ppp = scal[TR_PPP], pyp = scal[TR_PYP], pyy = scal[TR_PYY];
             const double d = delta2 - pyy;
             const double tau = d / (pyp + __dsqrt_rn(pyp * pyp + ppp * d));      // the root without cancellation (pi_yp >= 0)
-            if (tr_not_finite(kappa)) {
+            if (cs_not_finite(kappa)) {
                 cs_breakdown(words);
             } else if (kappa <= 0.0) {
-                if (tr_not_finite(delta2)) {          // negative curvature and no boundary to follow it to
+                if (cs_not_finite(delta2)) {          // negative curvature and no boundary to follow it to
                     words[W_EXIT] = 3;
                     cs_breakdown(words);
                 } else {
@@ -132,7 +92,7 @@ __global__ void __launch_bounds__(kBlock) k_tr_rows(TrPat P, const double *__res
 
 // ---- the vector kernels ----------------------------------------------------------------------------------------------------------------
 // the start of a solve
-__global__ void __launch_bounds__(kBlock) k_tr_start(TrPat P, int kind, const double *__restrict__ nz, const double *__restrict__ g, TrVecs V,
+__global__ void __launch_bounds__(kBlock) k_tr_start(CsView P, int kind, const double *__restrict__ nz, const double *__restrict__ g, TrVecs V,
                                                      double lambda, double rtol, double *scal, int *words, double *part)
 {
     __shared__ double s_w[kBlock / 64];
@@ -163,7 +123,7 @@ __global__ void __launch_bounds__(kBlock) k_tr_start(TrPat P, int kind, const do
         int done = 0;
         if (tot[1] == 0.0) done = 1;                                             // g = 0: y = 0, no iteration
         else if (cs_word(words, W_FLAGS) & 2) done = 1;                          // an m_j that is zero or not finite
-        else if (tr_not_finite(tot[0])) { atomicOr(words + W_FLAGS, 2); done = 1; }   // gamma
+        else if (cs_not_finite(tot[0])) { atomicOr(words + W_FLAGS, 2); done = 1; }   // gamma
         if (done) __hip_atomic_store(words + W_DONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
@@ -191,7 +151,7 @@ __global__ void __launch_bounds__(kBlock) k_tr_update(int N, TrVecs V, double *s
         words[W_ITERS] = words[W_ITERS] + 1;
         if (words[W_EXIT] != 0 || tot[1] <= scal[TR_TOL2]) {      // the boundary was reached (k_tr_rows), or converged inside
             __hip_atomic_store(words + W_DONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else if (tr_not_finite(tot[0])) {
+        } else if (cs_not_finite(tot[0])) {
             cs_breakdown(words);
         } else {
             scal[TR_BETA] = tot[0] / scal[TR_GAMMA];
@@ -249,74 +209,27 @@ __global__ void __launch_bounds__(kBlock) k_tr_final(int N, TrVecs V, const doub
 
 }  // namespace fdjac
 
-struct fd_csc_tr {
-    fd_ctx *ctx = nullptr;
-    fdjac::CscLists L;                 // (fdjac_csc_pattern.hip)
-    fdjac::CscSolveState S;
-    double *d_vec = nullptr;           // r, q, y, p, z, m (N doubles each)
-};
+struct fd_csc_tr : fdjac::CscHandle {};      // d_vec: r, q, y, p, z, m (N doubles each)
 
 using namespace fdjac;
 
-static void tr_free(fd_csc_tr *s)
-{
-    csc_lists_free(&s->L);
-    s->S.free();
-    if (s->d_vec) (void)hipFree(s->d_vec);
-    delete s;
-}
-
-static TrPat tr_pat(const fd_csc_tr *s)
-{
-    const CscLists &L = s->L;
-    TrPat P;
-    P.N = (int)L.N; P.nlong = L.nlong_r;
-    P.row_ptr = L.row_ptr; P.row_col = L.row_col; P.row_slot = L.row_slot; P.row_order = L.row_order; P.long_rows = L.long_rows; P.diag = L.diag;
-    return P;
-}
 static TrVecs tr_vecs(const fd_csc_tr *s)
 {
     TrVecs V;
     const size_t N = (size_t)s->L.N;
-    V.r = s->d_vec; V.q = V.r + N; V.y = V.q + N; V.p = V.y + N; V.z = V.p + N; V.m = V.z + N;
+    s->slice({{&V.r, N}, {&V.q, N}, {&V.y, N}, {&V.p, N}, {&V.z, N}, {&V.m, N}});
     return V;
-}
-static unsigned tr_tiles(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
-
-static int tr_init(fd_csc_tr *s, fd_ctx *ctx, int64_t N, const void *colptr, const void *rowval, int idx_bytes, int idx_base, int idx_kind)
-{
-    const char *who = "fd_csc_tr_create";
-    const int rc = csc_lists_build(ctx, who, N, N, colptr, rowval, idx_bytes, idx_base, idx_kind, CSC_WANT_DIAG, &s->L);
-    if (rc != FD_OK) return rc;
-    s->ctx = ctx;
-    CSC_TRY(who, hipMalloc((void **)&s->d_vec, sizeof(double) * 6 * (size_t)N));
-    return s->S.create(who, ctx->stream, TR_NSCAL, 3 * ((N + kBlock - 1) / kBlock));
 }
 
 int fd_csc_tr_create(fd_ctx *ctx, int64_t N, const void *colptr, const void *rowval, int idx_bytes, int idx_base, int idx_kind, fd_csc_tr **out)
 {
-    FD_REQUIRE(out != nullptr, FD_ERR_ARG, "NULL argument");
-    *out = nullptr;
-    fd_csc_tr *s = new (std::nothrow) fd_csc_tr();
-    FD_REQUIRE(s != nullptr, FD_ERR_NOMEM, "out of host memory");
-    const int rc = tr_init(s, ctx, N, colptr, rowval, idx_bytes, idx_base, idx_kind);
-    if (rc != FD_OK) {
-        if (s->ctx) (void)hipStreamSynchronize(s->ctx->stream);
-        tr_free(s);
-        return rc;
-    }
-    *out = s;
-    return FD_OK;
+    return csc_handle_create(out, [&](fd_csc_tr *s) {
+        return s->init(ctx, "fd_csc_tr_create", N, N, colptr, rowval, idx_bytes, idx_base, idx_kind, CSC_WANT_DIAG, 6 * (size_t)N, TR_NSCAL,
+                       3 * (int64_t)cs_tiles(N, kBlock));
+    });
 }
 
-int fd_csc_tr_destroy(fd_csc_tr *s)
-{
-    if (!s) return FD_OK;
-    (void)hipSetDevice(s->ctx->device);
-    (void)hipStreamSynchronize(s->ctx->stream);
-    tr_free(s);
-    return FD_OK;
-}
+int fd_csc_tr_destroy(fd_csc_tr *s) { return csc_handle_destroy(s); }
 
 int fd_csc_tr_set_options(fd_csc_tr *s, double rtol, int max_iterations)
 {
@@ -327,8 +240,7 @@ int fd_csc_tr_set_options(fd_csc_tr *s, double rtol, int max_iterations)
 int fd_csc_tr_set_policy(fd_csc_tr *s, int keep_unconverged)
 {
     FD_REQUIRE(s != nullptr, FD_ERR_ARG, "tr is NULL");
-    s->S.keep = keep_unconverged ? 1 : 0;
-    return FD_OK;
+    return s->S.set_policy(keep_unconverged);
 }
 
 // q = (H + lambda I) v on the stream: the long rows, then the tiles
@@ -336,10 +248,9 @@ template <int MODE>
 static void tr_product(fd_csc_tr *s, const double *nz, const double *v, double *y, double lambda, double delta2)
 {
     hipStream_t st = s->ctx->stream;
-    const TrPat P = tr_pat(s);
-    if (P.nlong > 0)
-        hipLaunchKernelGGL(k_tr_long_rows, dim3((unsigned)P.nlong), dim3(kBlock), 0, st, P, nz, v, y, MODE ? (const int *)s->S.d_words : (const int *)nullptr);
-    hipLaunchKernelGGL((k_tr_rows<MODE>), dim3(tr_tiles(P.N, kBlock)), dim3(kBlock), 0, st, P, nz, v, y, lambda, delta2, s->S.d_scal, s->S.d_words, s->S.d_part);
+    const CsView P = cs_view(s->L);
+    cs_launch_long<false, CS_LONG_SUM>(st, P, nz, v, y, MODE ? s->S.d_words : nullptr);
+    hipLaunchKernelGGL((k_tr_rows<MODE>), dim3(cs_tiles(P.N, kBlock)), dim3(kBlock), 0, st, P, nz, v, y, lambda, delta2, s->S.d_scal, s->S.d_words, s->S.d_part);
 }
 
 static bool tr_lambda_ok(double lambda) { return lambda >= 0.0 && lambda < HUGE_VAL; }      // (a NaN fails the comparison)
@@ -367,8 +278,8 @@ int fd_csc_tr_step_async(fd_csc_tr *s, double lambda, double radius, int norm_ki
     const int N = (int)s->L.N;
     const double *nz = (const double *)nzval;
     const TrVecs V = tr_vecs(s);
-    const TrPat P = tr_pat(s);
-    const unsigned gv = tr_tiles(N, kCsVecTile);
+    const CsView P = cs_view(s->L);
+    const unsigned gv = cs_tiles(N, kCsVecTile);
     const double delta2 = radius * radius;      // +Inf (radius >= 1.35e154): no boundary
     FD_HIP_CHECK(hipMemsetAsync(S.d_words, 0, sizeof(int) * W_NWORDS, st));
     hipLaunchKernelGGL(k_tr_start, dim3(gv), dim3(kBlock), 0, st, P, norm_kind, nz, (const double *)g, V, lambda, S.rtol, S.d_scal, S.d_words, S.d_part);
@@ -390,11 +301,9 @@ int fd_csc_tr_status(fd_csc_tr *s, int *flags_out, int *exit_out, int64_t *itera
     FD_REQUIRE(s != nullptr, FD_ERR_ARG, "tr is NULL");
     int w[W_NWORDS];
     double sc[TR_NSCAL];
-    const int rc = s->S.read_status(s->ctx, w, sc);
+    const int rc = s->status(w, sc, flags_out, iterations_out);
     if (rc != FD_OK) return rc;
-    if (flags_out) *flags_out = w[W_FINAL];
     if (exit_out) *exit_out = w[W_EXIT];
-    if (iterations_out) *iterations_out = w[W_ITERS];
     if (resid_out) *resid_out = std::sqrt(sc[TR_RHO]);
     if (g_norm_out) *g_norm_out = std::sqrt(sc[TR_RHO0]);
     if (step_norm_out) *step_norm_out = std::sqrt(sc[TR_YW2]);

@@ -19,7 +19,12 @@ _window2d) is what every "same bits" comparison of the store routes and of the d
 one residual the library ships for any pattern (FD_F_SPARSE, SparseF::row in csrc/fdjac_functor_f.hip: f_r = sum over the pattern's
 entries (r, j) of row r, ascending j, of w(r, j) phi(x_j), one IEEE operation at a time in a fixed order), so the model covers random
 and rectangular patterns, empty rows and columns, greedy / invalid colourings and columns without a colour
-(tests/exact_general.py holds the cases, tests/test_gpu_exact_general.py runs them); to_dense is the dense-J destination."""
+(tests/exact_general.py holds the cases, tests/test_gpu_exact_general.py runs them); to_dense is the dense-J destination.
+
+The complex step.  imag(f(x + i eps mask_c)) / eps with eps = eps(T) for every colour: the residuals restated on explicit (re, im)
+pairs of real arrays (c_add ... c_div_s, tridiag_fc, stencil5_fc, lap7_fc, sparse_fc, colour_values_complex) in the operation order
+of `cd` (csrc/fdjac_builtin_f.hip) and fd_cplx<T> (include/fdjac_device.h); an unperturbed coordinate's imaginary part is +0
+(tests/exact_complex_cases.py holds the cases, tests/test_gpu_exact_complex.py runs them)."""
 import numpy as np
 
 import eps_order
@@ -101,8 +106,9 @@ def stencil5_f(x, nx, ny, nl):
 
 
 def lap7_f(x, nx, ny, nz):
-    """FD_F_LAP7 (lap7_row in csrc/fdjac_functor_f.hip) in x's element type, real or complex: the six neighbours added in the order
-    down, south, west, east, north, up (0 outside the grid), minus 6 times the centre, plus (centre * centre) * east."""
+    """FD_F_LAP7 (lap7_row in csrc/fdjac_functor_f.hip) in x's REAL element type: the six neighbours added in the order down, south,
+    west, east, north, up (0 outside the grid), minus 6 times the centre, plus (centre * centre) * east.  (The complex step's form is
+    lap7_fc below, on explicit (re, im) pairs: numpy's complex dtypes are not used for values.)"""
     T = x.dtype.type
     g = x.reshape(nz, ny, nx)
     d, s, w, e, n, u = (np.zeros_like(g) for _ in range(6))
@@ -151,6 +157,180 @@ def sparse_f(M, N, colptr, rowval, dtype=F64):
                 out[r] = np.cumsum(t[start[r]:start[r] + cnt[r]])[-1]
         return out
     return f
+
+
+# ---- the complex step (src/jacobians.jl:623-648): complex arithmetic as explicit (re, im) pairs -----------------------------------------
+# A complex array is a pair of real arrays of the element type.  Each function below is ONE operator of `cd` (csrc/fdjac_builtin_f.hip)
+# and of fd_cplx<T> (include/fdjac_device.h), one IEEE operation per line of the device code; numpy evaluates every ufunc on its own
+# (no fused multiply-add across two calls), and numpy's complex dtypes -- whose product loops may fuse and whose T(2) * z is a full
+# complex product -- are not used for values.
+def c_add(a, b):
+    return a[0] + b[0], a[1] + b[1]
+
+
+def c_sub(a, b):
+    return a[0] - b[0], a[1] - b[1]
+
+
+def c_mul(a, b):
+    """complex * complex: (ar br - ai bi, ar bi + ai br)."""
+    return a[0] * b[0] - a[1] * b[1], a[0] * b[1] + a[1] * b[0]
+
+
+def c_smul(s, a):
+    """scalar * complex, component-wise: s * (Inf, 0) = (Inf, 0), where the full product has 0 * Inf = NaN in the imaginary part."""
+    return s * a[0], s * a[1]
+
+
+def c_add_s(a, s):
+    return a[0] + s, a[1]
+
+
+def c_sub_s(a, s):
+    return a[0] - s, a[1]
+
+
+def c_div_s(a, s):
+    return a[0] / s, a[1] / s
+
+
+def _shifted(a, fill):
+    """`fill(part)` applied to both parts of a pair."""
+    return fill(a[0]), fill(a[1])
+
+
+def tridiag_fc(x, nl, smul=c_smul):
+    """tridiag_row<cd, NL> on a pair: (xm - 2 x) + xp [+ (x x) xp]; a neighbour outside the domain is the pair (0, 0)."""
+    T = x[0].dtype.type
+    z = np.zeros(1, x[0].dtype)
+    xm = _shifted(x, lambda p: np.concatenate([z, p[:-1]]))
+    xp = _shifted(x, lambda p: np.concatenate([p[1:], z]))
+    v = c_add(c_sub(xm, smul(T(2), x)), xp)
+    if nl:
+        v = c_add(v, c_mul(c_mul(x, x), xp))
+    return v
+
+
+def stencil5_fc(x, nx, ny, nl, smul=c_smul):
+    """stencil5_row<cd, SK> (stencil5_pair, k_f_stencil5): (((w + e) + s) + n) - 4 c [+ (c c) e]."""
+    T = x[0].dtype.type
+
+    def nb(sl_to, sl_from):
+        def fill(p):
+            g = p.reshape(ny, nx)
+            o = np.zeros_like(g)
+            o[sl_to] = g[sl_from]
+            return o
+        return _shifted(x, fill)
+    S = np.s_
+    w, e = nb(S[:, 1:], S[:, :-1]), nb(S[:, :-1], S[:, 1:])
+    s, n = nb(S[1:, :], S[:-1, :]), nb(S[:-1, :], S[1:, :])
+    g = _shifted(x, lambda p: p.reshape(ny, nx))
+    v = c_sub(c_add(c_add(c_add(w, e), s), n), smul(T(4), g))
+    if nl:
+        v = c_add(v, c_mul(c_mul(g, g), e))
+    return v[0].reshape(-1), v[1].reshape(-1)
+
+
+def lap7_fc(x, nx, ny, nz, smul=c_smul):
+    """lap7_row<cd>: ((((((d + s) + w) + e) + n) + u) - 6 c) + (c c) e."""
+    T = x[0].dtype.type
+
+    def nb(sl_to, sl_from):
+        def fill(p):
+            g = p.reshape(nz, ny, nx)
+            o = np.zeros_like(g)
+            o[sl_to] = g[sl_from]
+            return o
+        return _shifted(x, fill)
+    S = np.s_
+    d, u = nb(S[1:], S[:-1]), nb(S[:-1], S[1:])
+    s, n = nb(S[:, 1:], S[:, :-1]), nb(S[:, :-1], S[:, 1:])
+    w, e = nb(S[:, :, 1:], S[:, :, :-1]), nb(S[:, :, :-1], S[:, :, 1:])
+    g = _shifted(x, lambda p: p.reshape(nz, ny, nx))
+    v = c_add(c_sub(c_add(c_add(c_add(c_add(c_add(d, s), w), e), n), u), smul(T(6), g)), c_mul(c_mul(g, g), e))
+    return v[0].reshape(-1), v[1].reshape(-1)
+
+
+def sparse_fc(M, N, colptr, rowval, dtype=F64, smul=c_smul):
+    """SparseF::row<cd> on pairs: the entries (r, j) of row r in ascending j, left to right, of w * (v + (q * v) * v) -- q * v and
+    w * (...) scalar * complex, (q v) * v complex * complex; the first term is ASSIGNED, a row without entries is the pair (+0, +0).
+    Both parts of a long row (more than 32 entries) are accumulated strictly sequentially by np.cumsum, as in sparse_f."""
+    T = np.dtype(dtype).type
+    colptr = np.asarray(colptr, np.int64) - 1
+    rows = np.asarray(rowval, np.int64) - 1
+    cols = np.repeat(np.arange(N, dtype=np.int64), np.diff(colptr))
+    order = np.lexsort((cols, rows))
+    rs, cs = rows[order], cols[order]
+    cnt = np.bincount(rs, minlength=M)
+    start = np.concatenate([[0], np.cumsum(cnt)])[:-1]
+    w = (T(1) + T(0.125) * ((rs + 3 * cs) & 7).astype(dtype)).astype(dtype)
+    q = T(0.25)
+    short = np.nonzero(cnt <= 32)[0]
+    long_rows = np.nonzero(cnt > 32)[0]
+    depth = int(cnt[short].max()) if short.size else 0
+    level = [(short[cnt[short] > k], start[short[cnt[short] > k]] + k) for k in range(depth)]
+
+    def f(x):
+        assert x[0].dtype == np.dtype(dtype) and x[1].dtype == np.dtype(dtype) and x[0].size == N, (x[0].dtype, x[0].size)
+        with np.errstate(all="ignore"):
+            v = (x[0][cs], x[1][cs])
+            t = smul(w, c_add(v, c_mul(smul(q, v), v)))
+            out = (np.zeros(M, dtype=dtype), np.zeros(M, dtype=dtype))
+            for k, (sel, at) in enumerate(level):
+                for part in (0, 1):
+                    out[part][sel] = t[part][at] if k == 0 else out[part][sel] + t[part][at]
+            for r in long_rows:
+                for part in (0, 1):
+                    out[part][r] = np.cumsum(t[part][start[r]:start[r] + cnt[r]])[-1]
+        return out
+    return f
+
+
+def fixture_complex(family, *prm, smul=c_smul):
+    """f((re, im)) -> (re, im) of the rational built-in families on pairs of x's dtype (the parameters of `fixture`).  smul: the
+    scalar * complex operator -- the CPU suite swaps in the full complex product to show that the cases tell the two apart."""
+    if family == "sparse":
+        M, N, colptr, rowval = prm
+        fs = {}
+
+        def f(x):
+            if x[0].dtype not in fs:
+                fs[x[0].dtype] = sparse_fc(M, N, colptr, rowval, x[0].dtype, smul)
+            return fs[x[0].dtype](x)
+        return f
+    if family in ("tridiag", "tridiag_nl"):
+        return lambda x: tridiag_fc(x, family == "tridiag_nl", smul)
+    if family == "lap7":
+        nx, ny, nz = prm
+        return lambda x: lap7_fc(x, nx, ny, nz, smul)
+    if family in ("lap5", "lap5_nl"):
+        nx, ny = prm
+        return lambda x: stencil5_fc(x, nx, ny, family == "lap5_nl", smul)
+    raise ValueError(family)
+
+
+def complex_epsilons(C, dtype=F64):
+    """The complex step's step size: eps(T) for every colour, whatever x, relstep and absstep are (src/jacobians.jl:626)."""
+    return np.full(C, np.finfo(dtype).eps, dtype=dtype)
+
+
+def colour_values_complex(f_pairs, x, colors0, C, eps):
+    """D[c][r] = im(f(x + i eps_c mask_c))[r] / eps_c in the element type: k_perturb MODE 2 (the pair (x_j, colour of j == c ? eps_c :
+    +0)), the complex f!, entry_value<2> (the imaginary part's IEEE quotient by eps_c).  No subtraction, no f(x)."""
+    x = np.asarray(x)
+    T = x.dtype.type
+    colors0 = np.asarray(colors0)
+    D = None
+    with np.errstate(all="ignore"):
+        for c in range(C):
+            e = T(eps[c])
+            im = np.where(colors0 == c, e, T(0)).astype(x.dtype)
+            _re, fi = f_pairs((x, im))
+            if D is None:
+                D = np.empty((C, fi.size), dtype=x.dtype)
+            D[c] = fi / e
+    return D if D is not None else np.empty((0, x.size), dtype=x.dtype)
 
 
 def fixture(family, *prm):

@@ -52,18 +52,20 @@ torch = pytest.importorskip("torch")
 
 SPARSE_ROWS = """
 // FD_F_SPARSE's row (csrc/fdjac_functor_f.hip, SparseF::row) from device pointers to the pattern by rows: the entries (r, j) of row r,
-// ascending j, left to right, w(r, j) * (v + (v / 4) v) with w = 1 + ((r + 3 j) mod 8) / 8; the first term is assigned
+// ascending j, left to right, w(r, j) * (v + (v / 4) v) with w = 1 + ((r + 3 j) mod 8) / 8; the first term is assigned.  Generic in the
+// point's value type V (real_t for forward / central differences, fd_cplx<real_t> for the complex step: tests/test_gpu_exact_complex.py)
 struct SparseRows {
     const long long *rp;
     const int *rc;
-    template <class P> __device__ real_t operator()(long long r, const P &X) const
+    template <class P> __device__ typename P::value_type operator()(long long r, const P &X) const
     {
+        typedef typename P::value_type V;
         const long long a = rp[r], b = rp[r + 1];
-        real_t s = 0;
+        V s = V{};
         for (long long k = a; k < b; ++k) {
             const long long j = rc[k];
-            const real_t v = X(j);
-            const real_t t = ((real_t)1 + (real_t)0.125 * (real_t)(int)((r + 3 * j) & 7)) * (v + ((real_t)0.25 * v) * v);
+            const V v = X(j);
+            const V t = ((real_t)1 + (real_t)0.125 * (real_t)(int)((r + 3 * j) & 7)) * (v + ((real_t)0.25 * v) * v);
             s = k == a ? t : s + t;
         }
         return s;

@@ -231,31 +231,49 @@ __device__ __forceinline__ r2_t ld_pair_guarded(const real_t *__restrict__ x, in
     return v;
 }
 
+// the quotient of row j - 1 + k of column j (k = 0 .. 2): xv = x[j - 2 .. j + 2] (row j - 1 + k reads xv[k .. k + 2] only), the point
+// x[j] +- e, every other coordinate x + 0.0 / x - 0.0.  The ONE place the storing wave kernels form a Float64 / pair-form quotient.
+template <int MODE, bool NL>
+__device__ __forceinline__ real_t tridiag_quotient(const real_t *xv, real_t e, int k)
+{
+    const real_t ed = MODE == 1 ? 2 * e : e;
+    real_t p[3], m[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { const real_t dlt = k + i == 2 ? e : (real_t)0; p[i] = xv[k + i] + dlt; m[i] = xv[k + i] - dlt; }
+    const real_t plus = tridiag_row<real_t, NL>(p[0], p[1], p[2]);
+    const real_t sub = MODE == 1 ? tridiag_row<real_t, NL>(m[0], m[1], m[2]) : tridiag_row<real_t, NL>(xv[k], xv[k + 1], xv[k + 2]);
+    return sub_exact(plus, sub) / ed;      // (the shared-reciprocal division measured 2 % slower here: bandwidth, not issue, bounds this kernel)
+}
+
 // the six quotients of a lane's two columns (rows j-1 .. j+1 of column j, then of column j + 1)
 template <int MODE, bool NL>
 __device__ __forceinline__ void tridiag_pair_quotients(const r2_t &L, const r2_t &Cc, const r2_t &R, real_t ea, real_t eb, real_t (&q)[6])
 {
     const real_t xv[6] = {L.x, L.y, Cc.x, Cc.y, R.x, R.y};
 #pragma unroll
-    for (int o = 0; o < 2; ++o) {                             // column j + o: x[j + o] +- e, every other coordinate x + 0.0 / x - 0.0
-        const real_t e = o == 0 ? ea : eb;
-        const real_t ed = MODE == 1 ? 2 * e : e;
-        real_t p[5], m[5];
+    for (int o = 0; o < 2; ++o)                               // column j + o
 #pragma unroll
-        for (int k = 0; k < 5; ++k) { const real_t dlt = k == 2 ? e : (real_t)0; p[k] = xv[o + k] + dlt; m[k] = xv[o + k] - dlt; }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const real_t plus = tridiag_row<real_t, NL>(p[k], p[k + 1], p[k + 2]);
-            const real_t sub = MODE == 1 ? tridiag_row<real_t, NL>(m[k], m[k + 1], m[k + 2])
-                                         : tridiag_row<real_t, NL>(xv[o + k], xv[o + k + 1], xv[o + k + 2]);
-            q[3 * o + k] = sub_exact(plus, sub) / ed;      // (the shared-reciprocal division measured 2 % slower here: bandwidth, not issue, bounds this kernel)
-        }
-    }
+        for (int k = 0; k < 3; ++k) q[3 * o + k] = tridiag_quotient<MODE, NL>(xv + o, o == 0 ? ea : eb, k);
+}
+// the line-aligned emit's seventh value (fd_band_emit_wave_lines' `qnext`): row j + 1 of column j + 2, the first stored value of the
+// column after the lane's pair -- the quotient the next wavefront's lane 0 forms as its q[0], from the same operands
+template <int MODE, bool NL>
+__device__ __forceinline__ real_t tridiag_next_quotient(const r2_t &Cc, const r2_t &R, real_t en)
+{
+    const real_t xv[3] = {Cc.x, Cc.y, R.x};
+    return tridiag_quotient<MODE, NL>(xv, en, 0);
+}
+
+// the colour of a wavefront's first column (the line-aligned placement may start a launch's first wavefront below column 0)
+__device__ __forceinline__ int tridiag_wave_color(int64_t jw, const fd_band_store &bst)
+{
+    const int64_t m = (jw + bst.shift) % bst.C;
+    return (int)(m < 0 ? m + bst.C : m);
 }
 
 template <int MODE, bool NL>
 __global__ void __launch_bounds__(kBlock)
-k_f_tridiag_store_wave(const real_t *__restrict__ x, const real_t *__restrict__ eps, int64_t n, fd_band_store bst, int64_t jstart)
+k_f_tridiag_store_wave(const real_t *__restrict__ x, const real_t *__restrict__ eps, int64_t n, fd_band_store bst, int64_t jstart, int lines)
 {
     __shared__ __attribute__((aligned(16))) real_t s_win[kBlock / 64][FD_BAND_WAVE_LDS(3)];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -266,12 +284,20 @@ k_f_tridiag_store_wave(const real_t *__restrict__ x, const real_t *__restrict__ 
     const int64_t j = jw + 2 * lane;
     const r2_t Cc = ld_pair_guarded(x, j, n), L = ld_pair_guarded(x, j - 2, n), R = ld_pair_guarded(x, j + 2, n);
     // cyclic colours: column j has colour (j + shift) mod C, column j + 1 the next one
-    const int c0w = (int)((jw + bst.shift) % bst.C);         // (wave-uniform 64-bit modulo: scalar unit)
+    const int c0w = tridiag_wave_color(jw, bst);             // (wave-uniform 64-bit modulo: scalar unit)
     const int c0 = (int)((uint32_t)(c0w + 2 * lane) % (uint32_t)bst.C);
     const int c1 = c0 + 1 == bst.C ? 0 : c0 + 1;
     const real_t ea = eps[c0], eb = eps[c1];
+    const real_t en = lines ? eps[(uint32_t)(c0w + 128) % (uint32_t)bst.C] : (real_t)0;      // the step size of column jw + 128
     real_t q[6];
     tridiag_pair_quotients<MODE, NL>(L, Cc, R, ea, eb, q);
+    if (lines) {
+        // line-aligned spans (the launcher placed jstart for them): lane 63 adds the first value of the next wavefront's first column
+        real_t qn = 0;
+        if (lane == 63) qn = tridiag_next_quotient<MODE, NL>(Cc, R, en);
+        fd_band_emit_wave_lines<real_t, true>(&bst, s_win[wave], jw, q, qn);
+        return;
+    }
     fd_band_emit_wave<real_t, 3, true>(&bst, s_win[wave], jw, q);      // (non-temporal: nothing re-reads nzval in this call)
 }
 
@@ -281,7 +307,7 @@ k_f_tridiag_store_wave(const real_t *__restrict__ x, const real_t *__restrict__ 
 // form: same bits.  N = 10^6: one launch instead of two, and a hand-off of two memory round trips instead of six.
 template <int MODE, bool NL, int NC, bool PIPE>
 __global__ void __launch_bounds__(kBlock)
-k_f_tridiag_fused(const real_t *__restrict__ x, int64_t n, fd_band_store bst, int64_t jstart, FusedEps fz)
+k_f_tridiag_fused(const real_t *__restrict__ x, int64_t n, fd_band_store bst, int64_t jstart, int lines, FusedEps fz)
 {
     // one LDS area, carved by role: storing workgroups (4 wave windows + the step sizes), reduction workgroups, finishers
     constexpr int kWinBytes = (kBlock / 64) * FD_BAND_WAVE_LDS(3) * (int)sizeof(real_t);
@@ -315,12 +341,18 @@ k_f_tridiag_fused(const real_t *__restrict__ x, int64_t n, fd_band_store bst, in
     if (wave == 0) fused_wait_eps(fz, cb, s_eps);
     __syncthreads();
     for (; gw < nwaves; gw += gstride) {
-        const int c0w = (int)((jw + bst.shift) % bst.C);
+        const int c0w = tridiag_wave_color(jw, bst);
         const int c0 = (int)((uint32_t)(c0w + 2 * lane) % (uint32_t)bst.C);
         const int c1 = c0 + 1 == bst.C ? 0 : c0 + 1;
         real_t q[6];
         tridiag_pair_quotients<MODE, NL>(L, Cc, R, s_eps[c0], s_eps[c1], q);
-        fd_band_emit_wave<real_t, 3, true>(&bst, s_win[wave], jw, q);
+        if (lines) {
+            real_t qn = 0;
+            if (lane == 63) qn = tridiag_next_quotient<MODE, NL>(Cc, R, s_eps[(uint32_t)(c0w + 128) % (uint32_t)bst.C]);
+            fd_band_emit_wave_lines<real_t, true>(&bst, s_win[wave], jw, q, qn);
+        } else {
+            fd_band_emit_wave<real_t, 3, true>(&bst, s_win[wave], jw, q);
+        }
         // (the next tile's x requested BEFORE this tile is computed was measured: 12 more registers -- 6 instead of 8 wavefronts per
         //  SIMD -- for 0.3 us of a rank's 7.5-us storing phase, and 0.8 us lost at N = 10^6)
         jw = jstart + (gw + gstride) * 128;
@@ -913,6 +945,25 @@ static unsigned fused_grid(K kernel, unsigned tiles_wg, int prefix)
     return (unsigned)prefix + (unsigned)(((int64_t)tiles_wg + rounds - 1) / rounds);
 }
 
+// The line-aligned emit (fd_band_emit_wave_lines; CSC nzval, Float64): the first wavefront's first column for it -- even (the x pairs
+// stay 16-B aligned), at most 14 below the even column the launch would start at otherwise (possibly below 0: columns outside the
+// local range are skipped anyway), and such that out + 8 (3 jstart - entry_begin) lies on a 128-B line:
+// 3 jstart = entry_begin - out / 8 (mod 16), and 3 * 11 = 1 (mod 16).  False -- *jstart untouched, the launch keeps fd_band_emit_wave --
+// when that solution is odd, out is not 8-B aligned, the storage is not CSC, or FDJAC_STORE_LINES=0 (test switch) says so.
+static bool tridiag_lines_jstart(const fd_band_store &bst, int64_t *jstart)
+{
+    if (sizeof(real_t) != 8 || bst.layout != FD_BAND_CSC) return false;
+    const char *sw = fdjac::test_switch("FDJAC_STORE_LINES");
+    if (sw && *sw && atoi(sw) == 0) return false;
+    const uintptr_t o = (uintptr_t)bst.out;
+    if (o & 7) return false;
+    const int64_t r = (int64_t)(((uint64_t)bst.entry_begin - (uint64_t)(o >> 3)) & 15);
+    const int64_t want = (11 * r) & 15;
+    if (want & 1) return false;
+    *jstart -= (*jstart - want) & 15;
+    return true;
+}
+
 template <typename CT>
 static int lazy_tridiag_launch(BuiltinF *b, void *fx, const fd_lazy_points *lp, int64_t fs, int64_t r0, int64_t r1,
                                hipStream_t s)
@@ -965,13 +1016,14 @@ static int lazy_tridiag_launch(BuiltinF *b, void *fx, const fd_lazy_points *lp, 
         }
 #endif
         if (wave_ok) {
-            const int64_t jstart = bst.col_begin & ~(int64_t)1;
+            int64_t jstart = bst.col_begin & ~(int64_t)1;
+            const int lines = tridiag_lines_jstart(bst, &jstart) ? 1 : 0;
             const int64_t nwaves = (bst.col_end - jstart + 127) / 128;
             const unsigned gw = (unsigned)((nwaves + kBlock / 64 - 1) / (kBlock / 64));
             if (lp->eps_job) {
                 // the fused step: this launch also runs the step-size reduction (finisher + reduction workgroups first, see k_f_tridiag_fused)
                 const FusedEps fz = *(const FusedEps *)lp->eps_job;
-#define FD_LAZY_FZP(MODE, NL, NCC, PP) hipLaunchKernelGGL((k_f_tridiag_fused<MODE, NL, NCC, PP>), dim3(fused_grid(k_f_tridiag_fused<MODE, NL, NCC, PP>, gw, fz.eg.C + fz.nblocks)), dim3(kBlock), 0, s, (const real_t *)lp->x, b->prm[0], bst, jstart, fz)
+#define FD_LAZY_FZP(MODE, NL, NCC, PP) hipLaunchKernelGGL((k_f_tridiag_fused<MODE, NL, NCC, PP>), dim3(fused_grid(k_f_tridiag_fused<MODE, NL, NCC, PP>, gw, fz.eg.C + fz.nblocks)), dim3(kBlock), 0, s, (const real_t *)lp->x, b->prm[0], bst, jstart, lines, fz)
 #define FD_LAZY_FZ(MODE, NL)                                                                                                              \
                 do { if (fz.eg.C <= 4) { if (fz.eg.tpb > 2) FD_LAZY_FZP(MODE, NL, 4, true); else FD_LAZY_FZP(MODE, NL, 4, false); }               \
                      else { if (fz.eg.tpb > 2) FD_LAZY_FZP(MODE, NL, kRegColors, true); else FD_LAZY_FZP(MODE, NL, kRegColors, false); } } while (0)
@@ -983,7 +1035,7 @@ static int lazy_tridiag_launch(BuiltinF *b, void *fx, const fd_lazy_points *lp, 
             }
 #define FD_LAZY_SW(MODE, NL)                                                                                       \
             hipLaunchKernelGGL((k_f_tridiag_store_wave<MODE, NL>), dim3(gw), dim3(kBlock), 0, s, (const real_t *)lp->x,  \
-                               (const real_t *)lp->eps, b->prm[0], bst, jstart)
+                               (const real_t *)lp->eps, b->prm[0], bst, jstart, lines)
             if (mode == 0) { if (nl) FD_LAZY_SW(0, true); else FD_LAZY_SW(0, false); }
             else { if (nl) FD_LAZY_SW(1, true); else FD_LAZY_SW(1, false); }
 #undef FD_LAZY_SW

@@ -294,7 +294,7 @@ __device__ __forceinline__ int eps_rescale_exp(double t, double relstep, double 
 // TEST SWITCHES.  A handful of FDJAC_* environment variables select between bit-identical kernel variants / plan builders so that the
 // tests can run both sides of every "same bits" claim (tests/test_gpu_parity.py, test_gpu_planbuild.py, ...):
 //   FDJAC_SMALL (fused single-workgroup launches of small problems), FDJAC_LAZY_DIFF / FDJAC_LAZY_STORE (hand-over forms of the lazy
-//   launchers), FDJAC_EPS_CYCLIC (the step-size reduction's computed colours), FDJAC_BAND_DESC (computed tile
+//   launchers), FDJAC_STORE_LINES (0: the tridiagonal storing launch keeps fd_band_emit_wave, no line-aligned spans), FDJAC_EPS_CYCLIC (the step-size reduction's computed colours), FDJAC_BAND_DESC (computed tile
 //   descriptors), FDJAC_PLAN_DEVICE (host vs device plan builder), FDJAC_WINDOW / FDJAC_WINDOW2D / FDJAC_SORTED / FDJAC_WIN_TILE /
 //   FDJAC_WIN_PERIODIC / FDJAC_TILE_ORDER (which decompression kernel a hand-over plan compiles to), FDJAC_COLOR_BATCH (rounds per
 //   read-back of the device colouring, 1..8) / FDJAC_COLOR_TAIL (0: no one-workgroup tail) / FDJAC_COLOR_STATS (1: one line of

@@ -349,6 +349,67 @@ __device__ inline void fd_band_emit_wave(const fd_band_store *d, T *win, long lo
     __builtin_amdgcn_wave_barrier();                                           /* the window may be reused */
 }
 /*
+ * The LINE-ALIGNED variant for the CSC layout of an exactly tridiagonal band (l = u = 1, W = 3).  The values of the columns
+ * jw .. jw + 127 start at local index 3 jw - 1 - entry_begin -- odd whenever 3 jw - entry_begin is even, so fd_band_emit_wave's
+ * window begins one pair before a pair boundary of the wave's own values: each of its store instructions straddles one more
+ * 128-byte line than it fills, and the two odd values at the ends leave as single-element stores.  Here the caller places jw so
+ * that  out + (3 jw - entry_begin)  -- the SECOND stored value of column jw, the diagonal -- lies on a 128-byte line (8-byte
+ * elements: 3 jw = entry_begin - out / 8 (mod 16)), and an interior wavefront owns the 384 values from there on: it leaves the
+ * first value of column jw (row jw - 1) to the wavefront before it and takes on the first value of column jw + 128 (row jw + 127)
+ * instead, which lane 63 -- whose x values reach that far -- computes and passes as `qnext` (read in lane 63 only).  Three whole
+ * store instructions per wavefront, every line written by exactly one of them, no single-element store.
+ * fd_band_wave_lines(d, jw) says whether the wavefront at jw is such an interior one (columns jw .. jw + 128 complete and inside
+ * the local range); the others -- the first (or first two) and the last of a launch -- write their columns through fd_band_emit_column, less the
+ * value the wavefront before them has written, plus the one the wavefront after them leaves out: every value exactly once.
+ * Every wavefront of the launch must use this function, with jw = jstart + 128 g.  q as for fd_band_emit_wave<T, 3>; all 64
+ * lanes call; window of FD_BAND_WAVE_LDS(3) elements.  Any 2 sizeof(T)-aligned placement is correct; the line-aligned one is fast.
+ */
+__device__ inline bool fd_band_wave_lines(const fd_band_store *d, long long jw)
+{
+    /* (jw > col_begin, not >=: a wavefront that starts exactly at the local range's first column has no wavefront before it to write
+       that column's first value -- it is the launch's first and writes column by column) */
+    return d->layout == FD_BAND_CSC && jw >= 1 && jw > d->col_begin && jw + 128 < d->col_end && jw + 128 < d->N && jw + 128 < d->M;
+}
+template <typename T, bool NT = true>
+__device__ inline void fd_band_emit_wave_lines(const fd_band_store *d, T *win, long long jw, const T *q, T qnext)
+{
+    typedef typename fd_band_pair_of<T>::type pair_t;
+    const int lane = (int)(threadIdx.x & 63);
+    const long long E = 3 * jw - d->entry_begin;                               /* local index of the entry (row jw, column jw) */
+    if (fd_band_wave_lines(d, jw)) {
+        /* slot s of the window <-> local index E + s: the lane's values sit in the slots 6 lane - 1 .. 6 lane + 4 */
+        if (lane) win[6 * lane - 1] = q[0];
+#pragma unroll
+        for (int m = 1; m < 6; ++m) win[6 * lane + m - 1] = q[m];
+        if (lane == 63) win[383] = qnext;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        T *base = (T *)d->out + E;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const int sl = 2 * (64 * a + lane);
+            const pair_t v = *(const pair_t *)(win + sl);
+            if (NT) __builtin_nontemporal_store(v, (pair_t *)(base + sl));
+            else *(pair_t *)(base + sl) = v;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();                                       /* the window may be reused */
+        return;
+    }
+    const long long j = jw + 2 * lane;
+    if (lane == 0 && fd_band_wave_lines(d, jw - 128)) {
+        /* column jw (inside the range, not the first of the matrix): its first value is the line-aligned neighbour's */
+        T *o = (T *)d->out + E;
+        o[0] = q[1];
+        if (jw + 1 < d->M) o[1] = q[2];
+    } else {
+        fd_band_emit_column<T>(d, j, q);
+    }
+    fd_band_emit_column<T>(d, j + 1, q + 3);
+    if (lane == 63 && fd_band_wave_lines(d, jw + 128)) ((T *)d->out)[E + 383] = qnext;   /* what that neighbour leaves out */
+}
+/*
  * The same for 4-byte elements with FOUR columns per lane: a wavefront's 256 columns, written as 16-byte stores (a Float32 pair
  * store moves 512 B per instruction, half of what the memory pipeline takes).  Lane t of a FULL wavefront holds the quotients of the
  * columns j = jw + 4t .. j + 3:  q[c W + k] = (row j + c - u + k, column j + c), c = 0 .. 3, k = 0 .. W-1.  jw is a multiple of 4

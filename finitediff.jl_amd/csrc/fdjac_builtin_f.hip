@@ -1373,8 +1373,9 @@ k_f_stencil5_store_wave4(const real_t *__restrict__ x, const real_t *__restrict_
 // ext/FiniteDiffBlockBandedMatricesExt.jl:16-42).  Thread k = (i, j) owns column k: it loads the 13 coordinates its five rows read, forms
 // the five quotients exactly as the CSC storing kernel does (stencil5_column_quotients) and writes the NINE slots of its column -- block
 // j-1: (0, q_S, 0), block j: (q_W, q_C, q_E), block j+1: (0, q_N, 0); slots of rows outside their block and whole columns without a colour
-// are 0, as k_decompress_bbb writes them.  A slot whose row does not depend on the column is exactly 0 in the hand-over path too (the
-// plan verified that the colouring is valid for the nine-point BBB pattern: no perturbed column reaches such a row).
+// are 0, as k_decompress_bbb writes them.  A slot whose row does not depend on the column holds the row's difference with itself over the
+// step, as in the hand-over path (the plan verified that the colouring is valid for the nine-point BBB pattern: no perturbed column
+// reaches such a row): +-0.0 for a finite row, NaN otherwise.
 template <typename CT, int MODE, int SK>
 __global__ void __launch_bounds__(kBlock) k_f_stencil5_store_bbb(const real_t *__restrict__ x, const real_t *__restrict__ eps, fd_bbb_store st, int nx, int ny)
 {
@@ -1398,9 +1399,26 @@ __global__ void __launch_bounds__(kBlock) k_f_stencil5_store_bbb(const real_t *_
     real_t q[5] = {0, 0, 0, 0, 0};
     const real_t e = none ? (real_t)1 : eps[c];
     if (!none) stencil5_column_quotients<MODE, SK, false, true, 5>(W, 0, i, j, nx, ny, e, q);
-    // an in-block row that does not depend on the column: the hand-over path divides an exact +0.0 difference by the step -- the sign
-    // of that zero follows the step's (dir = -1)
-    const real_t zq = (real_t)0 / (MODE == 1 ? 2 * e : e);
+    // an in-block row that does not depend on the column (the four corner rows (i +- 1, j +- 1)): the hand-over path divides the difference
+    // of the row's value with ITSELF by the step -- an exact +0.0 while that value is finite (the sign of the quotient follows the step's,
+    // dir = -1), NaN where the row reads a NaN / Inf coordinate or overflows.  So the row is evaluated and fr - fr divided: a constant
+    // zero here stored 0.0 where the reference and every other route store NaN (tests/test_gpu_exact_structured.py, nan_inf).
+    // zc[a][b]: row (i + 2 b - 1, j + 2 a - 1); a row outside the grid gives a value that is never stored
+    real_t zc[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const int dj = 2 * a - 1, di = 2 * b - 1;
+            auto at = [&](int ddi, int ddj) -> real_t {                      // coordinate (i + ddi, j + ddj), 0 outside the grid
+                const int ii = i + ddi, jj = j + ddj;
+                const bool in = ii >= 0 && ii < nx && jj >= 0 && jj < ny;
+                const real_t v = x[in ? (int64_t)jj * nx + ii : k];          // (unconditional load from a clamped index)
+                return in ? v : (real_t)0;
+            };
+            const real_t fr = stencil5_row<real_t, SK>(at(di, dj), at(di - 1, dj), at(di + 1, dj), at(di, dj - 1), at(di, dj + 1));
+            zc[a][b] = (fr - fr) / (MODE == 1 ? 2 * e : e);
+        }
     // rows k - nx, k - 1, k, k + 1, k + nx; those that do not exist hold garbage in q: they are never stored
     real_t *out = (real_t *)st.out;
     const long long sJ = st.stride[j];
@@ -1412,7 +1430,7 @@ __global__ void __launch_bounds__(kBlock) k_f_stencil5_store_bbb(const real_t *_
         const bool kin = K >= 0 && K < ny;
         real_t *o = out + st0 + (long long)i * sJ;                         // slots t = 0, 1, 2 <-> rows i - 1, i, i + 1 of block K (mu = 1)
         const real_t mid = d == 0 ? q[0] : d == 1 ? q[2] : q[4];
-        const real_t lo = d == 1 ? q[1] : zq, hi = d == 1 ? q[3] : zq;
+        const real_t lo = d == 1 ? q[1] : zc[d >> 1][0], hi = d == 1 ? q[3] : zc[d >> 1][1];
         o[0] = (kin && !none && i - 1 >= 0) ? lo : (real_t)0;
         o[1] = (kin && !none) ? mid : (real_t)0;
         o[2] = (kin && !none && i + 1 < nx) ? hi : (real_t)0;

@@ -357,9 +357,12 @@ def fixture(family, *prm):
     raise ValueError(family)
 
 
-def colour_values(f, x, colors0, C, eps, fdtype, f_in=None):
+def colour_values(f, x, colors0, C, eps, fdtype, f_in=None, zero="model"):
     """D[c][r]: the value the plain evaluation stores for row r in a column of colour c; (C, M) for a residual of M rows.  f_in: the
-    caller's f(x) of a forward difference -- subtracted as it is given."""
+    caller's f(x) of a forward difference -- subtracted as it is given.  zero: the form of an UNPERTURBED coordinate -- "model"
+    x_i + copysign(0, eps_c) (Julia's eps * false), "library" x_i + (+0.0) whatever the sign of eps_c (k_perturb, fd_column_point: they
+    differ at x_i = -0.0 for dir = -1 only, tests/test_gpu_exact_store.py), "none" x_i itself (a MUTATION: what the row-wise kernels
+    once did; the CPU suites show that their cases tell it apart)."""
     x = np.asarray(x)
     T = x.dtype.type
     with np.errstate(all="ignore"):
@@ -369,9 +372,9 @@ def colour_values(f, x, colors0, C, eps, fdtype, f_in=None):
         D = None
         for c in range(C):
             e = T(eps[c])
-            z = np.copysign(T(0), e)
+            z = np.copysign(T(0), e) if zero == "model" else T(0)
             m = colors0 == c
-            xp = np.where(m, x + e, x + z)
+            xp = np.where(m, x + e, x if zero == "none" else x + z)
             if fdtype == "forward":
                 row = (f(xp) - base) / e
             else:
@@ -430,6 +433,193 @@ def to_tridiagonal(D, colors0, N):
         return out
     j = np.arange(N)
     return take(j[:-1] + 1, j[:-1]), take(j, j), take(j[:-1], j[:-1] + 1)
+
+
+def to_banded_general(D, colors0, M, N, l, u, outside=0.0, row_shift=0):
+    """to_banded with the two knobs the mutation checks turn: `outside` = what a slot of a row outside the matrix holds (the model: 0;
+    NaN = "left unwritten" over a NaN-filled destination), row_shift = every slot takes the row `row_shift` below its own."""
+    out = np.full((l + u + 1, N), outside, D.dtype)
+    colors0 = np.asarray(colors0)
+    j = np.arange(N)
+    for b in range(l + u + 1):
+        i = j + b - u
+        inside = (i >= 0) & (i < M)
+        out[b, inside & (colors0 < 0)] = 0
+        ok = inside & (colors0 >= 0)
+        out[b, j[ok]] = D[colors0[j[ok]], np.clip(i[ok] + row_shift, 0, M - 1)]
+    return out.T.reshape(-1)
+
+
+def to_blockbanded(D, colors0, layout):
+    """BlockBandedMatrix data (patterns.BlockBandedLayout; ext/FiniteDiffBlockBandedMatricesExt.jl:44-68): column j of block-column J
+    holds the rows of its in-band blocks K = max(J - bu, 0) .. min(J + bl, nb - 1), stacked, at block_starts(K0, J) - 1 +
+    (j - off[J]) stride[J]; every one of them holds D[colour of j][row], 0 for a column without a colour."""
+    colors0 = np.asarray(colors0)
+    bs, nb, bl, bu = layout.blk_sizes, layout.nblk, layout.bl, layout.bu
+    off = np.concatenate([[0], np.cumsum(bs)])
+    out = np.zeros(layout.data_len, D.dtype)
+    for J in range(nb):
+        K0, K1 = max(0, J - bu), min(nb - 1, J + bl)
+        r0, r1 = int(off[K0]), int(off[K1 + 1])
+        st = int(layout.block_strides[J])
+        s = int(layout.block_starts[(bu + K0 - J) + (bl + bu + 1) * J]) - 1
+        for jj in range(int(bs[J])):
+            c = int(colors0[off[J] + jj])
+            if c >= 0:
+                out[s + jj * st:s + jj * st + (r1 - r0)] = D[c, r0:r1]
+    return out
+
+
+def to_bandedblockbanded(D, colors0, layout, outside=0.0, row_shift=0):
+    """BandedBlockBandedMatrix data (patterns.BandedBlockBandedLayout; ext/FiniteDiffBlockBandedMatricesExt.jl:16-42).  Every element
+    of data is defined: slot t of column j (local jj, block-column J) of the slab of block (K, J) is row k = jj + t - mu of block K --
+    D[colour of j][off[K] + k] where 0 <= k < n_K, an exact +0.0 where the row falls outside its block, and +0.0 in every slot of a
+    column without a colour; what no slab reaches holds +0.0 (the reference zero-fills J, src/jacobians.jl:530-532).  outside /
+    row_shift: the mutation knobs of to_banded_general (a slot outside its block "left unwritten"; one row off in a sub-band)."""
+    colors0 = np.asarray(colors0)
+    bs, nb, bl, bu, lam, mu = layout.blk_sizes, layout.nblk, layout.bl, layout.bu, layout.lam, layout.mu
+    off = np.concatenate([[0], np.cumsum(bs)])
+    w = bl + bu + 1
+    M = int(off[-1])
+    out = np.zeros(layout.data_len, D.dtype)
+    for J in range(nb):
+        st = int(layout.block_strides[J])
+        jj = np.arange(int(bs[J]))
+        c = colors0[off[J] + jj]
+        for K in range(max(0, J - bu), min(nb - 1, J + bl) + 1):
+            s = int(layout.block_starts[(bu + K - J) + w * J]) - 1
+            for t in range(lam + mu + 1):
+                k = jj + t - mu
+                dest = s + jj * st + t
+                inb = (k >= 0) & (k < bs[K])
+                out[dest[~inb]] = outside
+                out[dest[c < 0]] = 0
+                ok = inb & (c >= 0)
+                out[dest[ok]] = D[c[ok], np.clip(off[K] + k[ok] + row_shift, 0, M - 1)]
+    return out
+
+
+# ---- the rational fixtures of the structured storages (tests/jit_fixtures.py holds the functors' source) -------------------------------------
+def _band_terms(N, l, u):
+    i = np.arange(N)
+    for d in range(-l, u + 1):
+        c = i + d
+        inn = (c >= 0) & (c < N)
+        yield np.clip(c, 0, N - 1), inn, ((i + 3 * c) & 7)
+
+
+def band_f(N, l, u, sign=False):
+    """BandF (tests/jit_fixtures.py): row i = the terms of the columns c = i - l .. i + u inside the matrix, left to right, the first
+    one ASSIGNED: w (v + (v / 4) v), w = 1 + ((i + 3 c) mod 8) / 8; sign=True (BandSign): ... + copysign(1, v), which sees the sign of a
+    zero coordinate."""
+    def f(x):
+        x = np.asarray(x)
+        T = x.dtype.type
+        with np.errstate(all="ignore"):
+            s = np.zeros(N, x.dtype)
+            started = np.zeros(N, bool)
+            for cc, inn, k in _band_terms(N, l, u):
+                v = x[cc]
+                t = (T(1) + T(0.125) * k.astype(x.dtype)) * (v + (T(0.25) * v) * v)
+                if sign:
+                    t = t + np.copysign(T(1), v)
+                s = np.where(inn, np.where(started, s + t, t), s)
+                started |= inn
+        return s
+    return f
+
+
+def band_fc(N, l, u, smul=c_smul):
+    """BandF on (re, im) pairs: w * (v + (q * v) * v) with q * v and w * (...) scalar * complex, (q v) * v complex * complex."""
+    def f(x):
+        T = x[0].dtype.type
+        with np.errstate(all="ignore"):
+            s = (np.zeros(N, x[0].dtype), np.zeros(N, x[0].dtype))
+            started = np.zeros(N, bool)
+            for cc, inn, k in _band_terms(N, l, u):
+                v = (x[0][cc], x[1][cc])
+                t = smul(T(1) + T(0.125) * k.astype(x[0].dtype), c_add(v, c_mul(smul(T(0.25), v), v)))
+                a = c_add(s, t)
+                s = tuple(np.where(inn, np.where(started, a[p], t[p]), s[p]) for p in (0, 1))
+                started |= inn
+        return s
+    return f
+
+
+def grid_f(nx, ny, reach):
+    """GridNL (tests/jit_fixtures.py) on an nx x ny grid: s = c c; for d = 1 .. reach: s += (0.5 / d) west_d, s += ((0.25 d) east_d) c;
+    s += south; s += 2 north -- a neighbour outside the grid adds the constant +0 (not a product with a zero)."""
+    def f(x):
+        x = np.asarray(x)
+        T = x.dtype.type
+        g = x.reshape(ny, nx)
+        zero = np.zeros_like(g)
+        with np.errstate(all="ignore"):
+            s = g * g
+            for d in range(1, reach + 1):
+                w, e = zero.copy(), zero.copy()
+                hw, he = np.zeros(g.shape, bool), np.zeros(g.shape, bool)
+                if d < nx:
+                    w[:, d:], hw[:, d:] = g[:, :-d], True
+                    e[:, :-d], he[:, :-d] = g[:, d:], True
+                s = s + np.where(hw, T(0.5 / d) * w, zero)
+                s = s + np.where(he, (T(0.25 * d) * e) * g, zero)
+            sv, nv = zero.copy(), zero.copy()
+            hs, hn = np.zeros(g.shape, bool), np.zeros(g.shape, bool)
+            sv[1:], hs[1:] = g[:-1], True
+            nv[:-1], hn[:-1] = g[1:], True
+            s = s + np.where(hs, sv, zero)
+            s = s + np.where(hn, T(2) * nv, zero)
+        return s.reshape(-1)
+    return f
+
+
+def _block_sums(parts, off, sign):
+    """Per block and part: the block's coordinates added left to right, the first one assigned (np.cumsum: strictly sequential)."""
+    out = []
+    for p in parts:
+        q = p + np.copysign(p.dtype.type(1), p) if sign else p
+        out.append(np.array([np.cumsum(q[off[b]:off[b + 1]])[-1] for b in range(off.size - 1)], dtype=p.dtype))
+    return out
+
+
+def blockrat_f(blk_sizes, bl=1, bu=1, sign=False):
+    """BlockRat (tests/jit_fixtures.py): row k of block b = x_k tot_b + (x_k x_k) x_k, tot_b = the sums S_J of the blocks J = b - bl ..
+    b + bu inside the matrix added left to right (the first one assigned), S_J = block J's coordinates added left to right; sign=True
+    (BlockSign): S_J adds v + copysign(1, v).  Any (non-empty) block sizes."""
+    bs = np.asarray(blk_sizes, np.int64)
+    off = np.concatenate([[0], np.cumsum(bs)])
+    blk = np.repeat(np.arange(bs.size), bs)
+
+    def f(x):
+        x = np.asarray(x)
+        with np.errstate(all="ignore"):
+            S, = _block_sums([x], off, sign)
+            tot = np.zeros(bs.size, x.dtype)
+            for b in range(bs.size):
+                Js = range(max(0, b - bl), min(bs.size - 1, b + bu) + 1)
+                tot[b] = np.cumsum(S[list(Js)])[-1]
+            return x * tot[blk] + (x * x) * x
+    return f
+
+
+def blockrat_fc(blk_sizes, bl=1, bu=1):
+    """BlockRat on (re, im) pairs: the sums part by part, x_k * tot and (x_k * x_k) * x_k complex * complex."""
+    bs = np.asarray(blk_sizes, np.int64)
+    off = np.concatenate([[0], np.cumsum(bs)])
+    blk = np.repeat(np.arange(bs.size), bs)
+
+    def f(x):
+        with np.errstate(all="ignore"):
+            S = _block_sums(list(x), off, False)
+            tot = [np.zeros(bs.size, x[0].dtype), np.zeros(bs.size, x[0].dtype)]
+            for b in range(bs.size):
+                Js = list(range(max(0, b - bl), min(bs.size - 1, b + bu) + 1))
+                for p in (0, 1):
+                    tot[p][b] = np.cumsum(S[p][Js])[-1]
+            t = (tot[0][blk], tot[1][blk])
+            return c_add(c_mul(x, t), c_mul(c_mul(x, x), x))
+    return f
 
 
 def same_bits(got, want):

@@ -7,6 +7,7 @@ import pytest
 
 import finitediff_jl_amd as fd
 from finitediff_jl_amd import patterns as P
+from jit_fixtures import BANDF, GRID_NL      # (shared with tests/test_gpu_exact_structured.py, which holds them to the exact host model)
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -199,27 +200,6 @@ def test_jit_functor_stores_an_exact_band_itself(fdtype, storage, N):
             a[N - 1, 2] = b[N - 1, 2] = 0.0
         assert not torch.isnan(b).any() or storage == "banded"
         assert torch.equal(a.view(torch.int64), b.view(torch.int64)), storage
-
-
-BANDF = """
-// a residual whose Jacobian is the exact band (l, u): row i = sum over c = i - l .. i + u of w(i, c) (x_c + x_c^2 / 4), left to right
-struct BandF {
-    long long n;
-    int l, u;
-    template <class P> __device__ real_t operator()(long long i, const P &X) const
-    {
-        real_t s = 0;
-        bool first = true;
-        for (long long c = i - l; c <= i + u; ++c) {
-            const bool in = c >= 0 && c < n;
-            const real_t v = X(in ? c : i);
-            const real_t t = ((real_t)1 + (real_t)0.125 * (real_t)(int)((i + 3 * c) & 7)) * (v + ((real_t)0.25 * v) * v);
-            if (in) { s = first ? t : s + t; first = false; }
-        }
-        return s;
-    }
-};
-"""
 
 
 @pytest.mark.parametrize("fdtype", ["forward", "central"])
@@ -654,32 +634,6 @@ def test_jit_functor_stores_blockbanded_data_itself(oracle, fdtype, case):
 
 
 # ---- a compiled row functor storing BandedBlockBandedMatrix data itself (fd_bbb_store_cols) ----------------------------------------------
-GRID_NL = """
-// an nx x ny grid, row k = (i, j): neighbours within `reach` along the grid row and the points straight above / below, nonlinear in x_k
-struct GridNL {
-    long long nx, ny, reach;
-    template <class P> __device__ typename P::value_type operator()(long long k, const P &X) const
-    {
-        typedef typename P::value_type V;
-        const long long j = k / nx, i = k - j * nx;
-        const V c = X(k);
-        V s = c * c;
-        for (long long d = 1; d <= reach; ++d) {
-            const bool hw = i - d >= 0, he = i + d < nx;
-            const V w = X(hw ? k - d : k), e = X(he ? k + d : k);
-            s = s + (hw ? (real_t)(0.5 / d) * w : (real_t)0);
-            s = s + (he ? (real_t)(0.25 * d) * e * c : (real_t)0);
-        }
-        const bool hs = j > 0, hn = j + 1 < ny;
-        const V sv = X(hs ? k - nx : k), nv = X(hn ? k + nx : k);
-        s = s + (hs ? sv : (real_t)0);
-        s = s + (hn ? (real_t)2 * nv : (real_t)0);
-        return s;
-    }
-};
-"""
-
-
 @pytest.mark.parametrize("fdtype", ["forward", "central"])
 @pytest.mark.parametrize("case", [(40, 30, 1), (23, 17, 3), (64, 5, 2)])
 def test_jit_functor_stores_bandedblockbanded_data_itself(oracle, fdtype, case):

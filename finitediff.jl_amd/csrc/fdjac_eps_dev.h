@@ -1,5 +1,5 @@
 // Device code of the step-size reduction shared by its own launches (fdjac_kernels.hip) and by the FUSED step of the built-in storing
-// launchers (fdjac_builtin_f.hip): level 0 of the defined two-level sum as a function, and the pieces of the one-launch Jacobian
+// launchers (fdjac_f_tridiag.hip): level 0 of the defined two-level sum as a function, and the pieces of the one-launch Jacobian
 // (round 6) -- reduction workgroups, ONE finisher workgroup, storing wavefronts that wait for the step sizes.
 //
 // The fused step hands values from workgroup to workgroup WITHOUT tickets or fences: every handed-over value is its own flag.  A slot

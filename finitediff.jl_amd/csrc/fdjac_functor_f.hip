@@ -11,7 +11,7 @@
 // Included by fdjac_builtin_f.hip (namespace fdjac, after BuiltinF).
 
 constexpr real_t kSix = 6, kQuarter = 0.25, kEighth = 0.125;
-template <bool FAST> __device__ __forceinline__ real_t div_shared(real_t a, real_t b, real_t y);   // (fdjac_builtin_f.hip, below the include)
+template <bool FAST> __device__ __forceinline__ real_t div_shared(real_t a, real_t b, real_t y);   // (fdjac_f_stencil5.hip, included later)
 template <bool FAST> __device__ __forceinline__ real_t div_shared(real_t a, real_t b, real_t y, bool bok);
 __device__ __forceinline__ bool div_shared_ok(real_t b);
 
@@ -811,18 +811,23 @@ __global__ void __launch_bounds__(kBlock) k_csc_store_cols_cplx(F f, const real_
 }
 
 // ---- launchers --------------------------------------------------------------------------------------------------------------
+static Lap7F lap7_functor(const BuiltinF *b)
+{
+    return {(int)b->prm[0], (int)b->prm[1], (int)b->prm[2], fd_magic31((uint32_t)(b->prm[0] * b->prm[1])), fd_magic31((uint32_t)b->prm[0])};
+}
+
 template <typename T>
 static int functor_family_launch(BuiltinF *b, void *fx, const void *x, int64_t nbatch, int64_t xs, int64_t fs, int64_t r0, int64_t r1, hipStream_t s)
 {
     const dim3 g((unsigned)((r1 - r0 + kBlock - 1) / kBlock), (unsigned)nbatch, 1);
     if (b->family == FD_F_LAP7) {
-        const Lap7F f = {(int)b->prm[0], (int)b->prm[1], (int)b->prm[2], fd_magic31((uint32_t)(b->prm[0] * b->prm[1])), fd_magic31((uint32_t)b->prm[0])};
+        const Lap7F f = lap7_functor(b);
         hipLaunchKernelGGL((k_f_rows<T, Lap7F>), g, dim3(kBlock), 0, s, (T *)fx, (const T *)x, f, xs, fs, r0, r1);
     } else {
         const SparseF f = {b->d_srow, b->d_scol};
         hipLaunchKernelGGL((k_f_rows<T, SparseF>), g, dim3(kBlock), 0, s, (T *)fx, (const T *)x, f, xs, fs, r0, r1);
     }
-    return hipGetLastError() == hipSuccess ? 0 : 4;
+    return launch_rc();
 }
 
 // the lazy launcher of these families serves exactly one request: store column by column (forward / central); everything else is
@@ -839,31 +844,33 @@ static int functor_family_lazy(BuiltinF *b, const fd_lazy_points *lp, hipStream_
     const real_t *x = (const real_t *)lp->x, *eps = (const real_t *)lp->eps;
     if (lp->is_complex) {       // the complex step: imag(row at x + i eps e_j) / eps, stored by this launch
         if (b->family == FD_F_LAP7) {
-            const Lap7F f = {(int)b->prm[0], (int)b->prm[1], (int)b->prm[2], fd_magic31((uint32_t)(b->prm[0] * b->prm[1])), fd_magic31((uint32_t)b->prm[0])};
+            const Lap7F f = lap7_functor(b);
             hipLaunchKernelGGL((k_csc_store_cols_cplx<CT, Lap7F>), dim3(g), dim3(kBlock), 0, s, f, x, eps, c_lo, c_hi, st);
         } else {
             const SparseF f = {b->d_srow, b->d_scol};
             hipLaunchKernelGGL((k_csc_store_cols_cplx<CT, SparseF>), dim3(g), dim3(kBlock), 0, s, f, x, eps, c_lo, c_hi, st);
         }
         store_launch_note() = FD_STORE_LAUNCH_FAMILY;
-        return hipGetLastError() == hipSuccess ? 0 : 4;
+        return launch_rc();
     }
-#define FD_COLS(FT, fobj)                                                                                                                  \
-    do {                                                                                                                                   \
-        if (lp->pts == 2) hipLaunchKernelGGL((fd_csc_store_cols<real_t, CT, 1, FT>), dim3(g), dim3(kBlock), 0, s, fobj, x, eps, c_lo, c_hi, st); \
-        else hipLaunchKernelGGL((fd_csc_store_cols<real_t, CT, 0, FT>), dim3(g), dim3(kBlock), 0, s, fobj, x, eps, c_lo, c_hi, st);              \
-        store_launch_note() = FD_STORE_LAUNCH_COLS;                                                                                        \
-    } while (0)
+    // the storing kernels' MODE: 0 forward, 1 central
+    const auto pick_mode = [&](auto &&launch) { fd_pick<0, 1>(lp->pts == 2 ? 1 : 0, launch); };
+    const auto store_cols = [&](const auto &f) {      // the plain column kernel every functor gets (include/fdjac_device.h)
+        using FT = std::decay_t<decltype(f)>;
+        pick_mode([&](auto M) { hipLaunchKernelGGL((fd_csc_store_cols<real_t, CT, M(), FT>), dim3(g), dim3(kBlock), 0, s, f, x, eps, c_lo,
+                                                   c_hi, st); });
+        store_launch_note() = FD_STORE_LAUNCH_COLS;
+    };
     if (b->family == FD_F_LAP7) {
-        const Lap7F f = {(int)b->prm[0], (int)b->prm[1], (int)b->prm[2], fd_magic31((uint32_t)(b->prm[0] * b->prm[1])), fd_magic31((uint32_t)b->prm[0])};
+        const Lap7F f = lap7_functor(b);
         if (st.valid_coloring) {      // the neighbourhood in registers (one perturbed coordinate per column)
-            if (lp->pts == 2) hipLaunchKernelGGL((k_f_lap7_store_cols<CT, 1>), dim3(g), dim3(kBlock), 0, s, f, x, eps, c_lo, c_hi, st);
-            else hipLaunchKernelGGL((k_f_lap7_store_cols<CT, 0>), dim3(g), dim3(kBlock), 0, s, f, x, eps, c_lo, c_hi, st);
+            pick_mode([&](auto M) { hipLaunchKernelGGL((k_f_lap7_store_cols<CT, M()>), dim3(g), dim3(kBlock), 0, s, f, x, eps, c_lo, c_hi,
+                                                       st); });
             // (every launch visits all local columns: one that counted no mismatch has verified the pattern)
             if (st.note) hipLaunchKernelGGL(k_lap7_note, dim3(1), dim3(1), 0, s, st.note, lap7_note_key(f, st));
             store_launch_note() = FD_STORE_LAUNCH_FAMILY;
         } else {
-            FD_COLS(Lap7F, f);
+            store_cols(f);
         }
     } else {
         const SparseF f = {b->d_srow, b->d_scol};
@@ -911,18 +918,18 @@ static int functor_family_lazy(BuiltinF *b, const fd_lazy_points *lp, hipStream_
             const size_t lds_e = fd_csc_ents_lds_bytes<real_t>(reach, lp->ncolors, st.ent_tile_max);
             const char *sw = test_switch("FDJAC_ROWS_ENTS");
             if (st.ent_col && st.ent_slot && st.ent_info && lds_e <= 64 * 1024 && (sw && *sw == '1')) {      // a thread per entry (fd_csc_store_ents)
-                if (lp->pts == 2) hipLaunchKernelGGL((fd_csc_store_ents<real_t, CT, 1, SparseF>), dim3(gr), dim3(kBlock), lds_e, s, f, x, eps, c_lo, c_hi, st, (int)reach);
-                else hipLaunchKernelGGL((fd_csc_store_ents<real_t, CT, 0, SparseF>), dim3(gr), dim3(kBlock), lds_e, s, f, x, eps, c_lo, c_hi, st, (int)reach);
+                pick_mode([&](auto M) { hipLaunchKernelGGL((fd_csc_store_ents<real_t, CT, M(), SparseF>), dim3(gr), dim3(kBlock), lds_e, s,
+                                                           f, x, eps, c_lo, c_hi, st, (int)reach); });
                 b->row_stores.fetch_add(1);
                 store_launch_note() = FD_STORE_LAUNCH_ENTS;
-                return hipGetLastError() == hipSuccess ? 0 : 4;
+                return launch_rc();
             }
             const size_t lds_g = fd_csc_rows_lds_bytes<real_t>(reach, lp->ncolors, cap_r);
-            if (lp->pts == 2) hipLaunchKernelGGL((fd_csc_store_rows<real_t, CT, 1, SparseF>), dim3(gr), dim3(kBlock), lds_g, s, f, x, eps, c_lo, c_hi, st, (int)reach, cap_r);
-            else hipLaunchKernelGGL((fd_csc_store_rows<real_t, CT, 0, SparseF>), dim3(gr), dim3(kBlock), lds_g, s, f, x, eps, c_lo, c_hi, st, (int)reach, cap_r);
+            pick_mode([&](auto M) { hipLaunchKernelGGL((fd_csc_store_rows<real_t, CT, M(), SparseF>), dim3(gr), dim3(kBlock), lds_g, s, f,
+                                                       x, eps, c_lo, c_hi, st, (int)reach, cap_r); });
             b->row_stores.fetch_add(1);
             store_launch_note() = FD_STORE_LAUNCH_ROWS;
-            return hipGetLastError() == hipSuccess ? 0 : 4;
+            return launch_rc();
         }
         if (verdict != 1) {                    // a column kernel
             bool done = false;
@@ -934,25 +941,26 @@ static int functor_family_lazy(BuiltinF *b, const fd_lazy_points *lp, hipStream_
                 const size_t lds_s = sparse_sorted_lds_bytes(reach, cap);
                 if (lds_s <= 64 * 1024 && (lp->pts == 2 || st.fx_base != nullptr)) {      // the entry-balanced form (see k_f_sparse_store_sorted)
                     const unsigned long long gate = (rows && verdict == 0) ? key : 0ull;
-                    if (lp->pts == 2) hipLaunchKernelGGL((k_f_sparse_store_sorted<CT, 1>), dim3(g), dim3(kBlock), lds_s, s, f, x, eps, c_lo, c_hi, st, (int)reach, cap, gate);
-                    else hipLaunchKernelGGL((k_f_sparse_store_sorted<CT, 0>), dim3(g), dim3(kBlock), lds_s, s, f, x, eps, c_lo, c_hi, st, (int)reach, cap, gate);
+                    pick_mode([&](auto M) { hipLaunchKernelGGL((k_f_sparse_store_sorted<CT, M()>), dim3(g), dim3(kBlock), lds_s, s, f, x,
+                                                               eps, c_lo, c_hi, st, (int)reach, cap, gate); });
                     store_launch_note() = FD_STORE_LAUNCH_FAMILY;
                     done = true;
                 } else if (lds <= 64 * 1024) {
-                    if (lp->pts == 2) hipLaunchKernelGGL((fd_csc_store_cols_win<real_t, CT, 1, SparseF>), dim3(g), dim3(kBlock), lds, s, f, x, eps, c_lo, c_hi, st, (int)reach, (int)sb, cap);
-                    else hipLaunchKernelGGL((fd_csc_store_cols_win<real_t, CT, 0, SparseF>), dim3(g), dim3(kBlock), lds, s, f, x, eps, c_lo, c_hi, st, (int)reach, (int)sb, cap);
+                    pick_mode([&](auto M) { hipLaunchKernelGGL((fd_csc_store_cols_win<real_t, CT, M(), SparseF>), dim3(g), dim3(kBlock),
+                                                               lds, s, f, x, eps, c_lo, c_hi, st, (int)reach, (int)sb, cap); });
                     store_launch_note() = FD_STORE_LAUNCH_COLS_WIN;
                     done = true;
                 }
             }
-            if (!done) FD_COLS(SparseF, f);
+            if (!done) store_cols(f);
         }
         if (verdict == 1) { b->row_stores.fetch_add(1); store_launch_note() = FD_STORE_LAUNCH_FAMILY; }      // (k_f_sparse_store_rows below stores)
         if (rows && verdict != 2) {
             const long long row_lo = std::max<long long>(0, st.col_begin - reach), row_hi = std::min<long long>(st.M, st.col_end + reach);
             const unsigned gr = fd_xcd_grid((row_hi - row_lo + kBlock - 1) / kBlock);
-            if (lp->pts == 2) hipLaunchKernelGGL((k_f_sparse_store_rows<CT, 1>), dim3(gr), dim3(kBlock), lds_r, s, f, b->d_sdest, e_base, x, eps, c_lo, c_hi, st, (int)reach, cap_r, row_lo, row_hi, key, expect, verdict == 1 ? 1 : 0);
-            else hipLaunchKernelGGL((k_f_sparse_store_rows<CT, 0>), dim3(gr), dim3(kBlock), lds_r, s, f, b->d_sdest, e_base, x, eps, c_lo, c_hi, st, (int)reach, cap_r, row_lo, row_hi, key, expect, verdict == 1 ? 1 : 0);
+            pick_mode([&](auto M) { hipLaunchKernelGGL((k_f_sparse_store_rows<CT, M()>), dim3(gr), dim3(kBlock), lds_r, s, f, b->d_sdest,
+                                                       e_base, x, eps, c_lo, c_hi, st, (int)reach, cap_r, row_lo, row_hi, key, expect,
+                                                       verdict == 1 ? 1 : 0); });
             if (verdict == 0) {
                 std::lock_guard<std::mutex> lock(b->rows_mutex);
                 if (!memo->pending) {                        // the verdict on its way to the host: read at a later call, never waited for
@@ -968,6 +976,5 @@ static int functor_family_lazy(BuiltinF *b, const fd_lazy_points *lp, hipStream_
             }
         }
     }
-#undef FD_COLS
-    return hipGetLastError() == hipSuccess ? 0 : 4;
+    return launch_rc();
 }

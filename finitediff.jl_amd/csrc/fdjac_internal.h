@@ -116,6 +116,7 @@
 
 #include "fdjac.h"
 #include "fdjac_device.h"
+#include "fdjac_dispatch.h"
 
 // communicator internals shared by both element-type builds (fdjac_comm.hip)
 extern "C" int fdjac_comm_allgather_f64(fd_comm *c, double *buf, int64_t slot_elems);
@@ -198,6 +199,9 @@ inline void set_error(const char *fmt, ...)
             return (code);                   \
         }                                    \
     } while (0)
+
+// what an f! launcher (fd_f_launch and its kin) returns after enqueueing: 0, or 4 when a launch of this thread failed
+inline int launch_rc() { return hipGetLastError() == hipSuccess ? 0 : 4; }
 
 enum PlanKind { K_CSC = 0, K_CSC_DENSE, K_COO_DENSE, K_TRIDIAG, K_BANDED, K_COLRANGE, K_DENSE, K_BBB };
 

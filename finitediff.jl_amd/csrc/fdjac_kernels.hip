@@ -1323,6 +1323,15 @@ static inline int grid_for(int64_t work_items, int per_block, int num_cus)
     return balanced_grid(tiles, cap);
 }
 
+// the register-path reductions' <NC, CYCLIC, NT>: colour sums kept per thread (4, 6 or 8 -- c3's five colours: 30 -> 26 us), colours
+// computed from the column (a cyclic colouring), non-temporal loads of x
+template <typename F> static inline void pick_eps_variant(const fd_plan *p, int C, F &&launch)
+{
+    fd_pick<4, 6, kRegColors>(C <= 4 ? 4 : C <= 6 ? 6 : kRegColors, [&](auto NC) {
+        fd_pick<false, true>(p->cyc_C > 0, [&](auto CY) { fd_pick<false, true>(p->eps_nt, [&](auto NT) { launch(NC, CY, NT); }); });
+    });
+}
+
 // step-size reduction, register path (C <= kRegColors): the groups [g0, g0 + ng) of the two-level reduction.  final = the launch
 // covers all kEpsGroups groups and writes eps itself; otherwise it stops at the group sums (d_gsum) -- a shard.
 template <typename CT>
@@ -1337,18 +1346,11 @@ static int launch_eps_groups_t(fd_plan *p, const real_t *x, int g0, int ng, bool
     eg.final_groups = final ? ng : 0;
     eg.C = C; eg.is_forward = p->fdtype == FD_FORWARD ? 1 : 0;
     eg.relstep = relstep; eg.absstep = absstep; eg.dir = dir;
-#define FD_EPS_REG(NCC, CY, NTT)                                                                                \
-    hipLaunchKernelGGL((k_eps_partial_reg<CT, NCC, CY, NTT>), dim3((unsigned)(ng * eg.bpg)), dim3(kBlock), 0, s, x,  \
-                       (const CT *)p->d_color, p->N, p->d_partial, p->d_gsum, p->d_tick, ldp, p->cyc_C, p->cyc_shift, g0 * eg.bpg, eg, \
-                       p->cx ? 1 : 0, p->d_eps, p->d_eps2)
-#define FD_EPS_REG_V(NCC)                                                                                       \
-    do {                                                                                                        \
-        if (p->cyc_C > 0) { if (p->eps_nt) FD_EPS_REG(NCC, true, true); else FD_EPS_REG(NCC, true, false); }     \
-        else { if (p->eps_nt) FD_EPS_REG(NCC, false, true); else FD_EPS_REG(NCC, false, false); }               \
-    } while (0)
-    if (C <= 4) FD_EPS_REG_V(4); else if (C <= 6) FD_EPS_REG_V(6); else FD_EPS_REG_V(kRegColors);      // (colour sums kept per thread: 4, 6 or 8 -- c3's five colours: 30 -> 26 us)
-#undef FD_EPS_REG_V
-#undef FD_EPS_REG
+    pick_eps_variant(p, C, [&](auto NC, auto CY, auto NT) {
+        hipLaunchKernelGGL((k_eps_partial_reg<CT, NC(), CY(), NT()>), dim3((unsigned)(ng * eg.bpg)), dim3(kBlock), 0, s, x,
+                           (const CT *)p->d_color, p->N, p->d_partial, p->d_gsum, p->d_tick, ldp, p->cyc_C, p->cyc_shift, g0 * eg.bpg, eg,
+                           p->cx ? 1 : 0, p->d_eps, p->d_eps2);
+    });
     if (final) p->eps2_fresh = p->d_eps2 != nullptr;
     FD_HIP_CHECK(hipGetLastError());
     return FD_OK;
@@ -1360,15 +1362,9 @@ static int launch_eps_flags_t(fd_plan *p, const real_t *x, const FusedEps &fz)
 {
     hipStream_t s = p->ctx->stream;
     const unsigned grid = (unsigned)(fz.eg.C + fz.nblocks);
-#define FD_EPS_FZ(NCC, CY, NTT) hipLaunchKernelGGL((k_eps_flags<CT, NCC, CY, NTT>), dim3(grid), dim3(kBlock), 0, s, x, (const CT *)p->d_color, p->N, fz)
-#define FD_EPS_FZ_V(NCC)                                                                                        \
-    do {                                                                                                        \
-        if (p->cyc_C > 0) { if (p->eps_nt) FD_EPS_FZ(NCC, true, true); else FD_EPS_FZ(NCC, true, false); }       \
-        else { if (p->eps_nt) FD_EPS_FZ(NCC, false, true); else FD_EPS_FZ(NCC, false, false); }                 \
-    } while (0)
-    if (fz.eg.C <= 4) FD_EPS_FZ_V(4); else if (fz.eg.C <= 6) FD_EPS_FZ_V(6); else FD_EPS_FZ_V(kRegColors);
-#undef FD_EPS_FZ_V
-#undef FD_EPS_FZ
+    pick_eps_variant(p, fz.eg.C, [&](auto NC, auto CY, auto NT) {
+        hipLaunchKernelGGL((k_eps_flags<CT, NC(), CY(), NT()>), dim3(grid), dim3(kBlock), 0, s, x, (const CT *)p->d_color, p->N, fz);
+    });
     p->eps2_fresh = p->d_eps2 != nullptr;
     FD_HIP_CHECK(hipGetLastError());
     return FD_OK;
@@ -1422,20 +1418,16 @@ int launch_eps_perturb_small(fd_plan *p, const real_t *x, double relstep, double
 {
     hipStream_t s = p->ctx->stream;
     const int fwd = p->fdtype == FD_FORWARD ? 1 : 0;
-#define FD_SMALL(CT, NC, PM)                                                                                        \
-    hipLaunchKernelGGL((k_eps_perturb_small<CT, NC, PM>), dim3(1), dim3(kSmallBlock), 0, s, x, (const CT *)p->d_color, \
-                       p->N, relstep, absstep, dir, fwd, (int)p->C, p->d_eps, p->d_X, p->ldx, base_row)
-#define FD_SMALL_PM(CT, NC)                                                        \
-    switch (pmode) {                                                               \
-    case 0: FD_SMALL(CT, NC, 0); break;                                            \
-    case 1: FD_SMALL(CT, NC, 1); break;                                            \
-    case 2: FD_SMALL(CT, NC, 2); break;                                            \
-    default: FD_SMALL(CT, NC, -1); break;                                          \
-    }
-    if (p->color8) { if (p->C <= 4) { FD_SMALL_PM(uint8_t, 4) } else { FD_SMALL_PM(uint8_t, kRegColors) } }
-    else { if (p->C <= 4) { FD_SMALL_PM(int32_t, 4) } else { FD_SMALL_PM(int32_t, kRegColors) } }
-#undef FD_SMALL_PM
-#undef FD_SMALL
+    const auto launch = [&](auto ct) {
+        using CT = decltype(ct);
+        fd_pick<4, kRegColors>(p->C <= 4 ? 4 : kRegColors, [&](auto NC) {
+            fd_pick<0, 1, 2, -1>(pmode >= 0 && pmode <= 2 ? pmode : -1, [&](auto PM) {
+                hipLaunchKernelGGL((k_eps_perturb_small<CT, NC(), PM()>), dim3(1), dim3(kSmallBlock), 0, s, x, (const CT *)p->d_color,
+                                   p->N, relstep, absstep, dir, fwd, (int)p->C, p->d_eps, p->d_X, p->ldx, base_row);
+            });
+        });
+    };
+    if (p->color8) launch(uint8_t{}); else launch(int32_t{});
     FD_HIP_CHECK(hipGetLastError());
     return FD_OK;
 }
@@ -1468,14 +1460,11 @@ static int launch_perturb_tm(fd_plan *p, const real_t *x, int c_lo, int B)
 
 int launch_perturb(fd_plan *p, const real_t *x, int c_lo, int B)
 {
-#define FD_DISPATCH(CT)                                                        \
-    switch (p->fdtype) {                                                       \
-    case FD_FORWARD: return launch_perturb_tm<CT, 0>(p, x, c_lo, B);           \
-    case FD_CENTRAL: return launch_perturb_tm<CT, 1>(p, x, c_lo, B);           \
-    default: return launch_perturb_tm<CT, 2>(p, x, c_lo, B);                   \
-    }
-    if (p->color8) { FD_DISPATCH(uint8_t) } else { FD_DISPATCH(int32_t) }
-#undef FD_DISPATCH
+    int rc = FD_OK;
+    fd_pick<0, 1, 2>(p->fdtype == FD_FORWARD ? 0 : p->fdtype == FD_CENTRAL ? 1 : 2, [&](auto M) {
+        rc = p->color8 ? launch_perturb_tm<uint8_t, M()>(p, x, c_lo, B) : launch_perturb_tm<int32_t, M()>(p, x, c_lo, B);
+    });
+    return rc;
 }
 
 template <int MODE>
@@ -1495,34 +1484,33 @@ static void launch_window_m(fd_plan *p, const real_t *fx, const real_t *FXa, con
     const int narr = p->win_ncol;
     // (tiles are walked back to front: the end of the f! batch is what the Infinity Cache still holds -- DESIGN section 5)
     const int vok = ((((uintptr_t)out) & kPairMask) == 0 ? 1 : 0) | 4;
+    // both window kernels' <NCT, FV>: the tile's colours kept in registers (4, 6 or kWinMaxCol), f(x) read as pairs
+    const auto pick_win = [&](auto &&launch) {
+        fd_pick<4, 6, kWinMaxCol>(p->win_ncol <= 4 ? 4 : p->win_ncol <= 6 ? 6 : kWinMaxCol, [&](auto NCT) {
+            fd_pick<false, true>(fxvec, [&](auto FV) { launch(NCT, FV); });
+        });
+    };
     if (p->window2d) {
         const int64_t g2 = 8 * xcd_chunks(p->w2_ntiles);
         const size_t shm2 = sizeof(real_t) * ((size_t)wp * (size_t)narr + kWinMaxCol) + 4 * (size_t)kW2Desc;
-#define FD_LAUNCH_W2(NCT, FV)                                                                                      \
-        hipLaunchKernelGGL((k_decompress_window2d<MODE, NCT, FV>), dim3((unsigned)g2), dim3(kBlock), shm2, s,        \
-                           p->d_wcode, p->d_w2desc, FXa, FXb, p->ldf, p->M, p->d_eps, c_lo, c_hi, out, p->w2_ntiles,  \
-                           vok, wp)
-        if (p->win_ncol <= 4) { if (fxvec) FD_LAUNCH_W2(4, true); else FD_LAUNCH_W2(4, false); }
-        else if (p->win_ncol <= 6) { if (fxvec) FD_LAUNCH_W2(6, true); else FD_LAUNCH_W2(6, false); }
-        else { if (fxvec) FD_LAUNCH_W2(kWinMaxCol, true); else FD_LAUNCH_W2(kWinMaxCol, false); }
-#undef FD_LAUNCH_W2
+        pick_win([&](auto NCT, auto FV) {
+            hipLaunchKernelGGL((k_decompress_window2d<MODE, NCT(), FV()>), dim3((unsigned)g2), dim3(kBlock), shm2, s, p->d_wcode,
+                               p->d_w2desc, FXa, FXb, p->ldf, p->M, p->d_eps, c_lo, c_hi, out, p->w2_ntiles, vok, wp);
+        });
         return;
     }
     const int64_t ntl = (p->nnz_local + p->win_tile - 1) / p->win_tile, tile0 = 0;
     if (ntl <= 0) return;
     const int64_t gw = 8 * xcd_chunks(ntl);
     const size_t shmw = sizeof(real_t) * ((size_t)wp * (size_t)narr + kWinMaxCol) + kWinHeadBytes;
-#define FD_LAUNCH_WIN(NCT, FV, UU)                                                                              \
-    hipLaunchKernelGGL((k_decompress_window<MODE, NCT, FV, UU>), dim3((unsigned)gw), dim3(kBlock), shmw, s,     \
-                       (const uint32_t *)p->d_wcode, p->d_wtiles, FXa, FXb, p->ldf, p->M, p->d_eps, c_lo,       \
-                       c_hi, out, p->nnz_local, vok, wp, p->win_per_P, p->win_per_S, p->win_per_magic, tile0, ntl,  \
-                       p->bd_t0, p->bd_t1, p->band_off, p->band_w, p->band_u, (int)p->band_C, p->band_mw)
-#define FD_LAUNCH_WIN_U(NCT, FV) do { if (p->win_tile == 2048) FD_LAUNCH_WIN(NCT, FV, 4); else if (p->win_tile == 1024) FD_LAUNCH_WIN(NCT, FV, 2); else FD_LAUNCH_WIN(NCT, FV, 1); } while (0)
-    if (p->win_ncol <= 4) { if (fxvec) FD_LAUNCH_WIN_U(4, true); else FD_LAUNCH_WIN_U(4, false); }
-    else if (p->win_ncol <= 6) { if (fxvec) FD_LAUNCH_WIN_U(6, true); else FD_LAUNCH_WIN_U(6, false); }
-    else { if (fxvec) FD_LAUNCH_WIN_U(kWinMaxCol, true); else FD_LAUNCH_WIN_U(kWinMaxCol, false); }
-#undef FD_LAUNCH_WIN_U
-#undef FD_LAUNCH_WIN
+    pick_win([&](auto NCT, auto FV) {
+        fd_pick<4, 2, 1>(p->win_tile == 2048 ? 4 : p->win_tile == 1024 ? 2 : 1, [&](auto UU) {
+            hipLaunchKernelGGL((k_decompress_window<MODE, NCT(), FV(), UU()>), dim3((unsigned)gw), dim3(kBlock), shmw, s,
+                               (const uint32_t *)p->d_wcode, p->d_wtiles, FXa, FXb, p->ldf, p->M, p->d_eps, c_lo, c_hi, out, p->nnz_local,
+                               vok, wp, p->win_per_P, p->win_per_S, p->win_per_magic, tile0, ntl, p->bd_t0, p->bd_t1, p->band_off,
+                               p->band_w, p->band_u, (int)p->band_C, p->band_mw);
+        });
+    });
 }
 
 template <typename CT, int MODE>
@@ -1545,27 +1533,16 @@ static int launch_decompress_tm(fd_plan *p, const real_t *fx, int c_lo, int c_hi
             const int64_t gq = 8 * xcd_chunks((p->nnz_local + kSortTile - 1) / kSortTile);
             const size_t shmq = sizeof(real_t) * (size_t)(kSortTile + (ldsq ? B : 0)) + (allw ? 0 : (size_t)kSortTile);
             const int vok = ((((uintptr_t)outs[0]) & kPairMask) == 0 ? 1 : 0) | (tile_order_reversed() ? 4 : 0);
-#define FD_LAUNCH_SORTED(LL, AW, SS)                                                                                 \
-            do { if (MODE == 0 && p->d_fxwin)                                                                          \
-                hipLaunchKernelGGL((k_decompress_sorted<CT, MODE, LL, AW, SS, true>), dim3((unsigned)gq), dim3(kBlock), shmq, s, \
-                               p->d_rowval, (const CT *)p->d_nzcolor, p->d_spos, FXa, FXb, p->ldf, p->d_eps, c_lo,    \
-                               c_hi, outs[0], p->nnz_local, vok, p->d_tile_order, p->d_fxwin);                         \
-            else                                                                                                       \
-                hipLaunchKernelGGL((k_decompress_sorted<CT, MODE, LL, AW, SS, false>), dim3((unsigned)gq), dim3(kBlock), shmq, s, \
-                               p->d_rowval, (const CT *)p->d_nzcolor, p->d_spos, FXa, FXb, p->ldf, p->d_eps, c_lo,    \
-                               c_hi, outs[0], p->nnz_local, vok, p->d_tile_order, (const int32_t *)nullptr); } while (0)
-            if (p->sorted_gather) {
-                if (ldsq && allw) FD_LAUNCH_SORTED(true, true, true);
-                else if (ldsq) FD_LAUNCH_SORTED(true, false, true);
-                else if (allw) FD_LAUNCH_SORTED(false, true, true);
-                else FD_LAUNCH_SORTED(false, false, true);
-            } else {
-                if (ldsq && allw) FD_LAUNCH_SORTED(true, true, false);
-                else if (ldsq) FD_LAUNCH_SORTED(true, false, false);
-                else if (allw) FD_LAUNCH_SORTED(false, true, false);
-                else FD_LAUNCH_SORTED(false, false, false);
-            }
-#undef FD_LAUNCH_SORTED
+            // <LL, AW, SS = true, FW>: eps staged in LDS, every entry written, f(x) of the tile's rows staged (forward differences)
+            fd_pick<false, true>(ldsq, [&](auto LL) {
+                fd_pick<false, true>(allw, [&](auto AW) {
+                    fd_pick<false, true>(MODE == 0 && p->d_fxwin, [&](auto FW) {
+                        hipLaunchKernelGGL((k_decompress_sorted<CT, MODE, LL(), AW(), true, FW()>), dim3((unsigned)gq), dim3(kBlock), shmq,
+                                           s, p->d_rowval, (const CT *)p->d_nzcolor, p->d_spos, FXa, FXb, p->ldf, p->d_eps, c_lo, c_hi,
+                                           outs[0], p->nnz_local, vok, p->d_tile_order, FW() ? (const int32_t *)p->d_fxwin : nullptr);
+                    });
+                });
+            });
             break;
         }
         if (p->window && p->kind == K_CSC) {
@@ -1578,18 +1555,14 @@ static int launch_decompress_tm(fd_plan *p, const real_t *fx, int c_lo, int c_hi
         const bool lds = B <= kEpsLdsMax;
         const size_t shm = lds ? sizeof(real_t) * (size_t)B : 0;
         const int vec_ok = ((((uintptr_t)outs[0]) & kPairMask) == 0 ? 1 : 0) | (tile_order_reversed() ? 4 : 0);
-#define FD_LAUNCH_LIST(HD, UU, LL, DEST, VOK)                                                                    \
-        hipLaunchKernelGGL((k_decompress_list<CT, MODE, HD, UU, LL>), dim3((unsigned)g), dim3(kBlock), shm, s,   \
-                           p->d_rowval, (const CT *)p->d_nzcolor, DEST, FXa, FXb, p->ldf, p->d_eps, c_lo, c_hi, \
-                           outs[0], p->nnz_local, VOK)
-        if (p->kind == K_CSC) {
-            if (lds) FD_LAUNCH_LIST(false, 2, true, nullptr, vec_ok);
-            else FD_LAUNCH_LIST(false, 2, false, nullptr, vec_ok);
-        } else {
-            if (lds) FD_LAUNCH_LIST(true, 2, true, p->d_dest, vec_ok & 4);
-            else FD_LAUNCH_LIST(true, 2, false, p->d_dest, vec_ok & 4);
-        }
-#undef FD_LAUNCH_LIST
+        // <HD, U, LL>: destinations from a list (the dense targets; no vector stores then), eps staged in LDS
+        fd_pick<false, true>(p->kind != K_CSC, [&](auto HD) {
+            fd_pick<false, true>(lds, [&](auto LL) {
+                hipLaunchKernelGGL((k_decompress_list<CT, MODE, HD(), U, LL()>), dim3((unsigned)g), dim3(kBlock), shm, s, p->d_rowval,
+                                   (const CT *)p->d_nzcolor, HD() ? p->d_dest : nullptr, FXa, FXb, p->ldf, p->d_eps, c_lo, c_hi, outs[0],
+                                   p->nnz_local, HD() ? vec_ok & 4 : vec_ok);
+            });
+        });
         break;
     }
     case K_TRIDIAG: {
@@ -1666,14 +1639,12 @@ static int launch_decompress_tm(fd_plan *p, const real_t *fx, int c_lo, int c_hi
 
 int launch_decompress(fd_plan *p, const real_t *fx, int c_lo, int c_hi, real_t *const *outs, int mode)
 {
-#define FD_DISPATCH(CT)                                                                 \
-    switch (mode) {                                                                \
-    case FD_FORWARD: return launch_decompress_tm<CT, 0>(p, fx, c_lo, c_hi, outs);       \
-    case FD_CENTRAL: return launch_decompress_tm<CT, 1>(p, fx, c_lo, c_hi, outs);       \
-    default: return launch_decompress_tm<CT, 2>(p, fx, c_lo, c_hi, outs);               \
-    }
-    if (p->color8) { FD_DISPATCH(uint8_t) } else { FD_DISPATCH(int32_t) }
-#undef FD_DISPATCH
+    int rc = FD_OK;
+    fd_pick<0, 1, 2>(mode == FD_FORWARD ? 0 : mode == FD_CENTRAL ? 1 : 2, [&](auto M) {
+        rc = p->color8 ? launch_decompress_tm<uint8_t, M()>(p, fx, c_lo, c_hi, outs)
+                       : launch_decompress_tm<int32_t, M()>(p, fx, c_lo, c_hi, outs);
+    });
+    return rc;
 }
 
 int launch_fill(fd_ctx *ctx, real_t *ptr, int64_t n, real_t v)

@@ -1030,13 +1030,13 @@ static void pb_launch_tiles(bool codes, int T, bool band, int64_t grid, int64_t 
                             int ib, int base, const fd_plan *p, int64_t e0, int64_t nloc, const uint8_t *d_color8, int64_t ntiles, int4 *d_wt,
                             uint16_t *d_code, PbStats *d_st, int64_t bw, int64_t bu)
 {
-#define FD_PB_TILES(CC, TT, BB)                                                                                                       \
-    hipLaunchKernelGGL((k_pb_tiles<CC, TT, BB>), dim3((unsigned)grid), dim3(kBlock), 0, s, d_colptr, d_rowval, ib, base, p->col0, p->col1, e0, \
-                       nloc, p->M, d_color8, ntiles, d_wt, d_code, d_st, bw, bu, tstride)
-    if (!codes) { if (T == 2048) FD_PB_TILES(false, 2048, false); else if (T == 1024) FD_PB_TILES(false, 1024, false); else FD_PB_TILES(false, 512, false); }
-    else if (band) { if (T == 2048) FD_PB_TILES(true, 2048, true); else if (T == 1024) FD_PB_TILES(true, 1024, true); else FD_PB_TILES(true, 512, true); }
-    else { if (T == 2048) FD_PB_TILES(true, 2048, false); else if (T == 1024) FD_PB_TILES(true, 1024, false); else FD_PB_TILES(true, 512, false); }
-#undef FD_PB_TILES
+    // <CODES, T, BAND>, with <CODES, BAND> one of 0 = <false, false>, 1 = <true, false>, 2 = <true, true>: band only matters with codes
+    fd_pick<0, 1, 2>(!codes ? 0 : band ? 2 : 1, [&](auto CB) {
+        fd_pick<2048, 1024, 512>(T == 2048 ? 2048 : T == 1024 ? 1024 : 512, [&](auto TT) {
+            hipLaunchKernelGGL((k_pb_tiles<(CB() >= 1), TT(), (CB() == 2)>), dim3((unsigned)grid), dim3(kBlock), 0, s, d_colptr, d_rowval,
+                               ib, base, p->col0, p->col1, e0, nloc, p->M, d_color8, ntiles, d_wt, d_code, d_st, bw, bu, tstride);
+        });
+    });
 }
 
 static int device_build_lists(fd_plan *p, const void *d_colptr, const void *d_rowval, int ib, int base, int64_t e0, int64_t nloc,

@@ -1,6 +1,6 @@
-"""The complex step of the BLOCK-COUPLED residual (FD_F_BLOCKCOUPLED; csrc/fdjac_builtin_f.hip: k_f_block_sigma, k_f_block_apply,
-k_f_blockcoupled_lazy, k_f_blockcoupled_store) against a high-precision value, entry by entry.  Pure numpy + mpmath; test
-infrastructure only.  tests/test_exact_complex_cpu.py holds the C oracle to the bound, tests/test_gpu_exact_complex.py the storing
+"""The complex step of the BLOCK-COUPLED residual (FD_F_BLOCKCOUPLED; csrc/fdjac_builtin_f.hip: k_f_block_sigma, k_f_block_apply;
+csrc/fdjac_f_blockcoupled.hip: k_f_blockcoupled_lazy, k_f_blockcoupled_store) against a high-precision value, entry by entry.
+Pure numpy + mpmath; test infrastructure only.  tests/test_exact_complex_cpu.py holds the C oracle to the bound, tests/test_gpu_exact_complex.py the storing
 launch and the hand-over path.
 
 The residual.  nb blocks of bs coordinates; w_j = (j + 1) / bs for the j-th coordinate of a block; sig_b = sum_j w_j x_{b, j};

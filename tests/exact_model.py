@@ -1,4 +1,4 @@
-"""Exact host model of what the storing kernels promise (csrc/fdjac_builtin_f.hip, include/fdjac_device.h): the BITS of the plain
+"""Exact host model of what the storing kernels promise (csrc/fdjac_f_*.hip, include/fdjac_device.h): the BITS of the plain
 colour-by-colour evaluation of src/jacobians.jl:537-622, restated in vectorised numpy independently of the library.  Test
 infrastructure only.
 

@@ -58,7 +58,7 @@ def np_dtype(case):
 
 
 def has_lazy(case):
-    """The built-in family has a lazy JVP launcher (csrc/fdjac_builtin_f.hip, has_lazy_jvp)."""
+    """The built-in family has a lazy JVP launcher (csrc/fdjac_f_jvp.hip, has_lazy_jvp)."""
     fam = case["family"]
     return fam.startswith("tridiag") or (fam.startswith("lap5") and case["prm"][0] % 2 == 0)
 

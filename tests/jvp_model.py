@@ -1,5 +1,5 @@
 """Exact host model of the finite-difference JVP (csrc/fdjac_jvp.hip: fd_jvp, fd_jvp_async; the lazy JVP kernels of
-csrc/fdjac_builtin_f.hip), restated in numpy independently of the library, one IEEE operation at a time.  Test infrastructure only.
+csrc/fdjac_f_jvp.hip), restated in numpy independently of the library, one IEEE operation at a time.  Test infrastructure only.
 
   dot(x, v)    Float64 products of the elements cast to Float64, summed in one of THREE defined orders:
                  dot_small    k_jvp_small: 1024 threads of one workgroup, thread t takes t, t + 1024, ...; the 64-lane tree

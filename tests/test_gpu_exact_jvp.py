@@ -1,4 +1,4 @@
-"""The finite-difference JVP (csrc/fdjac_jvp.hip: fd_jvp, fd_jvp_async; the lazy JVP kernels of csrc/fdjac_builtin_f.hip) against the
+"""The finite-difference JVP (csrc/fdjac_jvp.hip: fd_jvp, fd_jvp_async; the lazy JVP kernels of csrc/fdjac_f_jvp.hip) against the
 exact host model (tests/jvp_model.py), bit for bit, on every route: the fused small launch, the materialised points paired and scalar,
 the lazy launchers' values and finished quotient, a launcher that declines (FD_LAZY_DECLINED -- no built-in launcher can, so a ctypes
 callback does), host staging, fd_jvp_async and a second call on the same cache.  The step size is compared with the model's in the

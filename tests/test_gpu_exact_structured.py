@@ -19,7 +19,7 @@ launch.)  A plan whose columns ALL lack a colour zero-fills the destination and 
 
 FOUND.  k_f_stencil5_store_bbb stored a constant 0 / eps in the four corner slots of a column (rows (i +- 1, j +- 1)); the model, the
 hand-over path and fd_bbb_store_cols store the row's difference with itself over the step -- NaN where the row reads a NaN / Inf
-coordinate: 58 of 10 800 values of bbb-40x30x1-lap5_nl-wide-store-forward-f64-nan_inf.  Fixed in csrc/fdjac_builtin_f.hip.
+coordinate: 58 of 10 800 values of bbb-40x30x1-lap5_nl-wide-store-forward-f64-nan_inf.  Fixed in csrc/fdjac_f_stencil5.hip.
 
 WHAT THE LIBRARY HAS NO SWITCH FOR.  k_decompress_colrange_wg's paired form is chosen by the layout and the destination's alignment
 alone and its tile order is fixed (reversed): the variant "scalar" reaches the scalar instantiation on an even layout through a

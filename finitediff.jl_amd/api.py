@@ -654,7 +654,7 @@ class CscSolver(_CscConsumer):
     """fd_csc_solver: the sparse consumer.  For a square J in ``SparseMatrixCSC`` storage -- the nzval a CSC plan has just written, left
     on the device -- ``matvec`` enqueues y = (alpha*I + beta*J) v (or its transpose) and ``solve`` enqueues y = (alpha*I + beta*J)^-1 b by
     BiCGStab whose scalars never leave the device, preconditioned by the diagonal or (``set_preconditioner``) by the inverses of the
-    diagonal blocks.  ``pattern`` is a ``SparseMatrixCSC`` / ``DevicePatternCSC`` or
+    diagonal blocks; ``set_method("gmres", restart)`` exchanges BiCGStab for restarted GMRES.  ``pattern`` is a ``SparseMatrixCSC`` / ``DevicePatternCSC`` or
     ``(colptr, rowval, N)`` with numpy arrays or CUDA tensors of int32 / int64 (``idx_base``-based).  A solve that does not converge
     within ``max_iterations`` (``status()`` flags bit 0) or breaks down (bit 1) fills y with NaN unless ``set_policy(True)``."""
 
@@ -723,6 +723,28 @@ class CscSolver(_CscConsumer):
         dev = "cuda:%d" % self.ctx.device
         lu = torch.as_tensor(_DevView(pl.value, nnz.value, False), device=dev).clone() if nnz.value else torch.empty(0, dtype=torch.float64, device=dev)
         return lu, torch.as_tensor(_DevView(pu.value, self.N, False), device=dev).clone(), bs.value
+
+    METHODS = {"bicgstab": 0, "gmres": 1}
+
+    def set_method(self, method="bicgstab", restart=30):
+        """``"bicgstab"`` (the default) or ``"gmres"``: right-preconditioned restarted GMRES(``restart``), ``restart`` in 1..64, with
+        whichever preconditioner is selected (fd_csc_solver_set_method).  ``set_options``, ``set_policy`` and ``status`` mean the same
+        under either method; under GMRES ``max_iterations`` caps the Arnoldi steps and ``resid`` is the last residual estimate."""
+        if method not in self.METHODS:
+            raise ValueError("method must be 'bicgstab' or 'gmres'")
+        _l.check(self.Lt.fd_csc_solver_set_method(self.handle, self.METHODS[method], int(restart)))
+
+    def gmres_basis(self):
+        """Synchronises.  Diagnostic: the last cycle of the last GMRES solve as float64 CUDA tensors (copies) -- V (restart + 1, N), the
+        basis vectors as rows, and H (restart, restart + 1), the Hessenberg columns as rows -- and the number of columns that cycle
+        completed: rows 0 .. len - 1 of either are valid."""
+        import torch
+        pv, ph, m, k = C.c_void_p(), C.c_void_p(), C.c_int(), C.c_int()
+        _l.check(self.Lt.fd_csc_solver_gmres_basis(self.handle, C.byref(pv), C.byref(ph), C.byref(m), C.byref(k)))
+        dev = "cuda:%d" % self.ctx.device
+        V = torch.as_tensor(_DevView(pv.value, (m.value + 1) * self.N, False), device=dev).clone().reshape(m.value + 1, self.N)
+        H = torch.as_tensor(_DevView(ph.value, m.value * (m.value + 1), False), device=dev).clone().reshape(m.value, m.value + 1)
+        return V, H, k.value
 
     def row_lists(self):
         """The solver's lists as int32 CUDA tensors (copies): row_ptr, row_col, row_slot, diag_slot; and the number of long rows."""

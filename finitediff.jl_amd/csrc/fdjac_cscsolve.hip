@@ -44,6 +44,9 @@
 //   apply (k_cs_ilu_apply): the block's x in LDS; forward, levels ascending: t = x_i, t = t - l_ik z_k (k ascending), z_i = t; backward:
 //     t = z_i, t = t - u_ij z_j (j ascending), z_i = t / u_i.
 // An iteration is 7 launches (+ 2 with long rows) as with block Jacobi.  tests/csc_ilu_model.py restates all of it.
+//
+// GMRES (fd_csc_solver_set_method): restarted, right-preconditioned by any of the three above, beside BiCGStab on the same handle; its
+// kernels and its orders are in fdjac_cscgmres.hip, included below; the host loop is csc_gmres_iterate() here.
 #include "fdjac_internal.h"
 #include "fdjac_device.h"
 #include "fdjac_csc_common.h"
@@ -58,7 +61,10 @@ constexpr int kCsBinvWaves = 2;        // blocks (one wavefront each) per workgr
 constexpr int kCsIluBsMax = FD_CSC_ILU_BS_MAX;      // the largest block of block ILU(0): its x / z fill 8 KiB of LDS
 constexpr int kCsPcIlu = 2;            // pc_kind of block ILU(0): the solver's own, fd_csc_solver_set_preconditioner does not take it
 // scalars of a solve, in device memory: doubles ...
-enum { S_RHO = 0, S_RHO_OLD, S_ALPHA, S_OMEGA, S_BNORM2, S_TOL2, S_RNORM2, S_SNORM2, S_NSCAL };      // (the words and the record: fdjac_csc_common.h)
+enum { S_RHO = 0, S_RHO_OLD, S_ALPHA, S_OMEGA, S_BNORM2, S_TOL2, S_RNORM2, S_SNORM2,      // (the words and the record: fdjac_csc_common.h)
+       S_GAMMA2, S_GTOL, S_GRES, S_NSCAL };      // GMRES: ||r||^2 at a cycle's start, rtol ||b||, the last residual estimate
+constexpr int W_GM_K = 6, W_GM_UPD = 7;          // GMRES: the cycle's completed columns; the columns its end adds to y (0: none)
+static_assert(W_GM_UPD < W_NWORDS, "the words of a solve");
 
 // ---- products --------------------------------------------------------------------------------------------------------------------------
 // The long rows first (k_cs_long<false, CS_LONG_AXPBY>: y_r = alpha v_r + beta sum), then the rows.
@@ -66,7 +72,8 @@ enum { S_RHO = 0, S_RHO_OLD, S_ALPHA, S_OMEGA, S_BNORM2, S_TOL2, S_RNORM2, S_SNO
 // goes through an LDS window of the tile's rows and `reach` elements on either side (anything outside it is read from memory: the
 // bits do not depend on the window); a wider pattern reads v from memory; the results cross LDS once so that y is
 // written -- and the dots are summed -- in row order.  MODE 0: y only.  1: + dot(c, y) -> alpha (the first product of an
-// iteration).  2: + dot(y, c), dot(y, y) -> omega (the second).
+// iteration).  2: + dot(y, c), dot(y, y) -> omega (the second).  3, 4: y only, guarded like 2 and like 1 (GMRES: a step's product and
+// the explicit residual's).
 template <typename TV, int MODE>
 __global__ void __launch_bounds__(kBlock) k_cs_rows(CsView P, double alpha, double beta, const real_t *__restrict__ nz, const TV *__restrict__ v,
                                                     TV *__restrict__ y, const double *__restrict__ c, double *scal, int *words, double *part)
@@ -74,7 +81,7 @@ __global__ void __launch_bounds__(kBlock) k_cs_rows(CsView P, double alpha, doub
     extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
     __shared__ double s_out[kBlock];
     __shared__ double s_w[kBlock / 64];
-    if (MODE != 0 && (cs_word(words, W_DONE) || (MODE == 2 && cs_word(words, W_EARLY)))) return;
+    if (MODE != 0 && (cs_word(words, W_DONE) || ((MODE == 2 || MODE == 3) && cs_word(words, W_EARLY)))) return;
     TV *s_v = (TV *)s_raw;
     const int ntile = (P.N + kBlock - 1) / kBlock;
     const int tile = MODE == 0 ? (int)fd_xcd_block(blockIdx.x, ntile) : (int)blockIdx.x;
@@ -426,6 +433,8 @@ __global__ void __launch_bounds__(kBlock) k_cs_final(int N, const double *__rest
 
 }  // namespace fdjac
 
+#include "fdjac_cscgmres.hip"
+
 struct fd_csc_solver : fdjac::CscHandle {      // d_vec: ten vectors of N doubles
     int window = 1;
     int pc_kind = FD_CSC_PRECOND_JACOBI, pc_bs = 0;      // what the next solve uses
@@ -437,8 +446,15 @@ struct fd_csc_solver : fdjac::CscHandle {      // d_vec: ten vectors of N double
     bool ilu_factored = false;         // a block-ILU solve has run on this schedule
     int *d_ilu_int = nullptr;          // run (4 N) | lev_f | lev_b | ord_f | ord_b (N each) | off_f | off_b (nblk (bs + 1) each) | nlev_f | nlev_b (nblk each)
     double *d_ilu = nullptr;
+    // GMRES (fd_csc_solver_set_method): what the next solve uses, and the buffers of the last GMRES solve (fdjac_cscgmres.hip: CsGm)
+    int method = FD_CSC_METHOD_BICGSTAB, gm_restart = 30;
+    double *d_gm = nullptr;
+    size_t gm_cap = 0;                 // doubles allocated
+    int gm_m = 0;                      // the restart of the last GMRES solve, 0: none yet
+    bool last_gmres = false;           // the last solve was a GMRES solve: its status reads the estimate
     ~fd_csc_solver()
     {
+        if (d_gm) (void)hipFree(d_gm);
         if (d_minv) (void)hipFree(d_minv);
         if (d_ilu_int) (void)hipFree(d_ilu_int);
         if (d_ilu) (void)hipFree(d_ilu);
@@ -490,6 +506,61 @@ int fd_csc_solver_set_preconditioner(fd_csc_solver *s, int kind, int block_size)
         FD_REQUIRE(block_size >= 2 && block_size <= kCsBsMax, FD_ERR_ARG, "block_size = %d (2 .. %d)", block_size, kCsBsMax);
     s->pc_kind = kind;
     s->pc_bs = kind == FD_CSC_PRECOND_BLOCK_JACOBI ? block_size : 0;
+    return FD_OK;
+}
+
+int fd_csc_solver_set_method(fd_csc_solver *s, int method, int restart)
+{
+    FD_REQUIRE(s != nullptr, FD_ERR_ARG, "solver is NULL");
+    FD_REQUIRE(method == FD_CSC_METHOD_BICGSTAB || method == FD_CSC_METHOD_GMRES, FD_ERR_ARG, "method = %d (0: BiCGStab, 1: GMRES)", method);
+    if (method == FD_CSC_METHOD_GMRES) {
+        FD_REQUIRE(restart >= 1 && restart <= kGmMax, FD_ERR_ARG, "restart = %d (1 .. %d)", restart, kGmMax);
+        s->gm_restart = restart;
+    }
+    s->method = method;
+    return FD_OK;
+}
+
+// the buffers of a GMRES solve with restart m in d_gm (CsGm's arrays in its order, then the partial sums and one slot for klast)
+static size_t gm_doubles(size_t N, int m, size_t ntile)
+{
+    const size_t k = (size_t)m;
+    return (k + 1) * N + 2 * k * (k + 1) + 2 * k + (k + 1) + k + 2 * (k + 1) + (k + 2) * ntile + 1;
+}
+static CsGm csc_gm(const fd_csc_solver *s, int m)
+{
+    const size_t N = (size_t)s->L.N, k = (size_t)m, ntile = cs_tiles(s->L.N, kCsVecTile);
+    CsGm G;
+    double *p = s->d_gm;
+    G.m = m; G.ntile = (int)ntile;
+    G.V = p; p += (k + 1) * N;
+    G.H = p; p += k * (k + 1);
+    G.R = p; p += k * (k + 1);
+    G.c = p; p += k;
+    G.s = p; p += k;
+    G.g = p; p += k + 1;
+    G.t = p; p += k;
+    G.h1 = p; p += k + 1;
+    G.h2 = p; p += k + 1;
+    G.part = p; p += (k + 2) * ntile;
+    G.klast = (int *)p;
+    return G;
+}
+
+// the basis and the Hessenberg columns of the last cycle of the last GMRES solve, for the tests: owned by the solver; synchronises
+int fd_csc_solver_gmres_basis(fd_csc_solver *s, const void **V_dev, const void **H_dev, int *restart, int *last_cycle_len)
+{
+    FD_REQUIRE(s != nullptr, FD_ERR_ARG, "solver is NULL");
+    FD_REQUIRE(s->gm_m > 0, FD_ERR_UNSUPPORTED, "no GMRES solve has run on this solver");
+    const CsGm G = csc_gm(s, s->gm_m);
+    if (V_dev) *V_dev = G.V;
+    if (H_dev) *H_dev = G.H;
+    if (restart) *restart = s->gm_m;
+    if (last_cycle_len) {
+        FD_HIP_CHECK(hipSetDevice(s->ctx->device));
+        FD_HIP_CHECK(hipStreamSynchronize(s->ctx->stream));
+        FD_HIP_CHECK(hipMemcpy(last_cycle_len, G.klast, sizeof(int), hipMemcpyDeviceToHost));
+    }
     return FD_OK;
 }
 
@@ -661,6 +732,75 @@ int fd_csc_matvec_async(fd_csc_solver *s, double alpha, double beta, const void 
     return FD_OK;
 }
 
+// The GMRES iterations behind the start kernels (fdjac_cscgmres.hip has the algorithm).  apply(which, x, out): out = M^-1 x of a block
+// preconditioner; which = 1 is skipped once the cycle is over, which = 0 only once the solve is.
+template <class A>
+static int csc_gmres_iterate(fd_csc_solver *s, double alpha, double beta, const real_t *nz, const real_t *b, const CsVecs &V, bool blocks, A apply)
+{
+    hipStream_t st = s->ctx->stream;
+    CscSolveState &S = s->S;
+    const int N = (int)s->L.N, m = s->gm_m;
+    const size_t n = (size_t)N;
+    const unsigned gv = cs_tiles(N, kCsVecTile);
+    const CsGm G = csc_gm(s, m);
+    double *z = V.p, *w = V.v, *u = V.s, *npart = G.part + (size_t)(m + 1) * G.ntile;
+    int *words = S.d_words;
+    hipLaunchKernelGGL(k_gm_start<true>, dim3(gv), dim3(kBlock), 0, st, N, (const double *)V.r, G, S.rtol, S.d_scal, (const int *)words);
+    const auto step = [&](int j) {      // 10 launches (+ 1 with long rows)
+        const double *vj = G.V + (size_t)j * n;
+        if (blocks) apply(1, vj, z);
+        else hipLaunchKernelGGL(k_gm_scale<true>, dim3(gv), dim3(kBlock), 0, st, N, vj, (const double *)V.d, z, (const int *)words);
+        csc_product<double, 3>(s, alpha, beta, nz, z, w, nullptr, true);
+        for (int pass = 0; pass < 2; ++pass) {
+            double *h = pass ? G.h2 : G.h1;
+            hipLaunchKernelGGL(k_cs_gs_dots, dim3(gv), dim3(kBlock), 0, st, N, j + 1, (const double *)w, (const double *)G.V, G.part, (const int *)words);
+            hipLaunchKernelGGL(k_cs_gs_reduce, dim3(j + 1), dim3(kBlock), 0, st, G.ntile, (const double *)G.part, h, (const int *)words);
+            fd_pick<false, true>(pass == 1, [&](auto NORM) {
+                hipLaunchKernelGGL(k_cs_gs_update<NORM()>, dim3(gv), dim3(kBlock), 0, st, N, j + 1, w, (const double *)G.V, (const double *)h, npart, (const int *)words);
+            });
+        }
+        hipLaunchKernelGGL(k_gm_hess, dim3(1), dim3(kBlock), 0, st, j, G, S.max_iterations, S.d_scal, words);
+        hipLaunchKernelGGL(k_gm_scale<false>, dim3(gv), dim3(kBlock), 0, st, N, (const double *)w, (const double *)(G.H + (size_t)j * (m + 1) + j + 1),
+                           G.V + (size_t)(j + 1) * n, (const int *)words);
+    };
+    const auto cycle_end = [&] {
+        hipLaunchKernelGGL(k_gm_tri, dim3(1), dim3(64), 0, st, G, words);
+        fd_pick<false, true>(!blocks, [&](auto DIAG) {
+            hipLaunchKernelGGL(k_gm_combine<DIAG()>, dim3(gv), dim3(kBlock), 0, st, N, G, (const double *)V.d, DIAG() ? V.y : u, (const int *)words);
+        });
+        if (blocks) {
+            apply(0, u, z);
+            hipLaunchKernelGGL(k_gm_yadd, dim3(gv), dim3(kBlock), 0, st, N, V.y, (const double *)z, (const int *)words);
+        }
+        hipLaunchKernelGGL(k_gm_close, dim3(1), dim3(64), 0, st, words);
+        csc_product<double, 4>(s, alpha, beta, nz, V.y, w, nullptr, true);
+        hipLaunchKernelGGL(k_gm_resid, dim3(gv), dim3(kBlock), 0, st, N, b, (const double *)w, V.r, S.d_scal, words, S.d_part);
+        hipLaunchKernelGGL(k_gm_start<false>, dim3(gv), dim3(kBlock), 0, st, N, (const double *)V.r, G, S.rtol, S.d_scal, (const int *)words);
+    };
+    // batches as in CscSolveState::run, but a batch ends where its cycle does, and the cycle's end goes with it
+    int enq = 0, j = 0, nb = 0;
+    bool stop = false;
+    while (!stop) {
+        int todo = S.max_iterations - enq < S.batch ? S.max_iterations - enq : S.batch;
+        if (m - j < todo) todo = m - j;
+        for (int it = 0; it < todo; ++it) step(j++);
+        enq += todo;
+        if (j == m || enq >= S.max_iterations) { cycle_end(); j = 0; }
+        FD_HIP_CHECK(hipGetLastError());
+        FD_HIP_CHECK(hipMemcpyAsync(&S.h_rec[nb & 1], S.d_words, sizeof(CsRecord), hipMemcpyDeviceToHost, st));
+        FD_HIP_CHECK(hipEventRecord(S.ev[nb & 1], st));
+        if (nb >= 1) {
+            FD_HIP_CHECK(hipEventSynchronize(S.ev[(nb - 1) & 1]));
+            const CsRecord &rec = S.h_rec[(nb - 1) & 1];
+            if (rec.done) stop = true;
+            else if (rec.early) { cycle_end(); stop = true; }      // the cycle ended in the middle of that batch: what it has goes into y
+        }
+        ++nb;
+        if (enq >= S.max_iterations) stop = true;
+    }
+    return FD_OK;
+}
+
 int fd_csc_solve_async(fd_csc_solver *s, double alpha, double beta, const void *nzval, const void *b, void *y)
 {
     FD_REQUIRE(s && b && y && (nzval || s->L.nnz == 0), FD_ERR_ARG, "NULL argument");
@@ -682,6 +822,19 @@ int fd_csc_solve_async(fd_csc_solver *s, double alpha, double beta, const void *
         const hipError_t e = hipMalloc((void **)&s->d_minv, sizeof(double) * (size_t)bs * n);
         if (e != hipSuccess) { (void)hipGetLastError(); FD_REQUIRE(false, FD_ERR_NOMEM, "block Jacobi: %d planes of %d doubles: %s", bs, N, hipGetErrorString(e)); }
         s->minv_cap = (size_t)bs * n;
+    }
+    const bool gmres = s->method == FD_CSC_METHOD_GMRES;
+    if (gmres && (s->gm_cap < gm_doubles(n, s->gm_restart, gv) || s->gm_m != s->gm_restart)) {
+        FD_HIP_CHECK(hipStreamSynchronize(st));
+        const size_t need = gm_doubles(n, s->gm_restart, gv);
+        if (s->gm_cap < need) {
+            if (s->d_gm) (void)hipFree(s->d_gm);
+            s->d_gm = nullptr; s->gm_cap = 0; s->gm_m = 0;
+            const hipError_t e = hipMalloc((void **)&s->d_gm, sizeof(double) * need);
+            if (e != hipSuccess) { (void)hipGetLastError(); FD_REQUIRE(false, FD_ERR_NOMEM, "GMRES: %d + 1 vectors of %d doubles: %s", s->gm_restart, N, hipGetErrorString(e)); }
+            s->gm_cap = need;
+        }
+        s->gm_m = s->gm_restart;
     }
     FD_HIP_CHECK(hipMemsetAsync(S.d_words, 0, sizeof(int) * W_NWORDS, st));
     const bool ilu = s->pc_kind == kCsPcIlu, blocks = ilu || bs > 0;      // blocks: the PC = 1 instances of the vector kernels
@@ -705,6 +858,16 @@ int fd_csc_solve_async(fd_csc_solver *s, double alpha, double beta, const void *
         hipLaunchKernelGGL(k_cs_binv, dim3(cs_tiles(cs_tiles(N, bs), kCsBinvWaves)), dim3(kCsBinvWaves * 64),
                            sizeof(double) * (size_t)kCsBinvWaves * (size_t)(bs * (2 * bs + 1) + bs), st, P, bs, alpha, beta, nz, s->d_minv, S.d_words);
         s->minv_bs = bs;
+    }
+    s->last_gmres = gmres;
+    if (gmres) {
+        const int rc = csc_gmres_iterate(s, alpha, beta, nz, (const real_t *)b, V, blocks, apply);
+        if (rc != FD_OK) return rc;
+        hipLaunchKernelGGL(k_gm_final, dim3(cs_tiles(N, kBlock)), dim3(kBlock), 0, st, N, (const double *)V.y, (real_t *)y, S.d_words,
+                           csc_gm(s, s->gm_m).klast, S.keep);
+        FD_HIP_CHECK(hipGetLastError());
+        S.solved = true;
+        return FD_OK;
     }
     const int rc = S.run(st, [&] {      // one iteration: 5 launches (+ 2 with long rows, + 2 with block Jacobi or block ILU)
         if (blocks) hipLaunchKernelGGL(k_cs_p<1>, dim3(gv), dim3(kBlock), 0, st, N, V, scal, words);
@@ -733,7 +896,7 @@ int fd_csc_solver_status(fd_csc_solver *s, int *flags_out, int64_t *iterations_o
     if (rc != FD_OK) return rc;
     if (flags_out) *flags_out = w[W_FINAL];
     if (iterations_out) *iterations_out = w[W_ITERS];
-    if (resid_out) *resid_out = std::sqrt(sc[S_RNORM2]);
+    if (resid_out) *resid_out = s->last_gmres ? sc[S_GRES] : std::sqrt(sc[S_RNORM2]);
     if (bnorm_out) *bnorm_out = std::sqrt(sc[S_BNORM2]);
     return FD_OK;
 }

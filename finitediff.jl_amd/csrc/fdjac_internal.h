@@ -79,6 +79,8 @@
 #define fd_csc_solver_set_block_ilu fd32_csc_solver_set_block_ilu
 #define fd_csc_solver_ilu_levels fd32_csc_solver_ilu_levels
 #define fd_csc_solver_ilu_factors fd32_csc_solver_ilu_factors
+#define fd_csc_solver_set_method fd32_csc_solver_set_method
+#define fd_csc_solver_gmres_basis fd32_csc_solver_gmres_basis
 #define fd_csc_matvec_async fd32_csc_matvec_async
 #define fd_csc_solve_async fd32_csc_solve_async
 #define fd_csc_solver_status fd32_csc_solver_status

@@ -85,7 +85,7 @@ EXPORTS = (
     "fd_blocktridiag_solver_create", "fd_blocktridiag_solver_destroy", "fd_blocktridiag_solver_set_policy", "fd_blocktridiag_solver_status",
     "fd_blocktridiag_solve_async",
     "fd_csc_solver_create", "fd_csc_solver_destroy", "fd_csc_matvec_async", "fd_csc_solver_set_options", "fd_csc_solver_set_policy", "fd_csc_solve_async", "fd_csc_solver_status", "fd_csc_solver_row_lists",
-    "fd_csc_solver_set_preconditioner", "fd_csc_solver_block_inverses", "fd_csc_solver_set_block_ilu", "fd_csc_solver_ilu_levels", "fd_csc_solver_ilu_factors",
+    "fd_csc_solver_set_preconditioner", "fd_csc_solver_block_inverses", "fd_csc_solver_set_block_ilu", "fd_csc_solver_ilu_levels", "fd_csc_solver_ilu_factors", "fd_csc_solver_set_method", "fd_csc_solver_gmres_basis",
     "fd_csc_lsq_create", "fd_csc_lsq_destroy", "fd_csc_lsq_matvec_async", "fd_csc_lsq_set_options", "fd_csc_lsq_set_policy", "fd_csc_lsq_solve_async", "fd_csc_lsq_status", "fd_csc_lsq_row_lists", "fd_csc_lsq_long_columns",
     "fd_csc_tr_create", "fd_csc_tr_destroy", "fd_csc_tr_set_options", "fd_csc_tr_set_policy", "fd_csc_tr_matvec_async", "fd_csc_tr_step_async", "fd_csc_tr_status",
     "fd_objective_compile", "fd_objective_destroy", "fd_objective_counts", "fd_hess_plan_create", "fd_hess_plan_destroy",
@@ -110,7 +110,7 @@ TYPED = (
     "fd_blocktridiag_solver_create", "fd_blocktridiag_solver_destroy", "fd_blocktridiag_solver_set_policy", "fd_blocktridiag_solver_status",
     "fd_blocktridiag_solve_async",
     "fd_csc_solver_create", "fd_csc_solver_destroy", "fd_csc_matvec_async", "fd_csc_solver_set_options", "fd_csc_solver_set_policy", "fd_csc_solve_async", "fd_csc_solver_status", "fd_csc_solver_row_lists",
-    "fd_csc_solver_set_preconditioner", "fd_csc_solver_block_inverses", "fd_csc_solver_set_block_ilu", "fd_csc_solver_ilu_levels", "fd_csc_solver_ilu_factors",
+    "fd_csc_solver_set_preconditioner", "fd_csc_solver_block_inverses", "fd_csc_solver_set_block_ilu", "fd_csc_solver_ilu_levels", "fd_csc_solver_ilu_factors", "fd_csc_solver_set_method", "fd_csc_solver_gmres_basis",
     "fd_csc_lsq_create", "fd_csc_lsq_destroy", "fd_csc_lsq_matvec_async", "fd_csc_lsq_set_options", "fd_csc_lsq_set_policy", "fd_csc_lsq_solve_async", "fd_csc_lsq_status", "fd_csc_lsq_row_lists", "fd_csc_lsq_long_columns",
 )
 EXPORTS = EXPORTS + tuple("fd32_" + n[3:] for n in TYPED)
@@ -297,6 +297,8 @@ def load():
     L.fd_csc_solver_set_block_ilu.argtypes = [vp, i32]
     L.fd_csc_solver_ilu_levels.argtypes = [vp, pp, pp, C.POINTER(i32), C.POINTER(i32)]
     L.fd_csc_solver_ilu_factors.argtypes = [vp, pp, pp, C.POINTER(i64), C.POINTER(i32)]
+    L.fd_csc_solver_set_method.argtypes = [vp, i32, i32]
+    L.fd_csc_solver_gmres_basis.argtypes = [vp, pp, pp, C.POINTER(i32), C.POINTER(i32)]
     L.fd_csc_lsq_create.argtypes = [vp, i64, i64, vp, vp, i32, i32, i32, pp]
     L.fd_csc_lsq_destroy.argtypes = [vp]
     L.fd_csc_lsq_matvec_async.argtypes = [vp, vp, vp, vp, i32]

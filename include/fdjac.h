@@ -761,8 +761,31 @@ int fd_banded_solve_async(fd_banded_solver *solver, double alpha, double beta, c
  *                         fd_csc_solver_row_lists (l_ik at the in-block lower positions, the final u_ij at the upper ones, u_ii at a
  *                         stored diagonal's, +0.0 at every position outside the row's block), and u, the N diagonals u_ii.  Any out
  *                         pointer may be NULL.  The layout may change with the solver.
+ *   fd_csc_solver_set_method  FD_CSC_METHOD_BICGSTAB (the default: everything above, restart ignored) or FD_CSC_METHOD_GMRES with restart
+ *                         in 1..FD_CSC_GMRES_RESTART_MAX: right-preconditioned restarted GMRES(restart) for the following solves, with
+ *                         whichever preconditioner is selected.  Any other method or restart is FD_ERR_ARG.  May be called between
+ *                         solves.  Under GMRES the other entry points mean what they mean above: y0 = 0; the solve stops when the
+ *                         residual estimate |g_j+1| of the rotated least-squares problem (at a restart: the explicit ||b - A y||_2) is
+ *                         <= rtol * ||b||_2; max_iterations caps the Arnoldi steps (one preconditioned product each; the explicit
+ *                         residual of a restart does not count); b = 0: y = 0, no iteration.  Status bit 0: the iterations ran out; bit
+ *                         1: breakdown (a bad preconditioner pivot as above, or ||b||^2, a Hessenberg entry, a rotation or a pivot of the
+ *                         triangular solve not finite, or such a pivot zero).  After either failure y is NaN, unless
+ *                         fd_csc_solver_set_policy(solver, 1): then y is the iterate of the columns completed so far.  resid is the last
+ *                         estimate.  An H[j + 1, j] that is exactly zero ends the cycle: converged, or a zero pivot.  Orthogonalisation is
+ *                         classical Gram-Schmidt applied twice (CGS2); every order is fixed (GMRES): the same bits every
+ *                         call.  A step is 10 launches (+ 1 with long rows) and streams about 4 j + 16 vectors at column j.  The
+ *                         first GMRES solve allocates (restart + 1) * N doubles for the basis and about 2 restart^2 + (restart + 2) *
+ *                         ceil(N / 1024) doubles beside it; freed with the solver.  No flexible variant, no warm start.  NOT TIMED.
+ *   fd_csc_solver_gmres_basis  DIAGNOSTIC ONLY (FD_ERR_UNSUPPORTED before the first GMRES solve): device pointers, owned by the solver, to
+ *                         the basis of the last cycle of the last GMRES solve (vector-major: v_i at V + i * N) and to its Hessenberg
+ *                         columns as Arnoldi gave them (column j at H + j * (restart + 1)), that solve's restart, and the columns the
+ *                         last cycle completed (v_0 .. v_len-1 and columns 0 .. len-1 are valid; reading it synchronises).  Any out
+ *                         pointer may be NULL.  The layout may change with the solver.
  * Everything is enqueued on the context's stream; fd_csc_solver_create and fd_csc_solver_status synchronise it.  Without a device
  * fd_csc_solver_create is FD_ERR_NODEVICE. */
+#define FD_CSC_METHOD_BICGSTAB       0   /* the default */
+#define FD_CSC_METHOD_GMRES          1
+#define FD_CSC_GMRES_RESTART_MAX     64   /* the largest restart of fd_csc_solver_set_method */
 #define FD_CSC_PRECOND_JACOBI        0   /* the default */
 #define FD_CSC_PRECOND_BLOCK_JACOBI  1
 #define FD_CSC_ILU_BS_MAX            1024   /* the largest block of fd_csc_solver_set_block_ilu */
@@ -782,6 +805,8 @@ int fd_csc_solver_block_inverses(fd_csc_solver *solver, const void **inv_dev, in
 int fd_csc_solver_set_block_ilu(fd_csc_solver *solver, int block_size);
 int fd_csc_solver_ilu_levels(fd_csc_solver *solver, const void **lev_fwd_dev, const void **lev_bwd_dev, int *max_fwd, int *max_bwd);
 int fd_csc_solver_ilu_factors(fd_csc_solver *solver, const void **lu_dev, const void **u_dev, int64_t *nblocks, int *block_size);
+int fd_csc_solver_set_method(fd_csc_solver *solver, int method, int restart);
+int fd_csc_solver_gmres_basis(fd_csc_solver *solver, const void **V_dev, const void **H_dev, int *restart, int *last_cycle_len);
 
 /* ---- the LEAST-SQUARES consumer: J v, J^T v and the damped Gauss-Newton step for a RECTANGULAR J (M x N) in SparseMatrixCSC storage ----
  * The pattern is that of a CSC plan that holds every column: colptr (N + 1) and rowval (nnz), Int32 or Int64, base 0 or 1, on the host or
@@ -1082,6 +1107,8 @@ int fd32_csc_solver_block_inverses(fd32_csc_solver *solver, const void **inv_dev
 int fd32_csc_solver_set_block_ilu(fd32_csc_solver *solver, int block_size);
 int fd32_csc_solver_ilu_levels(fd32_csc_solver *solver, const void **lev_fwd_dev, const void **lev_bwd_dev, int *max_fwd, int *max_bwd);
 int fd32_csc_solver_ilu_factors(fd32_csc_solver *solver, const void **lu_dev, const void **u_dev, int64_t *nblocks, int *block_size);
+int fd32_csc_solver_set_method(fd32_csc_solver *solver, int method, int restart);
+int fd32_csc_solver_gmres_basis(fd32_csc_solver *solver, const void **V_dev, const void **H_dev, int *restart, int *last_cycle_len);
 typedef struct fd32_csc_lsq fd32_csc_lsq;
 int fd32_csc_lsq_create(fd_ctx *ctx, int64_t M, int64_t N, const void *colptr, const void *rowval, int idx_bytes, int idx_base, int idx_kind,
                       fd32_csc_lsq **out);

@@ -925,8 +925,19 @@ class TridiagSolver:
         solution the pivot-free elimination cannot vouch for; True = the result anyway (the status flag is raised either way)."""
         _l.check(self.Lt.fd_tridiag_solver_set_policy(self.handle, 1 if trust_non_dominant else 0))
 
+    def set_pivoting(self, on):
+        """fd_tridiag_solver_set_pivoting: True = the following solves go through the recursive partitioned solve with partial pivoting
+        inside every partition of 8 rows -- for the systems the default elimination refuses (I - gamma*J of a centrally differenced
+        advection term, indefinite rows, alpha = 0; what LinearAlgebra's ``Tridiagonal \\`` solves).  False (default) = the pivot-free
+        elimination, the fast path.  Takes effect from the next solve and may be toggled.  One GPU, the whole matrix: with pivoting on,
+        ``solve`` with ``comm`` or a row window, ``interface`` and ``finish`` raise (FD_ERR_UNSUPPORTED).  ``status()`` then still
+        reports bit 0 without refusing; bit 2 (value 4) = a zero or non-finite pivot was met and y is all NaN."""
+        _l.check(self.Lt.fd_tridiag_solver_set_pivoting(self.handle, 1 if on else 0))
+
     def status(self):
-        """fd_tridiag_solver_status: bit 0 = the last solve met a row that is not diagonally dominant (no pivoting: y is NaN unless trusted)."""
+        """fd_tridiag_solver_status: bit 0 = the last solve met a row that is not diagonally dominant (no pivoting: y is NaN unless trusted;
+        with ``set_pivoting(True)``: reported only); bit 1 = a peer rank refused; bit 2 (value 4) = the pivoted solve met a zero or
+        non-finite pivot (y is NaN whatever the policy)."""
         v = C.c_int()
         _l.check(self.Lt.fd_tridiag_solver_status(self.handle, C.byref(v)))
         return v.value

@@ -35,6 +35,7 @@
 #define fd_tridiag_solver_destroy fd32_tridiag_solver_destroy
 #define fd_tridiag_solver_status fd32_tridiag_solver_status
 #define fd_tridiag_solver_set_policy fd32_tridiag_solver_set_policy
+#define fd_tridiag_solver_set_pivoting fd32_tridiag_solver_set_pivoting
 #define fd_tridiag_solve_async fd32_tridiag_solve_async
 #define fd_tridiag_solve_interface fd32_tridiag_solve_interface
 #define fd_tridiag_solve_finish fd32_tridiag_solve_finish
@@ -1024,6 +1025,289 @@ __global__ void k_tri_interface(const double *__restrict__ packets, int W, int r
     adj[1] = rank + 1 < W ? Cr * work[(2 * rank + 2) * 6 + 5] : 0.0;      // C_r * p_{r+1}
 }
 
+// ---- Pivoted solve (fd_tridiag_solver_set_pivoting; DESIGN §4.4 "Pivoted solve") ---------------------------------------------
+// For the systems the elimination above refuses: I - gamma J of a centrally differenced advection term, indefinite rows, alpha = 0.
+// A recursive partitioned solve with partial pivoting inside every partition (the scheme of Klein and Strzodka's RPTS).  Every
+// order below is fixed -- no fused multiply-add (-ffp-contract=off), IEEE division -- and tests/tri_pivot_model.py restates it in
+// numpy: y and the status word are bit-identical to that model.
+//   step     two rows with the same leading interior unknown x_j: the accumulated row (f, p, q, 0, s) on (x_first, x_j, x_j+1) and
+//            the matrix row (0, a, b, c, d) on (x_j, x_j+1, x_j+2).  Pivot = the accumulated row if |p| >= |a|, else the matrix row;
+//            l = other.lead / pivot.lead; new accumulated row = other - l * pivot on (x_first, x_j+1, x_j+2).  Branch-free: selects.
+//   chunk    8 consecutive rows, one thread.  Down from row 1 with rows 2 .. 7 -> E_B on (x_0, x_7, x_8); up from row 6 with rows
+//            5 .. 0, a and c exchanged -> E_A on (x_-1, x_0, x_7).  The coarse level holds (x_0, x_7) of every chunk with rows E_A,
+//            E_B: two rows per chunk, a quarter of the level below.  The last chunk of a level has its true length m (no identity
+//            padding: two interior unknowns would meet one row on tridiag(1, 0, 1)); m = 2, 1: its rows are its coarse rows.
+//   top      a level of <= kPivTop rows: one workgroup, the same reduction in LDS until <= 8 rows remain, which one thread solves
+//            by the same step (the accumulated row starts as row 0 with f = 0: dgtsv's elimination), then the levels back through LDS.
+//   substitution  x_0, x_7 and the next chunk's x_0 come from the coarse level; the downward sweep is repeated with the 6 pivot
+//            rows kept in registers; x_j = (rhs - f x_0 - n1 x_j+1 - n2 x_j+2) / lead for j = 6 .. 1.
+// One level per launch; coarse levels are four arrays (a, b, c, d) and a solution array.  A pivot lead that is 0 or not finite
+// raises status bit 2 (value 4) and y is NaN.  LIMIT: the two sweeps of a chunk share rows, so for matrices with exact structural
+// zeros E_A and E_B can coincide and the coarse system is singular although the matrix is not (N = 11 with b_9 = 0): bit 2, not a
+// wrong answer.
+constexpr int kPivTop = kTriTileRows;                 // 2048 rows: 256 chunks, one per thread
+constexpr int kPivLds = 512 + 128 + 32 + 8;           // the top's coarse levels: <= 512, 128, 32, 8 rows
+constexpr int kPivBad = 4;
+__host__ __device__ constexpr int tripiv_off(int lv) { return lv <= 1 ? 0 : lv == 2 ? 512 : lv == 3 ? 640 : 672; }
+__host__ __device__ inline int64_t tripiv_next_rows(int64_t n)
+{
+    const int64_t nc = (n + kChunk - 1) / kChunk, m = n - kChunk * (nc - 1);
+    return 2 * (nc - 1) + (m < 2 ? m : 2);
+}
+struct PivAcc { double f, p, q, s; };
+struct PivRow { double f, lead, n1, n2, rhs; };
+__device__ __forceinline__ int tripiv_bad(double lead) { return !(__builtin_isfinite(lead) && lead != 0.0); }
+__device__ __forceinline__ PivAcc tripiv_step(const PivAcc &A, double a, double b, double c, double d, PivRow &P, int &bad)
+{
+    const bool swap = !(fabs(A.p) >= fabs(a));            // (a tie keeps the accumulated row)
+    P.f = swap ? 0.0 : A.f; P.lead = swap ? a : A.p; P.n1 = swap ? b : A.q; P.n2 = swap ? c : 0.0; P.rhs = swap ? d : A.s;
+    const double of = swap ? A.f : 0.0, ol = swap ? A.p : a, on1 = swap ? A.q : b, on2 = swap ? 0.0 : c, orh = swap ? A.s : d;
+    const double l = ol / P.lead;
+    bad |= tripiv_bad(P.lead);
+    PivAcc N;
+    N.f = of - l * P.f; N.p = on1 - l * P.n1; N.q = on2 - l * P.n2; N.s = orh - l * P.rhs;      // (l * 0 is formed: the signs of zeros)
+    return N;
+}
+// FULL: all 8 rows, no step conditional; otherwise the level's last chunk, m >= 3 rows (selects over the unrolled rows, never a
+// runtime index: the rows live in registers)
+template <bool FULL>
+__device__ __forceinline__ PivAcc tripiv_down(const SrcRegs<1> &R, int m, PivRow (&P)[kChunk - 2], int &bad)
+{
+    PivAcc E{R.a[1], R.b[1], R.c[1], R.d[0][1]};
+#pragma unroll
+    for (int j = 2; j < kChunk; ++j)
+        if (FULL || j < m) E = tripiv_step(E, R.a[j], R.b[j], R.c[j], R.d[0][j], P[j - 2], bad);      // P[j - 2]: the pivot row of x_j-1
+    return E;
+}
+template <bool FULL> __device__ __forceinline__ PivAcc tripiv_up(const SrcRegs<1> &R, int m, int &bad)
+{
+    PivAcc E{R.c[kChunk - 2], R.b[kChunk - 2], R.a[kChunk - 2], R.d[0][kChunk - 2]};
+    PivRow unused;
+#pragma unroll
+    for (int j = kChunk - 3; j >= 0; --j) {
+        if (!FULL && j == m - 2) E = PivAcc{R.c[j], R.b[j], R.a[j], R.d[0][j]};
+        else if (FULL || j < m - 2) E = tripiv_step(E, R.c[j], R.b[j], R.a[j], R.d[0][j], unused, bad);
+    }
+    return E;
+}
+struct PivCoarse { double a[2], b[2], c[2], d[2]; };
+template <bool FULL> __device__ __forceinline__ void tripiv_coarse(const SrcRegs<1> &R, int m, PivCoarse &C, int &bad)
+{
+    if (FULL || m >= 3) {
+        PivRow unused[kChunk - 2];
+        const PivAcc B = tripiv_down<FULL>(R, m, unused, bad);
+        const PivAcc A = tripiv_up<FULL>(R, m, bad);
+        C.a[0] = A.q; C.b[0] = A.p; C.c[0] = A.f; C.d[0] = A.s;      // E_A on (x_-1, x_0, x_last)
+        C.a[1] = B.f; C.b[1] = B.p; C.c[1] = B.q; C.d[1] = B.s;      // E_B on (x_0, x_last, x_next)
+    } else {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) { C.a[i] = R.a[i]; C.b[i] = R.b[i]; C.c[i] = R.c[i]; C.d[i] = R.d[0][i]; }
+    }
+}
+// chunk k of a level: its coarse rows 2k, 2k + 1 into the four arrays of the level above
+__device__ __forceinline__ void tripiv_reduce_chunk(const SrcRegs<1> &R, int64_t n, int64_t nc, int64_t k, double *ca, double *cb,
+                                                   double *cc, double *cd, int &bad)
+{
+    PivCoarse C;
+    int cnt = 2;
+    if (k + 1 < nc) tripiv_coarse<true>(R, kChunk, C, bad);
+    else {
+        const int m = (int)(n - k * kChunk);
+        tripiv_coarse<false>(R, m, C, bad);
+        cnt = m < 2 ? m : 2;
+    }
+    ca[2 * k] = C.a[0]; cb[2 * k] = C.b[0]; cc[2 * k] = C.c[0]; cd[2 * k] = C.d[0];
+    if (cnt > 1) { ca[2 * k + 1] = C.a[1]; cb[2 * k + 1] = C.b[1]; cc[2 * k + 1] = C.c[1]; cd[2 * k + 1] = C.d[1]; }
+}
+// chunk k's unknowns from the coarse solution X (nX values): x_0 = X[2k], x_last = X[2k + 1], x_next = X[2k + 2] (0 past the end)
+template <typename Out>
+__device__ __forceinline__ void tripiv_subst_chunk(const SrcRegs<1> &R, int64_t n, int64_t nc, int64_t k, double x0, double xl, double xn,
+                                                  const Out &y)
+{
+    const int64_t s = k * kChunk;
+    int bad = 0;
+    PivRow P[kChunk - 2];
+    double x[kChunk + 1];
+    if (k + 1 < nc) {
+        (void)tripiv_down<true>(R, kChunk, P, bad);
+        x[0] = x0; x[kChunk - 1] = xl; x[kChunk] = xn;
+#pragma unroll
+        for (int j = kChunk - 2; j >= 1; --j) x[j] = (P[j - 1].rhs - P[j - 1].f * x0 - P[j - 1].n1 * x[j + 1] - P[j - 1].n2 * x[j + 2]) / P[j - 1].lead;
+#pragma unroll
+        for (int j = 0; j < kChunk; ++j) y.put(s + j, x[j]);
+    } else {
+        const int m = (int)(n - s);
+        if (m >= 3) (void)tripiv_down<false>(R, m, P, bad);
+#pragma unroll
+        for (int j = 1; j <= kChunk; ++j) x[j] = (j == m - 1) ? xl : 0.0;      // (x_m = 0: past the level's end)
+        x[0] = x0;
+#pragma unroll
+        for (int j = kChunk - 2; j >= 1; --j)
+            if (j <= m - 2) x[j] = (P[j - 1].rhs - P[j - 1].f * x0 - P[j - 1].n1 * x[j + 1] - P[j - 1].n2 * x[j + 2]) / P[j - 1].lead;
+#pragma unroll
+        for (int j = 0; j < kChunk; ++j)
+            if (j < m) y.put(s + j, x[j]);
+    }
+}
+// a level of n <= 8 rows, one thread: dgtsv's elimination by the same step, then the back-substitution
+__device__ __forceinline__ void tripiv_bottom(const SrcRegs<1> &R, int n, double (&x)[kChunk + 2], int &bad)
+{
+    PivAcc E{0.0, R.b[0], R.c[0], R.d[0][0]};
+    PivRow P[kChunk];
+#pragma unroll
+    for (int j = 1; j < kChunk; ++j)
+        if (j < n) E = tripiv_step(E, R.a[j], R.b[j], R.c[j], R.d[0][j], P[j - 1], bad);
+    bad |= tripiv_bad(E.p);
+#pragma unroll
+    for (int j = 0; j < kChunk; ++j)
+        if (j == n - 1) P[j] = PivRow{E.f, E.p, E.q, 0.0, E.s};      // the pivot row of the last unknown
+    x[kChunk] = 0.0; x[kChunk + 1] = 0.0;
+#pragma unroll
+    for (int j = kChunk - 1; j >= 0; --j)
+        x[j] = j < n ? (P[j].rhs - P[j].f * 0.0 - P[j].n1 * x[j + 1] - P[j].n2 * x[j + 2]) / P[j].lead : 0.0;
+}
+// a coarse level in memory: four arrays (lane-consecutive loads through tri_fetch_rows)
+struct SrcSoA {
+    const double *a, *b, *c, *d;
+    static constexpr bool kUnitRhs = false;
+    __device__ __forceinline__ double raw(int which, int64_t i) const { return (which == 0 ? a : which == 1 ? b : which == 2 ? c : d)[i]; }
+    __device__ __forceinline__ double fix(int, int64_t, double v) const { return v; }
+};
+struct PivPlainOut {
+    double *x;
+    __device__ __forceinline__ void put(int64_t i, double v) const { x[i] = v; }
+};
+template <typename Src, bool CSC>
+__global__ void __launch_bounds__(kBlock) k_tripiv_reduce(Src src, int64_t n, int64_t nc, double *__restrict__ ca, double *__restrict__ cb,
+                                                          double *__restrict__ cc, double *__restrict__ cd, int *__restrict__ status)
+{
+    __shared__ double lds[CSC ? kTriRawSlots : kTriPitch];
+    const int64_t row0 = (int64_t)blockIdx.x * kTriTileRows;
+    TriTileLoads<Src, CSC> G;
+    G.issue(src, n, row0);
+    SrcRegs<1> R;
+    G.land(src, n, row0, lds, R);
+    if constexpr (Src::kUnitRhs) tri_guard_rows<1>(R, n, row0, src.nd_flag);      // (level 0: bit 0 is still reported)
+    const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (k >= nc) return;
+    int bad = 0;
+    tripiv_reduce_chunk(R, n, nc, k, ca, cb, cc, cd, bad);
+    if (bad) atomicOr(status, kPivBad);
+}
+// Level 0 writes y through LDS with dense stores (as k_tri_backsub), all NaN if a pivot was bad: every pivot has been seen by the
+// reductions and the top before this kernel starts.
+template <typename Src, bool CSC, typename OutT>
+__global__ void __launch_bounds__(kBlock) k_tripiv_subst(Src src, int64_t n, int64_t nc, const double *__restrict__ X, int64_t nX,
+                                                         OutT *__restrict__ y, const int *__restrict__ status)
+{
+    __shared__ double lds[CSC ? kTriRawSlots : kTriPitch];
+    const int64_t tile = Src::kUnitRhs ? (int64_t)gridDim.x - 1 - blockIdx.x : (int64_t)blockIdx.x;      // (level 0 from the tail: see k_tri_backsub_csc)
+    const int64_t row0 = tile * kTriTileRows, k = tile * kBlock + threadIdx.x;
+    // (needed after the sweep: in flight with the rows; clamped, selected below)
+    const int64_t i0 = 2 * k < nX ? 2 * k : nX - 1, i1 = 2 * k + 1 < nX ? 2 * k + 1 : nX - 1, i2 = 2 * k + 2 < nX ? 2 * k + 2 : nX - 1;
+    const double x0 = X[i0], xl = X[i1], xnr = X[i2];
+    const double xn = 2 * k + 2 < nX ? xnr : 0.0;
+    bool poison = false;
+    if constexpr (Src::kUnitRhs) poison = (*status & kPivBad) != 0;
+    TriTileLoads<Src, CSC> G;
+    G.issue(src, n, row0);
+    SrcRegs<1> R;
+    G.land(src, n, row0, lds, R);
+    __syncthreads();                                      // every thread has copied the last array out of LDS
+    if (k < nc) tripiv_subst_chunk(R, n, nc, k, x0, xl, xn, TriLdsOut{lds, row0});
+    __syncthreads();
+    const int64_t rows = (n - row0 < kTriTileRows) ? n - row0 : kTriTileRows;
+#pragma unroll
+    for (int j = 0; j < kChunk; ++j) {
+        const int r = j * kBlock + (int)threadIdx.x;
+        if (r < rows) y[row0 + r] = poison ? (OutT)__builtin_nan("") : (OutT)lds[r + (r >> 3)];
+    }
+}
+// rows 8t .. 8t + 7 of a coarse level of the top (LDS, level lv at tripiv_off(lv))
+__device__ __forceinline__ void tripiv_lds_rows(const double *LA, const double *LB, const double *LC, const double *LD, int off, int t, int n,
+                                               SrcRegs<1> &Q)
+{
+#pragma unroll
+    for (int i = 0; i < kChunk; ++i) {
+        const int r = t * kChunk + i, rc = off + (r < n ? r : n - 1);
+        Q.a[i] = LA[rc]; Q.b[i] = LB[rc]; Q.c[i] = LC[rc]; Q.d[0][i] = LD[rc];
+    }
+}
+// The top: a level of n <= kPivTop rows finished inside one workgroup.  Level 0 of the top stays in registers (a chunk per thread);
+// its coarse levels (<= 512, 128, 32, 8 rows) and their solutions live in LDS.
+template <typename Src, bool CSC, typename OutT>
+__global__ void __launch_bounds__(kBlock) k_tripiv_top(Src src, int n, OutT *__restrict__ y, int *__restrict__ status)
+{
+    // (once the rows are in registers only the first kTriPitch doubles of the fetch buffer are used again, as the output's staging:
+    //  the coarse levels sit behind them, inside the CSC fetch buffer where there is one)
+    constexpr int kFetch = CSC ? kTriRawSlots : kTriPitch, kNeed = kTriPitch + 5 * kPivLds;
+    __shared__ double lds[kFetch > kNeed ? kFetch : kNeed];
+    double *LA = lds + kTriPitch, *LB = LA + kPivLds, *LC = LB + kPivLds, *LD = LC + kPivLds, *LX = LD + kPivLds;
+    __shared__ int sbad;
+    const int t = threadIdx.x;
+    if (t == 0) sbad = 0;
+    TriTileLoads<Src, CSC> G;
+    G.issue(src, n, 0);
+    SrcRegs<1> R;
+    G.land(src, n, 0, lds, R);
+    if constexpr (Src::kUnitRhs) tri_guard_rows<1>(R, n, 0, src.nd_flag);
+    __syncthreads();                                      // every thread has copied the last array out of the fetch buffer
+    constexpr int kLv = 5;                                // levels 0 .. 4 of the top
+    int nn[kLv];
+    nn[0] = n;
+#pragma unroll
+    for (int lv = 1; lv < kLv; ++lv) nn[lv] = nn[lv - 1] > kChunk ? (int)tripiv_next_rows(nn[lv - 1]) : 0;
+    int bad = 0;
+    const TriLdsOut out0{lds, 0};
+#pragma unroll
+    for (int lv = 0; lv < kLv; ++lv) {
+        if (nn[lv] > kChunk) {                            // reduce level lv into level lv + 1 (lv < 4: a level of the top has <= 2048 / 4^lv rows)
+            const int nc = (nn[lv] + kChunk - 1) / kChunk;
+            if (t < nc) {
+                SrcRegs<1> Q;
+                if (lv == 0) Q = R; else tripiv_lds_rows(LA, LB, LC, LD, tripiv_off(lv), t, nn[lv], Q);
+                const int o = tripiv_off(lv + 1);
+                tripiv_reduce_chunk(Q, nn[lv], nc, t, LA + o, LB + o, LC + o, LD + o, bad);
+            }
+            __syncthreads();
+        } else if (nn[lv] > 0) {                          // the level one thread solves
+            if (t == 0) {
+                SrcRegs<1> Q;
+                if (lv == 0) Q = R; else tripiv_lds_rows(LA, LB, LC, LD, tripiv_off(lv), 0, nn[lv], Q);
+                double x[kChunk + 2];
+                tripiv_bottom(Q, nn[lv], x, bad);
+#pragma unroll
+                for (int i = 0; i < kChunk; ++i)
+                    if (i < nn[lv]) { if (lv == 0) out0.put(i, x[i]); else LX[tripiv_off(lv) + i] = x[i]; }
+            }
+        }
+    }
+    if (bad) sbad = 1;
+    __syncthreads();
+#pragma unroll
+    for (int lv = kLv - 2; lv >= 0; --lv) {
+        if (nn[lv] > kChunk) {                            // level lv from the solved level lv + 1
+            const int nc = (nn[lv] + kChunk - 1) / kChunk, nX = nn[lv + 1];
+            if (t < nc) {
+                SrcRegs<1> Q;
+                if (lv == 0) Q = R; else tripiv_lds_rows(LA, LB, LC, LD, tripiv_off(lv), t, nn[lv], Q);
+                const double *X = LX + tripiv_off(lv + 1);
+                const double x0 = X[2 * t], xl = X[2 * t + 1 < nX ? 2 * t + 1 : nX - 1], xn = 2 * t + 2 < nX ? X[2 * t + 2] : 0.0;
+                if (lv == 0) tripiv_subst_chunk(Q, nn[lv], nc, t, x0, xl, xn, out0);
+                else tripiv_subst_chunk(Q, nn[lv], nc, t, x0, xl, xn, PivPlainOut{LX + tripiv_off(lv)});
+            }
+            __syncthreads();
+        }
+    }
+    const bool poison = Src::kUnitRhs && sbad != 0;
+    if (t == 0 && sbad != 0) atomicOr(status, kPivBad);
+#pragma unroll
+    for (int j = 0; j < kChunk; ++j) {
+        const int r = j * kBlock + t;
+        if (r < n) y[r] = poison ? (OutT)__builtin_nan("") : (OutT)lds[r + (r >> 3)];
+    }
+}
+
 }  // namespace fdjac
 
 struct fd_tridiag_solver {
@@ -1039,6 +1323,11 @@ struct fd_tridiag_solver {
     double *adj = nullptr, *cpl = nullptr, *work = nullptr;
     int *status = nullptr;                            // device word: bit 0 = the last solve met a row that is not diagonally dominant
     int refuse = 1;                                   // fd_tridiag_solver_set_policy: such a solve writes NaN (default) / its solution anyway
+    // the pivoted solve (fd_tridiag_solver_set_pivoting): its own level schedule; buffers allocated at the first pivoted solve
+    int pivoting = 0;
+    int piv_nlev = 0;
+    int64_t piv_n[fdjac::kMaxLevels] = {0};
+    double *piv_buf[fdjac::kMaxLevels] = {nullptr};   // level l >= 1: a, b, c, d and the solution, piv_n[l] doubles each
 };
 
 using namespace fdjac;
@@ -1225,6 +1514,13 @@ int fd_tridiag_solver_set_policy(fd_tridiag_solver *s, int trust_non_dominant)
     return FD_OK;
 }
 
+int fd_tridiag_solver_set_pivoting(fd_tridiag_solver *s, int on)
+{
+    FD_REQUIRE(s != nullptr, FD_ERR_ARG, "solver is NULL");
+    s->pivoting = on ? 1 : 0;
+    return FD_OK;
+}
+
 int fd_tridiag_solver_destroy(fd_tridiag_solver *s)
 {
     if (!s) return FD_OK;
@@ -1234,10 +1530,59 @@ int fd_tridiag_solver_destroy(fd_tridiag_solver *s)
         if (s->lev_sum[k]) (void)hipFree(s->lev_sum[k]);
         if (s->lev_sol[k]) (void)hipFree(s->lev_sol[k]);
         if (s->lev_halo[k]) (void)hipFree(s->lev_halo[k]);
+        if (s->piv_buf[k]) (void)hipFree(s->piv_buf[k]);
     }
     for (void *p : {(void *)s->packets, (void *)s->adj, (void *)s->cpl, (void *)s->work, (void *)s->status})
         if (p) (void)hipFree(p);
     delete s;
+    return FD_OK;
+}
+
+// The pivoted solve of the whole matrix: one level per launch down to the top (<= kPivTop rows, one workgroup), then back.
+static int tri_pivot_solve(fd_tridiag_solver *s, double alpha, double beta, const void *const *J, const void *rhs, void *y)
+{
+    if (s->piv_nlev == 0) {                               // the first pivoted solve: the schedule and the level buffers
+        int64_t n = s->n;
+        int l = 0;
+        s->piv_n[0] = n;
+        while (n > kPivTop) {
+            n = tripiv_next_rows(n);
+            ++l;
+            FD_REQUIRE(l < kMaxLevels, FD_ERR_UNSUPPORTED, "too many levels");
+            s->piv_n[l] = n;
+        }
+        for (int k = 1; k <= l; ++k)
+            if (!s->piv_buf[k] && hipMalloc((void **)&s->piv_buf[k], sizeof(double) * 5 * (size_t)s->piv_n[k]) != hipSuccess) {
+                set_error("hipMalloc failed in the pivoted tridiagonal solve");
+                return FD_ERR_NOMEM;
+            }
+        s->piv_nlev = l + 1;
+    }
+    const SrcUser u = make_src(s, alpha, beta, J, rhs, nullptr);
+    hipStream_t st = s->ctx->stream;
+    const bool csc = u.layout == FD_TRI_CSC;
+    const int top = s->piv_nlev - 1;
+    auto lev = [&](int l) { const int64_t n = s->piv_n[l]; const double *p = s->piv_buf[l]; return SrcSoA{p, p + n, p + 2 * n, p + 3 * n}; };
+    for (int l = 0; l < top; ++l) {
+        const int64_t n = s->piv_n[l], nc = (n + kChunk - 1) / kChunk, n1 = s->piv_n[l + 1];
+        const unsigned g = (unsigned)((nc + kBlock - 1) / kBlock);
+        double *o = s->piv_buf[l + 1];
+        if (l == 0 && csc) hipLaunchKernelGGL((k_tripiv_reduce<SrcUser, true>), dim3(g), dim3(kBlock), 0, st, u, n, nc, o, o + n1, o + 2 * n1, o + 3 * n1, s->status);
+        else if (l == 0) hipLaunchKernelGGL((k_tripiv_reduce<SrcUser, false>), dim3(g), dim3(kBlock), 0, st, u, n, nc, o, o + n1, o + 2 * n1, o + 3 * n1, s->status);
+        else hipLaunchKernelGGL((k_tripiv_reduce<SrcSoA, false>), dim3(g), dim3(kBlock), 0, st, lev(l), n, nc, o, o + n1, o + 2 * n1, o + 3 * n1, s->status);
+    }
+    if (top == 0 && csc) hipLaunchKernelGGL((k_tripiv_top<SrcUser, true, real_t>), dim3(1), dim3(kBlock), 0, st, u, (int)s->piv_n[0], (real_t *)y, s->status);
+    else if (top == 0) hipLaunchKernelGGL((k_tripiv_top<SrcUser, false, real_t>), dim3(1), dim3(kBlock), 0, st, u, (int)s->piv_n[0], (real_t *)y, s->status);
+    else hipLaunchKernelGGL((k_tripiv_top<SrcSoA, false, double>), dim3(1), dim3(kBlock), 0, st, lev(top), (int)s->piv_n[top], s->piv_buf[top] + 4 * s->piv_n[top], s->status);
+    for (int l = top - 1; l >= 0; --l) {
+        const int64_t n = s->piv_n[l], nc = (n + kChunk - 1) / kChunk, n1 = s->piv_n[l + 1];
+        const unsigned g = (unsigned)((nc + kBlock - 1) / kBlock);
+        const double *X = s->piv_buf[l + 1] + 4 * n1;
+        if (l == 0 && csc) hipLaunchKernelGGL((k_tripiv_subst<SrcUser, true, real_t>), dim3(g), dim3(kBlock), 0, st, u, n, nc, X, n1, (real_t *)y, (const int *)s->status);
+        else if (l == 0) hipLaunchKernelGGL((k_tripiv_subst<SrcUser, false, real_t>), dim3(g), dim3(kBlock), 0, st, u, n, nc, X, n1, (real_t *)y, (const int *)s->status);
+        else hipLaunchKernelGGL((k_tripiv_subst<SrcSoA, false, double>), dim3(g), dim3(kBlock), 0, st, lev(l), n, nc, X, n1, s->piv_buf[l] + 4 * n, (const int *)s->status);
+    }
+    FD_HIP_CHECK(hipGetLastError());
     return FD_OK;
 }
 
@@ -1261,6 +1606,7 @@ int fd_tridiag_solve_interface(fd_tridiag_solver *s, double alpha, double beta, 
                                void *packet_dev)
 {
     FD_REQUIRE(s && J && rhs && packet_dev, FD_ERR_ARG, "NULL argument");
+    FD_REQUIRE(!s->pivoting, FD_ERR_UNSUPPORTED, "the pivoted solve is not sharded: fd_tridiag_solver_set_pivoting(solver, 0) first");
     FD_REQUIRE(s->layout == FD_TRI_CSC ? J[0] != nullptr : J[1] != nullptr, FD_ERR_ARG, "J's values are NULL");   // (dl / du may be empty)
     FD_HIP_CHECK(hipSetDevice(s->ctx->device));
     (void)hipMemsetAsync(s->status, 0, sizeof(int), s->ctx->stream);      // (the dominance guard of this solve)
@@ -1282,6 +1628,7 @@ int fd_tridiag_solve_finish(fd_tridiag_solver *s, double alpha, double beta, con
                             const void *packets_dev, int rank, int nranks, void *y)
 {
     FD_REQUIRE(s && J && rhs && packets_dev && y, FD_ERR_ARG, "NULL argument");
+    FD_REQUIRE(!s->pivoting, FD_ERR_UNSUPPORTED, "the pivoted solve is not sharded: fd_tridiag_solver_set_pivoting(solver, 0) first");
     FD_REQUIRE(s->layout == FD_TRI_CSC ? J[0] != nullptr : J[1] != nullptr, FD_ERR_ARG, "J's values are NULL");
     FD_REQUIRE(nranks >= 1 && nranks <= kMaxRanks && rank >= 0 && rank < nranks, FD_ERR_ARG, "rank %d of %d", rank, nranks);
     FD_HIP_CHECK(hipSetDevice(s->ctx->device));
@@ -1296,7 +1643,14 @@ int fd_tridiag_solve_async(fd_tridiag_solver *s, double alpha, double beta, cons
 {
     FD_REQUIRE(s && J && rhs && y, FD_ERR_ARG, "NULL argument");
     FD_REQUIRE(s->layout == FD_TRI_CSC ? J[0] != nullptr : J[1] != nullptr, FD_ERR_ARG, "J's values are NULL");
+    FD_REQUIRE(!s->pivoting || (!comm && s->n == s->N), FD_ERR_UNSUPPORTED,
+               "the pivoted solve takes the whole matrix on one GPU (rows [%lld,%lld) of %lld%s)", (long long)s->g0,
+               (long long)(s->g0 + s->n), (long long)s->N, comm ? ", a communicator" : "");
     FD_HIP_CHECK(hipSetDevice(s->ctx->device));
+    if (s->pivoting) {
+        (void)hipMemsetAsync(s->status, 0, sizeof(int), s->ctx->stream);
+        return tri_pivot_solve(s, alpha, beta, J, rhs, y);
+    }
     if (!comm) {
         FD_REQUIRE(s->n == s->N, FD_ERR_ARG, "a solver for rows [%lld,%lld) of %lld needs a communicator", (long long)s->g0,
                    (long long)(s->g0 + s->n), (long long)s->N);

@@ -676,9 +676,22 @@ int fd_tridiag_solver_destroy(fd_tridiag_solver *solver);
    the refusal off for callers who know their matrix is fine without dominance (symmetric positive definite, M-matrices): the flag is
    still raised, y is the elimination's result.  In a MULTI-RANK solve a rank that refuses does so for every rank: its interface packet
    carries NaN, every rank's y is poisoned and every rank's status has bit 1 set ("a peer refused"; bit 0 stays with the rank that owns the
-   offending rows).  fd_tridiag_solver_status synchronises the context's stream. */
+   offending rows).  Bit 2 (value 4) belongs to the pivoted solve below.  fd_tridiag_solver_status synchronises the context's stream. */
 int fd_tridiag_solver_set_policy(fd_tridiag_solver *solver, int trust_non_dominant);
 int fd_tridiag_solver_status(fd_tridiag_solver *solver, int *flags_out);
+/* The PIVOTED solve, opt-in per solver (default 0; takes effect from the next solve; may be toggled): on = 1 sends the following
+   fd_tridiag_solve_async calls through a recursive partitioned solve with partial pivoting inside every partition of 8 rows (the
+   scheme of Klein and Strzodka's RPTS; Float64 arithmetic for both element types) instead of the pivot-free elimination -- for the
+   systems that one refuses: I - gamma*J of a centrally differenced advection term (zero diagonal, +-c/2h off it) once
+   gamma*c/h > 1, indefinite rows, alpha = 0.  Bit 0 of the status word is still reported (the rows are checked anyway) but never
+   causes a refusal.  Bit 2 (value 4): a pivot was zero or not finite -- y is then all NaN, whatever fd_tridiag_solver_set_policy
+   says.  A limit by construction: the two elimination sweeps of a partition share rows, so for matrices with exact structural zeros
+   the reduced system can be singular although the matrix is not (smallest example: N = 11 with a zero diagonal entry in row 9); such
+   a solve ends in bit 2, never in a wrong answer.  One GPU, the whole matrix: with pivoting on, fd_tridiag_solve_async with a
+   communicator or a row window, fd_tridiag_solve_interface and fd_tridiag_solve_finish return FD_ERR_UNSUPPORTED before any launch.
+   Slower than the default path (one level per launch, about 13 N doubles of traffic); the level buffers are allocated at the
+   first pivoted solve. */
+int fd_tridiag_solver_set_pivoting(fd_tridiag_solver *solver, int on);
 /* comm == NULL: the solver's rows are the whole system.  J: 3 (diagonals) or 1 (CSC) device pointers; b, y device. */
 int fd_tridiag_solve_async(fd_tridiag_solver *solver, double alpha, double beta, const void *const *J, const void *b,
                            void *y, fd_comm *comm);
@@ -1127,6 +1140,7 @@ int fd32_tridiag_solver_create(fd_ctx *ctx, int64_t N, int64_t row_begin, int64_
 int fd32_tridiag_solver_destroy(fd32_tridiag_solver *solver);
 int fd32_tridiag_solver_set_policy(fd32_tridiag_solver *solver, int trust_non_dominant);
 int fd32_tridiag_solver_status(fd32_tridiag_solver *solver, int *flags_out);
+int fd32_tridiag_solver_set_pivoting(fd32_tridiag_solver *solver, int on);
 int fd32_tridiag_solve_async(fd32_tridiag_solver *solver, double alpha, double beta, const void *const *J, const void *b,
                              void *y, fd_comm *comm);
 int fd32_tridiag_solve_interface(fd32_tridiag_solver *solver, double alpha, double beta, const void *const *J,

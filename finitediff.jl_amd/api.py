@@ -841,6 +841,110 @@ class CscTrustRegion(_CscConsumer):
                 "pred": pr.value}
 
 
+class JfnkSolver:
+    """fd_jfnk_solver: the matrix-free consumer.  ``solve`` enqueues y = (alpha*I + beta*J(x))^-1 b by restarted GMRES(``restart``) whose
+    product is the finite-difference JVP of ``f`` at ``x`` -- J is never stored, so f needs no pattern and no colouring -- and ``apply``
+    enqueues w = alpha*z + beta*J(x) z.  Float64, square f (M = N), device arrays.  ``f`` is a ``BuiltinF``, a compiled functor (``JitF``
+    ...) or a raw ``(launcher, context)`` pair, as ``finite_difference_jvp_b`` takes them; ``set_lazy(f)`` installs f's lazy JVP launcher.
+    A solve that runs out of iterations (``status()`` flags bit 0) or breaks down (bit 1) fills y with NaN unless ``set_policy(True)``."""
+
+    def __init__(self, N, fdtype="forward", restart=30, ctx=None):
+        self.ctx = ctx or Context.default()
+        self.N, self.fdtype = int(N), _norm_fdtype(fdtype)
+        self.dtype = np.dtype(np.float64)
+        h = C.c_void_p()
+        _l.check(self.ctx.L.fd_jfnk_solver_create(self.ctx.handle, self.N, _l.FDTYPES[self.fdtype], int(restart), C.byref(h)))
+        self.handle = h
+        self._fin = weakref.finalize(self, self.ctx.L.fd_jfnk_solver_destroy, h)
+        self._lazy_keep = self._diag_keep = None
+
+    def _dev(self, a, what):
+        if a is None:
+            return None
+        p, k, _keep = _ptr(a, what, self.dtype)
+        if k != _l.DEVICE:
+            raise ValueError("the matrix-free solver takes device arrays")
+        if int(np.prod(a.shape)) != self.N:
+            raise ValueError("%s must hold N = %d elements" % (what, self.N))      # DimensionMismatch
+        return p
+
+    @staticmethod
+    def _launcher(f):
+        if isinstance(f, tuple):
+            return f[0], f[1]
+        if np.dtype(getattr(f, "dtype", np.float64)) != np.dtype(np.float64):
+            raise TypeError("the matrix-free solver is Float64 only")
+        return f.fn, f.fctx
+
+    def set_options(self, rtol=1e-10, max_iterations=500):
+        _l.check(self.ctx.L.fd_jfnk_solver_set_options(self.handle, float(rtol), int(max_iterations)))
+
+    def set_policy(self, keep_unconverged):
+        _l.check(self.ctx.L.fd_jfnk_solver_set_policy(self.handle, 1 if keep_unconverged else 0))
+
+    def set_steps(self, relstep=None, absstep=None, dir=True):
+        """The JVP's steps as ``finite_difference_jvp_b`` takes them (None: the defaults)."""
+        _l.check(self.ctx.L.fd_jfnk_solver_set_steps(self.handle, -1.0 if relstep is None else float(relstep),
+                                                     -1.0 if absstep is None else float(absstep), float(dir)))
+
+    def set_diagonal(self, d):
+        """N doubles on the device, the right preconditioner M = diag(d), read by every solve (the array is kept alive); None: none."""
+        self._diag_keep = d
+        _l.check(self.ctx.L.fd_jfnk_solver_set_diagonal(self.handle, self._dev(d, "d")))
+
+    def set_lazy(self, f=None, quotient=True):
+        """Install ``f``'s lazy JVP launcher (``f.lazy_jvp_fn``; a raw launcher is taken as it is, with ``quotient`` as its capability
+        bits) or, with None or an f that has none, clear it.  ``quotient=False``: the launcher writes values, never the quotient."""
+        if f is not None and not hasattr(f, "lazy_jvp_fn") and not isinstance(f, _l.F_LAUNCH_LAZY_JVP):
+            f = None
+        if isinstance(f, _l.F_LAUNCH_LAZY_JVP):
+            lz, caps = f, int(quotient)
+        else:
+            lz = getattr(f, "lazy_jvp_fn", None) if f is not None else None
+            caps = int(getattr(f, "lazy_jvp_caps", 0)) if (lz is not None and quotient) else 0
+        self._lazy_keep = lz            # (the ctypes function object must outlive the calls)
+        _l.check(self.ctx.L.fd_jfnk_solver_set_lazy_f(self.handle, lz if lz is not None else _l.F_LAUNCH_LAZY_JVP(), caps if lz is not None else 0))
+
+    def _call(self, entry, f, x, f_in, a, b, alpha, beta):
+        fn, fctx = self._launcher(f)
+        rc = entry(self.handle, float(alpha), float(beta), fn, fctx, self._dev(x, "x"), self._dev(f_in, "f_in"), a, b)
+        err = getattr(f, "error", None)
+        if err is not None:
+            f.error = None
+            raise err
+        _l.check(rc)
+
+    def apply(self, f, x, z, w, alpha=1.0, beta=-1.0, f_in=None):
+        """Enqueue w = alpha*z + beta*J(x) z (fd_jfnk_apply_async)."""
+        self._call(self.ctx.L.fd_jfnk_apply_async, f, x, f_in, self._dev(z, "z"), self._dev(w, "w"), alpha, beta)
+
+    def solve(self, f, x, b, y, alpha=1.0, beta=-1.0, f_in=None):
+        """Enqueue y = (alpha*I + beta*J(x))^-1 b (fd_jfnk_solve_async)."""
+        self._call(self.ctx.L.fd_jfnk_solve_async, f, x, f_in, self._dev(b, "b"), self._dev(y, "y"), alpha, beta)
+
+    def status(self):
+        """Synchronises.  {"flags": bit 0 the iterations ran out | bit 1 breakdown, "iterations", "resid": the last estimate, "bnorm"}."""
+        f, it, r, bn = C.c_int(), C.c_int64(), C.c_double(), C.c_double()
+        _l.check(self.ctx.L.fd_jfnk_solver_status(self.handle, C.byref(f), C.byref(it), C.byref(r), C.byref(bn)))
+        return {"flags": f.value, "iterations": it.value, "resid": r.value, "bnorm": bn.value}
+
+    def counts(self):
+        """(operator applications, base evaluations f(x)) enqueued since creation."""
+        a, b = C.c_int64(), C.c_int64()
+        _l.check(self.ctx.L.fd_jfnk_solver_counts(self.handle, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def basis(self):
+        """Synchronises.  Diagnostic, as ``CscSolver.gmres_basis``: V (restart + 1, N), H (restart, restart + 1) and the last cycle's length."""
+        import torch
+        pv, ph, m, k = C.c_void_p(), C.c_void_p(), C.c_int(), C.c_int()
+        _l.check(self.ctx.L.fd_jfnk_solver_basis(self.handle, C.byref(pv), C.byref(ph), C.byref(m), C.byref(k)))
+        dev = "cuda:%d" % self.ctx.device
+        V = torch.as_tensor(_DevView(pv.value, (m.value + 1) * self.N, False), device=dev).clone().reshape(m.value + 1, self.N)
+        H = torch.as_tensor(_DevView(ph.value, m.value * (m.value + 1), False), device=dev).clone().reshape(m.value, m.value + 1)
+        return V, H, k.value
+
+
 class BlockTridiagSolver:
     """fd_blocktridiag_solver: (alpha*I + beta*J) y = b on the device for a block-tridiagonal J of ``nblk`` dense ``b x b`` blocks
     (b <= 32) in ``BlockBandedMatrix`` data (block bandwidths (1, 1), uniform block sizes) -- the storage a block-banded plan fills

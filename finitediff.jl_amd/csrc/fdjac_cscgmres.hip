@@ -281,8 +281,9 @@ __global__ void k_gm_tri(CsGm G, int *words)
     if (bad) atomicOr(words + W_FLAGS, 2);
     else words[W_GM_UPD] = K;
 }
-// u = V t over the columns k_gm_tri counted; DIAG: y = y + u / d at once, otherwise u is stored for the block apply
-template <bool DIAG>
+// u = V t over the columns k_gm_tri counted; HOW 1: y = y + u / d at once; 2: y = y + u (no preconditioner: the matrix-free consumer);
+// 0: u is stored for the block apply
+template <int HOW>
 __global__ void __launch_bounds__(kBlock) k_gm_combine(int N, CsGm G, const double *__restrict__ d, double *__restrict__ out, const int *words)
 {
     const int K = words[W_GM_UPD];
@@ -311,7 +312,8 @@ __global__ void __launch_bounds__(kBlock) k_gm_combine(int N, CsGm G, const doub
     for (int k = 0; k < kGsPer; ++k) {
         const int i = e0 + k * kBlock;
         if (i >= N) continue;
-        if (DIAG) out[i] = out[i] + acc[k] / d[i];
+        if (HOW == 1) out[i] = out[i] + acc[k] / d[i];
+        else if (HOW == 2) out[i] = out[i] + acc[k];
         else out[i] = acc[k];
     }
 }

@@ -527,11 +527,10 @@ static size_t gm_doubles(size_t N, int m, size_t ntile)
     const size_t k = (size_t)m;
     return (k + 1) * N + 2 * k * (k + 1) + 2 * k + (k + 1) + k + 2 * (k + 1) + (k + 2) * ntile + 1;
 }
-static CsGm csc_gm(const fd_csc_solver *s, int m)
+static CsGm gm_view(double *p, size_t N, int m)
 {
-    const size_t N = (size_t)s->L.N, k = (size_t)m, ntile = cs_tiles(s->L.N, kCsVecTile);
+    const size_t k = (size_t)m, ntile = cs_tiles((int64_t)N, kCsVecTile);
     CsGm G;
-    double *p = s->d_gm;
     G.m = m; G.ntile = (int)ntile;
     G.V = p; p += (k + 1) * N;
     G.H = p; p += k * (k + 1);
@@ -546,6 +545,7 @@ static CsGm csc_gm(const fd_csc_solver *s, int m)
     G.klast = (int *)p;
     return G;
 }
+static CsGm csc_gm(const fd_csc_solver *s, int m) { return gm_view(s->d_gm, (size_t)s->L.N, m); }
 
 // the basis and the Hessenberg columns of the last cycle of the last GMRES solve, for the tests: owned by the solver; synchronises
 int fd_csc_solver_gmres_basis(fd_csc_solver *s, const void **V_dev, const void **H_dev, int *restart, int *last_cycle_len)
@@ -732,25 +732,25 @@ int fd_csc_matvec_async(fd_csc_solver *s, double alpha, double beta, const void 
     return FD_OK;
 }
 
-// The GMRES iterations behind the start kernels (fdjac_cscgmres.hip has the algorithm).  apply(which, x, out): out = M^-1 x of a block
-// preconditioner; which = 1 is skipped once the cycle is over, which = 0 only once the solve is.
-template <class A>
-static int csc_gmres_iterate(fd_csc_solver *s, double alpha, double beta, const real_t *nz, const real_t *b, const CsVecs &V, bool blocks, A apply)
+// The GMRES iterations behind the start kernels (fdjac_cscgmres.hip has the algorithm), shared by the sparse consumer and the
+// matrix-free one (fdjac_jfnk.hip).  Each callable enqueues on st and returns FD_OK or the code that ends the call:
+//   precond(vj, z)      the step's z = M^-1 v_j; returns where z is (vj itself without a preconditioner); guarded by `cycle over`
+//   product(mode, v, w) w = A v; mode 3: a step's product (nothing once the cycle is over), 4: the explicit residual's (once the solve is)
+//   add(u, z)           the cycle's end behind k_gm_tri: y = y + M^-1 (V t) over the columns W_GM_UPD counts
+template <class PC, class PR, class AD>
+static int csc_gmres_iterate(hipStream_t st, CscSolveState &S, int N, const CsGm &G, const real_t *b, const CsVecs &V, PC precond, PR product, AD add)
 {
-    hipStream_t st = s->ctx->stream;
-    CscSolveState &S = s->S;
-    const int N = (int)s->L.N, m = s->gm_m;
+    const int m = G.m;
     const size_t n = (size_t)N;
     const unsigned gv = cs_tiles(N, kCsVecTile);
-    const CsGm G = csc_gm(s, m);
     double *z = V.p, *w = V.v, *u = V.s, *npart = G.part + (size_t)(m + 1) * G.ntile;
     int *words = S.d_words;
+    int rc = FD_OK;
     hipLaunchKernelGGL(k_gm_start<true>, dim3(gv), dim3(kBlock), 0, st, N, (const double *)V.r, G, S.rtol, S.d_scal, (const int *)words);
-    const auto step = [&](int j) {      // 10 launches (+ 1 with long rows)
-        const double *vj = G.V + (size_t)j * n;
-        if (blocks) apply(1, vj, z);
-        else hipLaunchKernelGGL(k_gm_scale<true>, dim3(gv), dim3(kBlock), 0, st, N, vj, (const double *)V.d, z, (const int *)words);
-        csc_product<double, 3>(s, alpha, beta, nz, z, w, nullptr, true);
+    const auto step = [&](int j) {      // the sparse consumer: 10 launches (+ 1 with long rows)
+        const double *vj = G.V + (size_t)j * n, *zj = nullptr;
+        if ((rc = precond(vj, z, &zj)) != FD_OK) return;
+        if ((rc = product(3, zj, w)) != FD_OK) return;
         for (int pass = 0; pass < 2; ++pass) {
             double *h = pass ? G.h2 : G.h1;
             hipLaunchKernelGGL(k_cs_gs_dots, dim3(gv), dim3(kBlock), 0, st, N, j + 1, (const double *)w, (const double *)G.V, G.part, (const int *)words);
@@ -765,15 +765,9 @@ static int csc_gmres_iterate(fd_csc_solver *s, double alpha, double beta, const 
     };
     const auto cycle_end = [&] {
         hipLaunchKernelGGL(k_gm_tri, dim3(1), dim3(64), 0, st, G, words);
-        fd_pick<false, true>(!blocks, [&](auto DIAG) {
-            hipLaunchKernelGGL(k_gm_combine<DIAG()>, dim3(gv), dim3(kBlock), 0, st, N, G, (const double *)V.d, DIAG() ? V.y : u, (const int *)words);
-        });
-        if (blocks) {
-            apply(0, u, z);
-            hipLaunchKernelGGL(k_gm_yadd, dim3(gv), dim3(kBlock), 0, st, N, V.y, (const double *)z, (const int *)words);
-        }
+        if ((rc = add(u, z)) != FD_OK) return;
         hipLaunchKernelGGL(k_gm_close, dim3(1), dim3(64), 0, st, words);
-        csc_product<double, 4>(s, alpha, beta, nz, V.y, w, nullptr, true);
+        if ((rc = product(4, (const double *)V.y, w)) != FD_OK) return;
         hipLaunchKernelGGL(k_gm_resid, dim3(gv), dim3(kBlock), 0, st, N, b, (const double *)w, V.r, S.d_scal, words, S.d_part);
         hipLaunchKernelGGL(k_gm_start<false>, dim3(gv), dim3(kBlock), 0, st, N, (const double *)V.r, G, S.rtol, S.d_scal, (const int *)words);
     };
@@ -783,9 +777,10 @@ static int csc_gmres_iterate(fd_csc_solver *s, double alpha, double beta, const 
     while (!stop) {
         int todo = S.max_iterations - enq < S.batch ? S.max_iterations - enq : S.batch;
         if (m - j < todo) todo = m - j;
-        for (int it = 0; it < todo; ++it) step(j++);
+        for (int it = 0; it < todo && rc == FD_OK; ++it) step(j++);
         enq += todo;
-        if (j == m || enq >= S.max_iterations) { cycle_end(); j = 0; }
+        if (rc == FD_OK && (j == m || enq >= S.max_iterations)) { cycle_end(); j = 0; }
+        if (rc != FD_OK) return rc;
         FD_HIP_CHECK(hipGetLastError());
         FD_HIP_CHECK(hipMemcpyAsync(&S.h_rec[nb & 1], S.d_words, sizeof(CsRecord), hipMemcpyDeviceToHost, st));
         FD_HIP_CHECK(hipEventRecord(S.ev[nb & 1], st));
@@ -794,6 +789,7 @@ static int csc_gmres_iterate(fd_csc_solver *s, double alpha, double beta, const 
             const CsRecord &rec = S.h_rec[(nb - 1) & 1];
             if (rec.done) stop = true;
             else if (rec.early) { cycle_end(); stop = true; }      // the cycle ended in the middle of that batch: what it has goes into y
+            if (rc != FD_OK) return rc;
         }
         ++nb;
         if (enq >= S.max_iterations) stop = true;
@@ -861,7 +857,29 @@ int fd_csc_solve_async(fd_csc_solver *s, double alpha, double beta, const void *
     }
     s->last_gmres = gmres;
     if (gmres) {
-        const int rc = csc_gmres_iterate(s, alpha, beta, nz, (const real_t *)b, V, blocks, apply);
+        const CsGm G = csc_gm(s, s->gm_m);
+        const int rc = csc_gmres_iterate(st, S, N, G, (const real_t *)b, V,
+            [&](const double *vj, double *z, const double **zj) {      // z = M^-1 v_j
+                if (blocks) apply(1, vj, z);
+                else hipLaunchKernelGGL(k_gm_scale<true>, dim3(gv), dim3(kBlock), 0, st, N, vj, (const double *)V.d, z, words);
+                *zj = z;
+                return FD_OK;
+            },
+            [&](int mode, const double *v, double *w) {
+                if (mode == 3) csc_product<double, 3>(s, alpha, beta, nz, v, w, nullptr, true);
+                else csc_product<double, 4>(s, alpha, beta, nz, v, w, nullptr, true);
+                return FD_OK;
+            },
+            [&](double *u, double *z) {      // y = y + M^-1 (V t): the diagonal inside k_gm_combine, the blocks behind it
+                if (!blocks) {
+                    hipLaunchKernelGGL(k_gm_combine<1>, dim3(gv), dim3(kBlock), 0, st, N, G, (const double *)V.d, V.y, words);
+                } else {
+                    hipLaunchKernelGGL(k_gm_combine<0>, dim3(gv), dim3(kBlock), 0, st, N, G, (const double *)V.d, u, words);
+                    apply(0, u, z);
+                    hipLaunchKernelGGL(k_gm_yadd, dim3(gv), dim3(kBlock), 0, st, N, V.y, (const double *)z, words);
+                }
+                return FD_OK;
+            });
         if (rc != FD_OK) return rc;
         hipLaunchKernelGGL(k_gm_final, dim3(cs_tiles(N, kBlock)), dim3(kBlock), 0, st, N, (const double *)V.y, (real_t *)y, S.d_words,
                            csc_gm(s, s->gm_m).klast, S.keep);
@@ -900,3 +918,7 @@ int fd_csc_solver_status(fd_csc_solver *s, int *flags_out, int64_t *iterations_o
     if (bnorm_out) *bnorm_out = std::sqrt(sc[S_BNORM2]);
     return FD_OK;
 }
+
+#ifndef FDJAC_F32
+#include "fdjac_jfnk.hip"      // the matrix-free consumer: Float64 only
+#endif

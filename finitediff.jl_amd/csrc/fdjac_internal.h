@@ -581,6 +581,36 @@ struct fd_plan {
     std::vector<float> samples[FD_NSTAGES];    // the individual spans (fd_plan_get_timing_samples), capped
 };
 
+// ---- the JVP plan (fdjac_jvp.hip) and the way into jvp_enqueue's pieces for a caller inside the library (fdjac_jfnk.hip) ----------
+struct fd_jvp_plan {
+    fd_ctx *ctx = nullptr;
+    int fdtype = 0;
+    int64_t M = 0, N = 0, ldx = 0, ldf = 0;
+    fdjac::real_t *d_X = nullptr, *d_FX = nullptr, *d_fx = nullptr, *d_eps = nullptr;
+    double *d_partial = nullptr;
+    fdjac::real_t *d_xs = nullptr, *d_vs = nullptr, *d_fin = nullptr, *d_out = nullptr;
+    int nparts = 1;
+    bool small_ok = true;          // fused single-workgroup launch of small problems (FDJAC_SMALL, read at plan creation)
+    fd_f_launch_lazy_jvp lazy_fn = nullptr;
+    int lazy_caps = 0;             // FD_LAZY_JVP_CAP_* of lazy_fn
+    bool lazy_diff = true;         // ask a FD_LAZY_JVP_CAP_QUOTIENT launcher for the finished quotient (FDJAC_LAZY_DIFF=0: never)
+};
+
+namespace fdjac {
+// jvp_enqueue with a caller's pieces in place of its own (not part of the C ABI; fd_jvp and fd_jvp_async pass none):
+struct JvpHooks {
+    bool have_partials;      // large route: the partial sums of dot(x, v) already lie in plan->d_partial, on k_dot_partial's grid
+                             // (plan->nparts workgroups) and in its per-thread order: no dot launch, k_jvp_eps reads them as they are
+    bool fin_is_base;        // f_in is f(x) as f! itself gives it: a quotient-capable lazy launcher may still write the quotient
+    void *user;
+    // instead of k_jvp_diff: the quotient is (a - b) / e with e = eps[0] (central: 2 eps[0]); b == NULL: a is `out`, where a lazy
+    // launcher has written the finished quotient.  Returns an FD_* code.
+    int (*close)(void *user, const real_t *a, const real_t *b, const real_t *eps, int central);
+};
+int jvp_enqueue_hooked(fd_jvp_plan *p, fd_f_launch f, void *fctx, const real_t *x, const real_t *v, const real_t *f_in, double relstep,
+                       double absstep, double dir, real_t *out, const JvpHooks *hk);
+}  // namespace fdjac
+
 namespace fdjac {
 int plan_record_fingerprint(fd_plan *p, int idx_kind, const fd_pattern_arrays *src, int64_t col0, int64_t col1);   // fdjac_match.hip
 }

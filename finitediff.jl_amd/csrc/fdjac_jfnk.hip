@@ -1,0 +1,405 @@
+// The MATRIX-FREE consumer (fd_jfnk_*): (alpha I + beta J(x)) y = b by the restarted GMRES of fdjac_cscgmres.hip on the
+// operator itself,  A(x) z = alpha z + beta q,  q = the finite-difference JVP of fdjac_jvp.hip for (x, z) -- no pattern, no colouring, no
+// stored J.  A piece of fdjac_cscsolve.hip (included there, in the Float64 build only): the GMRES kernels, CscSolveState, the words and
+// the scalars are that file's, the host loop is csc_gmres_iterate(); the JVP's launches are jvp_enqueue's, entered through JvpHooks
+// (fdjac_internal.h).  tests/jfnk_model.py restates every order in numpy and the GPU tests compare bits.
+//
+// THE OPERATOR.  q is what fd_jvp_async gives for (x, z) with the solver's steps and fdtype, on whichever route jvp_enqueue takes (small,
+// materialised, lazy values, lazy quotient); then w_e = alpha z_e + beta q_e, two multiplications and one addition.  The closing kernel
+// k_jf_close forms the quotient as k_jvp_diff does and the combination in the same pass: it stands where k_jvp_diff stood.
+// THE STEP'S z.  With a diagonal d (right preconditioner M = diag(d)) and N above kSmallN, k_jf_open reads x, v_j and d once, stores
+// z = v_j / d and leaves the partial sums of dot(x, z) on k_dot_partial's grid and in its per-thread order; k_jvp_eps takes them as they
+// are.  The order is the paired one when x is aligned to a pair (z is the solver's own and always is): jvp_enqueue's rule on (x, z),
+// wherever v_j = V + j N and d sit -- off a pair they are read element by element.  Up to kSmallN: k_gm_scale<true>, then k_jvp_small.
+// Without a diagonal z is v_j in place and the JVP's own dot reads it there: for an odd N its variant alternates with j.
+// THE REST is the sparse consumer's GMRES word for word: y0 = 0, CGS2, the rotations, the back substitution, the restart through the
+// same operator (r = b - A(x) y), flags, NaN in y after a failure unless the policy keeps the iterate.
+// After `cycle over` the kernels here do nothing (gm_idle), but the caller's f! is still launched by the steps already enqueued: what it
+// writes is scratch that nothing reads.
+#pragma once
+
+struct fd_jfnk_solver {
+    fd_ctx *ctx = nullptr;
+    int64_t N = 0, ld = 0;             // ld: N rounded up to 32 (every vector of d_vec starts on a pair)
+    int fdtype = FD_FORWARD, m = 30;
+    fdjac::CscSolveState S;
+    fd_jvp_plan *jp = nullptr;
+    double *d_vec = nullptr;           // r | z | w | u | y | fx: ld doubles each
+    double *d_gm = nullptr;            // fdjac_cscgmres.hip: CsGm
+    const double *d_diag = nullptr;    // the caller's diagonal, or NULL
+    double relstep = -1.0, absstep = -1.0, dir = 1.0;
+    int64_t applications = 0, base_evaluations = 0;
+    bool have_state = false;
+};
+
+namespace fdjac {
+
+// z = v / d, and this workgroup's sum of x_i z_i in k_dot_partial<PAIRED>'s order (fdjac_jvp.hip): the same loop, the same shuffle tree.
+// PAIRED is jvp_enqueue's own rule on the operands of the dot (x and z on a pair), so q is what fd_jvp_async gives for (x, z) wherever
+// v and d sit; VLOAD: v and d are on a pair too and are read 16 bytes at a time, otherwise element by element (the same values).
+template <bool PAIRED, bool VLOAD>
+__global__ void __launch_bounds__(kBlock) k_jf_open(const double *__restrict__ x, const double *__restrict__ v, const double *__restrict__ d,
+                                                    int64_t n, double *__restrict__ z, double *__restrict__ partial, const int *words)
+{
+    if (gm_idle(words)) return;
+    typedef double d2_t __attribute__((ext_vector_type(2)));
+    double acc = 0.0;
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    if (PAIRED) {
+        const int64_t n2 = n >> 1;
+        for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n2; i += stride) {
+            const d2_t a = reinterpret_cast<const d2_t *>(x)[i];
+            d2_t b, c;
+            if (VLOAD) {
+                b = reinterpret_cast<const d2_t *>(v)[i];
+                c = reinterpret_cast<const d2_t *>(d)[i];
+            } else {
+                b = d2_t{v[2 * i], v[2 * i + 1]};
+                c = d2_t{d[2 * i], d[2 * i + 1]};
+            }
+            const d2_t q = {b.x / c.x, b.y / c.y};
+            reinterpret_cast<d2_t *>(z)[i] = q;
+            acc += a.x * q.x;
+            acc += a.y * q.y;
+        }
+        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+            const double q = v[n - 1] / d[n - 1];
+            z[n - 1] = q;
+            acc += x[n - 1] * q;
+        }
+    } else {
+        for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+            const double q = v[i] / d[i];
+            z[i] = q;
+            acc += x[i] * q;
+        }
+    }
+    __shared__ double red[kBlock / 64];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+        for (int w = 0; w < kBlock / 64; ++w) t += red[w];
+        partial[blockIdx.x] = t;
+    }
+}
+
+// w = alpha z + beta q with q = (a - b) / e, e = eps[0] or 2 eps[0] exactly as k_jvp_diff forms it; b == NULL: a holds q already (a lazy
+// launcher's quotient; a may be w).  mode 3: nothing once the cycle is over; 4: nothing once the solve is; words == NULL: unguarded.
+template <bool VEC>
+__global__ void __launch_bounds__(kBlock) k_jf_close(const double *a, const double *b, const double *__restrict__ eps, int central, int64_t n,
+                                                     double alpha, double beta, const double *__restrict__ z, double *w, const int *words, int mode)
+{
+    if (words && (cs_word(words, W_DONE) || (mode == 3 && cs_word(words, W_EARLY)))) return;
+    typedef double d2_t __attribute__((ext_vector_type(2)));
+    const double e = central ? 2 * eps[0] : eps[0];
+    if (VEC) {
+        const int64_t i = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * 2;
+        if (i + 1 < n) {
+            d2_t q = *reinterpret_cast<const d2_t *>(a + i);
+            if (b) {
+                const d2_t bv = *reinterpret_cast<const d2_t *>(b + i);
+                q = d2_t{(q.x - bv.x) / e, (q.y - bv.y) / e};
+            }
+            const d2_t zv = *reinterpret_cast<const d2_t *>(z + i);
+            *reinterpret_cast<d2_t *>(w + i) = d2_t{alpha * zv.x + beta * q.x, alpha * zv.y + beta * q.y};
+        } else if (i < n) {
+            const double q = b ? (a[i] - b[i]) / e : a[i];
+            w[i] = alpha * z[i] + beta * q;
+        }
+        return;
+    }
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        const double q = b ? (a[i] - b[i]) / e : a[i];
+        w[i] = alpha * z[i] + beta * q;
+    }
+}
+
+// the start of a solve: r = b, y = 0, ||b||^2, and the diagonal's check -- k_cs_init<0> with the caller's d in place of the pattern's
+__global__ void __launch_bounds__(kBlock) k_jf_init(int N, const double *__restrict__ d, const double *__restrict__ b, double *__restrict__ r,
+                                                    double *__restrict__ y, double rtol, double *scal, int *words, double *part)
+{
+    __shared__ double s_w[kBlock / 64];
+    const int i0 = blockIdx.x * kCsVecTile + threadIdx.x;
+    double mine[1] = {0.0}, tot[1];
+    bool bad = false;
+    for (int k = 0; k < kCsVecTile / kBlock; ++k) {
+        const int i = i0 + k * kBlock;
+        if (i >= N) continue;
+        const double bi = b[i];
+        if (d) bad = bad || cs_bad_pivot(d[i]);
+        r[i] = bi; y[i] = 0.0;
+        mine[0] += bi * bi;
+    }
+    if (bad) atomicOr(words + W_FLAGS, 2);
+    if (cs_finish<1>(mine, part, words, tot, s_w) && threadIdx.x == 0) {
+        scal[S_BNORM2] = tot[0];
+        int done = 0;
+        if (tot[0] == 0.0) done = 1;                                                 // b = 0: y = 0, no iteration
+        else if (cs_word(words, W_FLAGS) & 2) done = 1;                              // a d_e that is zero or not finite
+        else if (cs_bad_pivot(tot[0])) { atomicOr(words + W_FLAGS, 2); done = 1; }   // ||b||^2 not finite
+        if (done) __hip_atomic_store(words + W_DONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+int balanced_grid(int64_t tiles, int64_t cap);
+
+struct JfOp {      // one application of the operator: what the closing kernel needs
+    fd_jfnk_solver *s;
+    double alpha, beta;
+    const double *z;
+    double *w;
+    const int *words;
+    int mode;
+};
+static int jf_close(void *user, const double *a, const double *b, const double *eps, int central)
+{
+    const JfOp *o = (const JfOp *)user;
+    const int64_t N = o->s->N;
+    hipStream_t st = o->s->ctx->stream;
+    const uintptr_t al = ((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)o->z) | ((uintptr_t)o->w);
+    if ((al & kPairMask) == 0)
+        hipLaunchKernelGGL(k_jf_close<true>, dim3((unsigned)((N + 2 * kBlock - 1) / (2 * kBlock))), dim3(kBlock), 0, st, a, b, eps, central, N, o->alpha,
+                           o->beta, o->z, o->w, o->words, o->mode);
+    else
+        hipLaunchKernelGGL(k_jf_close<false>, dim3(balanced_grid((N + kBlock - 1) / kBlock, (int64_t)o->s->ctx->num_cus * 8)), dim3(kBlock), 0, st, a, b,
+                           eps, central, N, o->alpha, o->beta, o->z, o->w, o->words, o->mode);
+    FD_HIP_CHECK(hipGetLastError());
+    return FD_OK;
+}
+// w = alpha z + beta J(x) z; fin: the subtrahend of the forward arm (NULL in the central arm); own_base: it is the solver's own f(x)
+static int jf_operator(fd_jfnk_solver *s, double alpha, double beta, fd_f_launch f, void *fctx, const double *x, const double *fin, bool own_base,
+                       const double *z, double *w, bool have_partials, const int *words, int mode)
+{
+    JfOp op = {s, alpha, beta, z, w, words, mode};
+    JvpHooks hk = {have_partials, own_base, &op, jf_close};
+    s->applications += 1;
+    return jvp_enqueue_hooked(s->jp, f, fctx, x, z, fin, s->relstep, s->absstep, s->dir, w, &hk);
+}
+// f(x) once per call in the forward arm without f_in: one launch of f!
+static int jf_base(fd_jfnk_solver *s, fd_f_launch f, void *fctx, const double *x, const double *f_in, const double **fin, bool *own)
+{
+    *fin = nullptr; *own = false;
+    if (s->fdtype != FD_FORWARD) return FD_OK;
+    if (f_in) { *fin = f_in; return FD_OK; }
+    double *fx = s->d_vec + 5 * s->ld;
+    const int rc = f(fctx, fx, x, 1, s->N, s->ld, 0, s->N, 0, (void *)s->ctx->stream);
+    FD_REQUIRE(rc == 0, FD_ERR_CALLBACK, "f! launcher returned %d", rc);
+    s->base_evaluations += 1;
+    *fin = fx; *own = true;
+    return FD_OK;
+}
+
+}  // namespace fdjac
+
+extern "C" {
+
+int fd_jfnk_solver_create(fd_ctx *ctx, int64_t N, int fdtype, int restart, fd_jfnk_solver **out)
+{
+    // (every range check stands before the first use of ctx: tests/test_jfnk_model_cpu.py sends them a context that is never dereferenced)
+    FD_REQUIRE(ctx && out, FD_ERR_ARG, "NULL argument");
+    *out = nullptr;
+    FD_REQUIRE(N >= 1 && N <= (int64_t)0x7FFFFFFF - kCsVecTile, FD_ERR_SHAPE, "N = %lld (1 .. 2^31 - 1025)", (long long)N);
+    if (fdtype != FD_FORWARD && fdtype != FD_CENTRAL) {
+        set_error("finite_difference_jvp doesn't support :complex-mode finite diff");
+        return FD_ERR_UNSUPPORTED;
+    }
+    FD_REQUIRE(restart >= 1 && restart <= kGmMax, FD_ERR_ARG, "restart = %d (1 .. %d)", restart, kGmMax);
+    FD_HIP_CHECK(hipSetDevice(ctx->device));
+    fd_jfnk_solver *s = new (std::nothrow) fd_jfnk_solver();
+    FD_REQUIRE(s != nullptr, FD_ERR_NOMEM, "out of host memory");
+    s->ctx = ctx; s->N = N; s->ld = (N + 31) / 32 * 32; s->fdtype = fdtype; s->m = restart;
+    const auto build = [&]() -> int {
+        const char *who = "jfnk solver";
+        const int rc = fd_jvp_plan_create(ctx, N, N, fdtype, &s->jp);
+        if (rc != FD_OK) return rc;
+        CSC_TRY(who, hipMalloc((void **)&s->d_vec, sizeof(double) * 6 * (size_t)s->ld));
+        CSC_TRY(who, hipMalloc((void **)&s->d_gm, sizeof(double) * gm_doubles((size_t)N, restart, cs_tiles(N, kCsVecTile))));
+        const int rs = s->S.create(who, ctx->stream, S_NSCAL, 2 * (int64_t)cs_tiles(N, kBlock));
+        if (rs != FD_OK) return rs;
+        s->have_state = true;
+        return FD_OK;
+    };
+    const int rc = build();
+    if (rc != FD_OK) {
+        (void)hipStreamSynchronize(ctx->stream);
+        s->S.free();
+        if (s->jp) (void)fd_jvp_plan_destroy(s->jp);
+        if (s->d_vec) (void)hipFree(s->d_vec);
+        if (s->d_gm) (void)hipFree(s->d_gm);
+        delete s;
+        return rc;
+    }
+    *out = s;
+    return FD_OK;
+}
+
+int fd_jfnk_solver_destroy(fd_jfnk_solver *s)
+{
+    if (!s) return FD_OK;
+    (void)hipSetDevice(s->ctx->device);
+    (void)hipStreamSynchronize(s->ctx->stream);
+    s->S.free();
+    (void)fd_jvp_plan_destroy(s->jp);
+    (void)hipFree(s->d_vec);
+    (void)hipFree(s->d_gm);
+    delete s;
+    return FD_OK;
+}
+
+int fd_jfnk_solver_set_options(fd_jfnk_solver *s, double rtol, int max_iterations)
+{
+    FD_REQUIRE(s != nullptr, FD_ERR_ARG, "solver is NULL");
+    return s->S.set_options(rtol, max_iterations);
+}
+
+int fd_jfnk_solver_set_policy(fd_jfnk_solver *s, int keep_unconverged)
+{
+    FD_REQUIRE(s != nullptr, FD_ERR_ARG, "solver is NULL");
+    return s->S.set_policy(keep_unconverged);
+}
+
+int fd_jfnk_solver_set_steps(fd_jfnk_solver *s, double relstep, double absstep, double dir)
+{
+    FD_REQUIRE(s != nullptr, FD_ERR_ARG, "solver is NULL");
+    s->relstep = relstep; s->absstep = absstep; s->dir = dir;
+    return FD_OK;
+}
+
+int fd_jfnk_solver_set_lazy_f(fd_jfnk_solver *s, fd_f_launch_lazy_jvp lazy, int caps)
+{
+    FD_REQUIRE(s != nullptr, FD_ERR_ARG, "solver is NULL");
+    FD_REQUIRE(lazy != nullptr || caps == 0, FD_ERR_ARG, "no lazy launcher installed");
+    const int rc = fd_jvp_plan_set_lazy_f(s->jp, lazy);
+    return rc != FD_OK ? rc : fd_jvp_plan_set_lazy_caps(s->jp, caps);
+}
+
+int fd_jfnk_solver_set_diagonal(fd_jfnk_solver *s, const void *d_dev)
+{
+    FD_REQUIRE(s != nullptr, FD_ERR_ARG, "solver is NULL");
+    s->d_diag = (const double *)d_dev;
+    return FD_OK;
+}
+
+int fd_jfnk_apply_async(fd_jfnk_solver *s, double alpha, double beta, fd_f_launch f, void *fctx, const void *x, const void *f_in, const void *z,
+                        void *w)
+{
+    FD_REQUIRE(s && f && x && z && w, FD_ERR_ARG, "NULL argument");
+    FD_REQUIRE(w != z && w != x, FD_ERR_ARG, "w must not be z or x");
+    FD_HIP_CHECK(hipSetDevice(s->ctx->device));
+    const double *fin;
+    bool own;
+    int rc = jf_base(s, f, fctx, (const double *)x, (const double *)f_in, &fin, &own);
+    if (rc == FD_OK) rc = jf_operator(s, alpha, beta, f, fctx, (const double *)x, fin, own, (const double *)z, (double *)w, false, nullptr, 0);
+    if (rc != FD_OK) (void)hipStreamSynchronize(s->ctx->stream);
+    return rc;
+}
+
+int fd_jfnk_solve_async(fd_jfnk_solver *s, double alpha, double beta, fd_f_launch f, void *fctx, const void *x, const void *f_in, const void *b,
+                        void *y)
+{
+    FD_REQUIRE(s && f && x && b && y, FD_ERR_ARG, "NULL argument");
+    FD_REQUIRE(y != x, FD_ERR_ARG, "y must not be x");
+    FD_HIP_CHECK(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    CscSolveState &S = s->S;
+    const int N = (int)s->N;
+    const size_t ld = (size_t)s->ld;
+    const unsigned gv = cs_tiles(N, kCsVecTile);
+    const double *xd = (const double *)x, *d = s->d_diag;
+    CsVecs V = {};
+    V.r = s->d_vec; V.p = s->d_vec + ld; V.v = s->d_vec + 2 * ld; V.s = s->d_vec + 3 * ld; V.y = s->d_vec + 4 * ld; V.d = const_cast<double *>(d);
+    const CsGm G = gm_view(s->d_gm, (size_t)N, s->m);
+    const int *words = S.d_words;
+    const auto run = [&]() -> int {
+        const double *fin;
+        bool own;
+        const int rb = jf_base(s, f, fctx, xd, (const double *)f_in, &fin, &own);
+        if (rb != FD_OK) return rb;
+        FD_HIP_CHECK(hipMemsetAsync(S.d_words, 0, sizeof(int) * W_NWORDS, st));
+        hipLaunchKernelGGL(k_jf_init, dim3(gv), dim3(kBlock), 0, st, N, d, (const double *)b, V.r, V.y, S.rtol, S.d_scal, S.d_words, S.d_part);
+        const bool fused = d != nullptr && !(s->jp->small_ok && s->N <= kSmallN);
+        bool partials = false;
+        return csc_gmres_iterate(st, S, N, G, (const double *)b, V,
+            [&](const double *vj, double *z, const double **zj) {      // z = v_j / d, or v_j itself
+                partials = false;
+                if (!d) { *zj = vj; return FD_OK; }
+                *zj = z;
+                if (!fused) {
+                    hipLaunchKernelGGL(k_gm_scale<true>, dim3(gv), dim3(kBlock), 0, st, N, vj, d, z, words);
+                    return FD_OK;
+                }
+                // the dot's order is jvp_enqueue's rule on (x, z); 0: scalar, 1: paired with v_j or d off a pair, 2: paired, 16-byte loads
+                const bool paired = ((((uintptr_t)xd) | ((uintptr_t)z)) & kPairMask) == 0;
+                const bool vload = ((((uintptr_t)vj) | ((uintptr_t)d)) & kPairMask) == 0;
+                fd_pick<0, 1, 2>(paired ? (vload ? 2 : 1) : 0, [&](auto HOW) {
+                    hipLaunchKernelGGL((k_jf_open<(HOW() > 0), (HOW() == 2)>), dim3(s->jp->nparts), dim3(kBlock), 0, st, xd, vj, d, (int64_t)N, z,
+                                       s->jp->d_partial, words);
+                });
+                partials = true;
+                return FD_OK;
+            },
+            [&](int mode, const double *v, double *w) {
+                const bool hp = mode == 3 && partials;
+                partials = false;
+                return jf_operator(s, alpha, beta, f, fctx, xd, fin, own, v, w, hp, words, mode);
+            },
+            [&](double *, double *) {      // y = y + u / d, or y = y + u
+                if (d) hipLaunchKernelGGL(k_gm_combine<1>, dim3(gv), dim3(kBlock), 0, st, N, G, d, V.y, words);
+                else hipLaunchKernelGGL(k_gm_combine<2>, dim3(gv), dim3(kBlock), 0, st, N, G, d, V.y, words);
+                return FD_OK;
+            });
+    };
+    const int rc = run();
+    if (rc != FD_OK) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    hipLaunchKernelGGL(k_gm_final, dim3(cs_tiles(N, kBlock)), dim3(kBlock), 0, st, N, (const double *)V.y, (double *)y, S.d_words, G.klast, S.keep);
+    FD_HIP_CHECK(hipGetLastError());
+    S.solved = true;
+    return FD_OK;
+}
+
+int fd_jfnk_solver_status(fd_jfnk_solver *s, int *flags, int64_t *iterations, double *resid, double *bnorm)
+{
+    FD_REQUIRE(s != nullptr, FD_ERR_ARG, "solver is NULL");
+    int w[W_NWORDS];
+    double sc[S_NSCAL];
+    const int rc = s->S.read_status(s->ctx, w, sc);
+    if (rc != FD_OK) return rc;
+    if (flags) *flags = w[W_FINAL];
+    if (iterations) *iterations = w[W_ITERS];
+    if (resid) *resid = sc[S_GRES];
+    if (bnorm) *bnorm = std::sqrt(sc[S_BNORM2]);
+    return FD_OK;
+}
+
+int fd_jfnk_solver_counts(fd_jfnk_solver *s, int64_t *applications, int64_t *base_evaluations)
+{
+    FD_REQUIRE(s != nullptr, FD_ERR_ARG, "solver is NULL");
+    if (applications) *applications = s->applications;
+    if (base_evaluations) *base_evaluations = s->base_evaluations;
+    return FD_OK;
+}
+
+int fd_jfnk_solver_basis(fd_jfnk_solver *s, const void **V_dev, const void **H_dev, int *restart, int *last_cycle_len)
+{
+    FD_REQUIRE(s != nullptr, FD_ERR_ARG, "solver is NULL");
+    FD_REQUIRE(s->S.solved, FD_ERR_UNSUPPORTED, "no solve has run on this solver");
+    const CsGm G = gm_view(s->d_gm, (size_t)s->N, s->m);
+    if (V_dev) *V_dev = G.V;
+    if (H_dev) *H_dev = G.H;
+    if (restart) *restart = s->m;
+    if (last_cycle_len) {
+        FD_HIP_CHECK(hipSetDevice(s->ctx->device));
+        FD_HIP_CHECK(hipStreamSynchronize(s->ctx->stream));
+        FD_HIP_CHECK(hipMemcpy(last_cycle_len, G.klast, sizeof(int), hipMemcpyDeviceToHost));
+    }
+    return FD_OK;
+}
+
+}  // extern "C"

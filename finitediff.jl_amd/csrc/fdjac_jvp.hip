@@ -172,20 +172,6 @@ k_jvp_diff(const real_t *__restrict__ a, const real_t *__restrict__ b, const rea
 
 }  // namespace fdjac
 
-struct fd_jvp_plan {
-    fd_ctx *ctx = nullptr;
-    int fdtype = 0;
-    int64_t M = 0, N = 0, ldx = 0, ldf = 0;
-    fdjac::real_t *d_X = nullptr, *d_FX = nullptr, *d_fx = nullptr, *d_eps = nullptr;
-    double *d_partial = nullptr;
-    fdjac::real_t *d_xs = nullptr, *d_vs = nullptr, *d_fin = nullptr, *d_out = nullptr;
-    int nparts = 1;
-    bool small_ok = true;          // fused single-workgroup launch of small problems (FDJAC_SMALL, read at plan creation)
-    fd_f_launch_lazy_jvp lazy_fn = nullptr;
-    int lazy_caps = 0;             // FD_LAZY_JVP_CAP_* of lazy_fn
-    bool lazy_diff = true;         // ask a FD_LAZY_JVP_CAP_QUOTIENT launcher for the finished quotient (FDJAC_LAZY_DIFF=0: never)
-};
-
 using namespace fdjac;
 
 extern "C" {
@@ -234,8 +220,10 @@ int fd_jvp_plan_destroy(fd_jvp_plan *p)
     return FD_OK;
 }
 
+// hk (fdjac_internal.h, JvpHooks): a caller inside the library that has the dot product's partial sums already and closes with a kernel
+// of its own; NULL (fd_jvp, fd_jvp_async): every launch below as it always was
 static int jvp_enqueue(fd_jvp_plan *p, fd_f_launch f, void *fctx, const real_t *xd, const real_t *vd, const real_t *fin,
-                       double relstep, double absstep, double dir, real_t *out)
+                       double relstep, double absstep, double dir, real_t *out, const JvpHooks *hk = nullptr)
 {
     hipStream_t s = p->ctx->stream;
     const int central = p->fdtype == FD_CENTRAL;
@@ -253,7 +241,8 @@ static int jvp_enqueue(fd_jvp_plan *p, fd_f_launch f, void *fctx, const real_t *
     // step as usual, then ONE f! launch that perturbs while loading -- the points pass and, in the forward arm, the
     // separate f(x) launch disappear.  A launcher that declines falls through to the materialised points.
     if (!small && p->lazy_fn) {
-        if (vx) hipLaunchKernelGGL(k_dot_partial<true>, dim3(p->nparts), dim3(kBlock), 0, s, xd, vd, p->N, p->d_partial);
+        if (hk && hk->have_partials) {}      // (the caller's kernel has left them in d_partial)
+        else if (vx) hipLaunchKernelGGL(k_dot_partial<true>, dim3(p->nparts), dim3(kBlock), 0, s, xd, vd, p->N, p->d_partial);
         else hipLaunchKernelGGL(k_dot_partial<false>, dim3(p->nparts), dim3(kBlock), 0, s, xd, vd, p->N, p->d_partial);
         hipLaunchKernelGGL(k_jvp_eps, dim3(1), dim3(kBlock), 0, s, p->d_partial, p->nparts, relstep, absstep, dir,
                            central ? 0 : 1, p->d_eps);
@@ -266,14 +255,17 @@ static int jvp_enqueue(fd_jvp_plan *p, fd_f_launch f, void *fctx, const real_t *
         lp.central = central;
         // a launcher that can, subtracts and divides itself and writes the JVP where the caller wants it: the call is
         // the step-size reduction + ONE f! launch (a caller's f_in is the subtrahend the reference uses: plain path then)
-        const bool quotient = (p->lazy_caps & FD_LAZY_JVP_CAP_QUOTIENT) && p->lazy_diff && !fin && ((((uintptr_t)out) & kPairMask) == 0);
+        // (hk->fin_is_base: fin is f(x) by the caller's own evaluation -- the subtrahend the launcher forms itself, bit for bit)
+        const bool quotient = (p->lazy_caps & FD_LAZY_JVP_CAP_QUOTIENT) && p->lazy_diff && (!fin || (hk && hk->fin_is_base)) &&
+                              ((((uintptr_t)out) & kPairMask) == 0);
         if (quotient) { lp.quotient_out = out; lp.base_out = nullptr; }
         const int lrc = p->lazy_fn(fctx, p->d_FX, &lp, p->ldf, (void *)s);
         FD_REQUIRE(lrc == 0 || lrc == FD_LAZY_DECLINED, FD_ERR_CALLBACK, "lazy JVP f! launcher returned %d", lrc);
-        if (lrc == 0 && quotient) return FD_OK;
+        if (lrc == 0 && quotient) return hk ? hk->close(hk->user, out, nullptr, p->d_eps, central) : FD_OK;
         if (lrc == 0) {
             const real_t *la = central ? p->d_FX + p->ldf : p->d_FX;
             const real_t *lb = central ? p->d_FX : (fin ? fin : p->d_fx);
+            if (hk) return hk->close(hk->user, la, lb, p->d_eps, central);
             if (((((uintptr_t)la) | ((uintptr_t)lb) | ((uintptr_t)out)) & kPairMask) == 0)
                 hipLaunchKernelGGL(k_jvp_diff<true>, dim3((unsigned)((p->M + 2 * kBlock - 1) / (2 * kBlock))), dim3(kBlock), 0, s,
                                    la, lb, p->d_eps, central, p->M, out);
@@ -289,7 +281,8 @@ static int jvp_enqueue(fd_jvp_plan *p, fd_f_launch f, void *fctx, const real_t *
         hipLaunchKernelGGL(k_jvp_small, dim3(1), dim3(kJvpSmallBlock), 0, s, xd, vd, p->N, relstep, absstep, dir, central,
                            base_in_batch ? 1 : -1, p->d_eps, p->d_X, p->ldx);
     } else {
-        if (vx) hipLaunchKernelGGL(k_dot_partial<true>, dim3(p->nparts), dim3(kBlock), 0, s, xd, vd, p->N, p->d_partial);
+        if (hk && hk->have_partials) {}      // (the caller's kernel has left them in d_partial)
+        else if (vx) hipLaunchKernelGGL(k_dot_partial<true>, dim3(p->nparts), dim3(kBlock), 0, s, xd, vd, p->N, p->d_partial);
         else hipLaunchKernelGGL(k_dot_partial<false>, dim3(p->nparts), dim3(kBlock), 0, s, xd, vd, p->N, p->d_partial);
         hipLaunchKernelGGL(k_jvp_eps, dim3(1), dim3(kBlock), 0, s, p->d_partial, p->nparts, relstep, absstep, dir,
                            central ? 0 : 1, p->d_eps);
@@ -322,6 +315,7 @@ static int jvp_enqueue(fd_jvp_plan *p, fd_f_launch f, void *fctx, const real_t *
         FD_REQUIRE(rc == 0, FD_ERR_CALLBACK, "f! launcher returned %d", rc);
         a = p->d_FX;
     }
+    if (hk) return hk->close(hk->user, a, b, p->d_eps, central);
     if (((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)out)) & kPairMask) == 0)
         hipLaunchKernelGGL(k_jvp_diff<true>, dim3((unsigned)((p->M + 2 * kBlock - 1) / (2 * kBlock))), dim3(kBlock), 0, s, a, b,
                            p->d_eps, central, p->M, out);
@@ -395,3 +389,11 @@ int fd_jvp_get_epsilon(fd_jvp_plan *p, double *eps_out)
 }
 
 }  // extern "C"
+
+namespace fdjac {
+int jvp_enqueue_hooked(fd_jvp_plan *p, fd_f_launch f, void *fctx, const real_t *x, const real_t *v, const real_t *f_in, double relstep,
+                       double absstep, double dir, real_t *out, const JvpHooks *hk)
+{
+    return jvp_enqueue(p, f, fctx, x, v, f_in, relstep, absstep, dir, out, hk);
+}
+}  // namespace fdjac

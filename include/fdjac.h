@@ -821,6 +821,49 @@ int fd_csc_solver_ilu_factors(fd_csc_solver *solver, const void **lu_dev, const 
 int fd_csc_solver_set_method(fd_csc_solver *solver, int method, int restart);
 int fd_csc_solver_gmres_basis(fd_csc_solver *solver, const void **V_dev, const void **H_dev, int *restart, int *last_cycle_len);
 
+/* ---- the MATRIX-FREE consumer: (alpha*I + beta*J(x)) y = b by restarted GMRES on the finite-difference JVP, J never stored --------------
+ * For an f! whose Jacobian pattern is dense, unknown or too wide to colour: the operator is  A(x) z = alpha*z + beta*q,  q what
+ * fd_jvp_async returns for (x, z) with the solver's steps and fdtype -- on whichever of its routes (small, materialised points, lazy
+ * values, lazy quotient), the same bits -- and w_e = alpha*z_e + beta*q_e, two multiplications and one addition.  f is square (M = N);
+ * Float64 only (no fd32_ twin); x, f_in, z, w, b, y and the diagonal are DEVICE arrays of N doubles.  In the forward arm f(x) is
+ * evaluated once per call (one launch of f!: a "base evaluation") when f_in is NULL; a given f_in is taken to be f(x); the central arm
+ * ignores it.  DESIGN.md 4.12 has the launches; tests/jfnk_model.py restates every order in numpy.
+ *   fd_jfnk_solver_create  N in 1 .. 2^31 - 1025 (else FD_ERR_SHAPE); fdtype FD_FORWARD or FD_CENTRAL (FD_COMPLEX: FD_ERR_UNSUPPORTED with
+ *                         the JVP's message); restart in 1..FD_CSC_GMRES_RESTART_MAX (else FD_ERR_ARG).  Allocates the JVP's scratch,
+ *                         six vectors and the basis ((restart + 1) * N doubles); synchronises.
+ *   fd_jfnk_solver_set_options / _set_policy   as fd_csc_solver_set_options / _set_policy (rtol default 1e-10, max_iterations 500).
+ *   fd_jfnk_solver_set_steps   relstep, absstep, dir as fd_jvp_async takes them (relstep <= 0: the default; absstep < 0: relstep).
+ *   fd_jfnk_solver_set_lazy_f  the lazy JVP launcher of f! and its FD_LAZY_JVP_CAP_* bits; NULL clears (caps must be 0 then).
+ *   fd_jfnk_solver_set_diagonal  N doubles d, read by every solve: the right preconditioner M = diag(d) (z = v_j / d, y += u / d).  NULL
+ *                         (the default): none.  A d_e that is zero or not finite is a breakdown before the first step.
+ *   fd_jfnk_apply_async   w = A(x) z; w must not be z or x.  The diagonal plays no part.
+ *   fd_jfnk_solve_async   GMRES(restart) exactly as fd_csc_solver_set_method describes it (y0 = 0, CGS2, the estimate, the restart through the
+ *                         explicit r = b - A(x) y, max_iterations caps the Arnoldi steps, b = 0: y = 0 with 0 iterations, ||b||^2 not
+ *                         finite: breakdown), with the operator above in place of the stored product.  y may be b, not x.  The
+ *                         iterations are enqueued in batches that never span a cycle; one 16-byte record per batch reaches the host.
+ *                         Steps enqueued after the cycle is over change nothing that the result or the diagnostic reads, BUT THE
+ *                         CALLER'S f! IS STILL LAUNCHED by them (on scratch points; what it writes is not read).  One call may be in
+ *                         flight per solver.  The operator is only approximately linear: the estimate inherits that.
+ *   fd_jfnk_solver_status  synchronises; flags (bit 0: the iterations ran out; bit 1: breakdown), iterations, the last estimate, ||b||_2.
+ *                         After a failure y is NaN unless fd_jfnk_solver_set_policy(solver, 1).
+ *   fd_jfnk_solver_counts  operator applications and base evaluations enqueued since creation.
+ *   fd_jfnk_solver_basis   DIAGNOSTIC ONLY, as fd_csc_solver_gmres_basis (FD_ERR_UNSUPPORTED before the first solve). */
+typedef struct fd_jfnk_solver fd_jfnk_solver;
+int fd_jfnk_solver_create(fd_ctx *ctx, int64_t N, int fdtype, int restart, fd_jfnk_solver **out);
+int fd_jfnk_solver_destroy(fd_jfnk_solver *solver);
+int fd_jfnk_solver_set_options(fd_jfnk_solver *solver, double rtol, int max_iterations);
+int fd_jfnk_solver_set_policy(fd_jfnk_solver *solver, int keep_unconverged);
+int fd_jfnk_solver_set_steps(fd_jfnk_solver *solver, double relstep, double absstep, double dir);
+int fd_jfnk_solver_set_lazy_f(fd_jfnk_solver *solver, fd_f_launch_lazy_jvp lazy, int caps);
+int fd_jfnk_solver_set_diagonal(fd_jfnk_solver *solver, const void *d_dev);
+int fd_jfnk_apply_async(fd_jfnk_solver *solver, double alpha, double beta, fd_f_launch f, void *fctx, const void *x, const void *f_in,
+                        const void *z, void *w);
+int fd_jfnk_solve_async(fd_jfnk_solver *solver, double alpha, double beta, fd_f_launch f, void *fctx, const void *x, const void *f_in,
+                        const void *b, void *y);
+int fd_jfnk_solver_status(fd_jfnk_solver *solver, int *flags, int64_t *iterations, double *resid, double *bnorm);
+int fd_jfnk_solver_counts(fd_jfnk_solver *solver, int64_t *applications, int64_t *base_evaluations);
+int fd_jfnk_solver_basis(fd_jfnk_solver *solver, const void **V_dev, const void **H_dev, int *restart, int *last_cycle_len);
+
 /* ---- the LEAST-SQUARES consumer: J v, J^T v and the damped Gauss-Newton step for a RECTANGULAR J (M x N) in SparseMatrixCSC storage ----
  * The pattern is that of a CSC plan that holds every column: colptr (N + 1) and rowval (nnz), Int32 or Int64, base 0 or 1, on the host or
  * on the device, exactly as fd_csc_solver_create takes them; M >= 1, N >= 1, nnz < 2^31, rows strictly ascending within a column and below

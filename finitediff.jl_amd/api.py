@@ -746,6 +746,31 @@ class CscSolver(_CscConsumer):
         H = torch.as_tensor(_DevView(ph.value, m.value * (m.value + 1), False), device=dev).clone().reshape(m.value, m.value + 1)
         return V, H, k.value
 
+    def _f64(self, a, what):
+        p, k, _keep = _ptr(a, what, np.dtype(np.float64))
+        if k != _l.DEVICE:
+            raise ValueError("the solver takes device arrays")
+        if int(np.prod(a.shape)) != self.N:
+            raise ValueError("%s must hold N = %d elements" % (what, self.N))
+        return p
+
+    def factor(self, J, alpha=1.0, beta=-1.0):
+        """Enqueue the factorisation M of alpha*I + beta*J for whichever preconditioner is selected (fd_csc_solver_factor_async): the
+        launches and the bits of a solve's set-up, kept until the next solve, preconditioner setter or ``factor`` on this solver.
+        ``apply_preconditioner`` applies it; ``JfnkSolver.set_preconditioner`` borrows it."""
+        _l.check(self.Lt.fd_csc_solver_factor_async(self.handle, float(alpha), float(beta), self._vals(J)))
+
+    def apply_preconditioner(self, x, out):
+        """Enqueue out = M^-1 x with the last ``factor`` (fd_csc_solver_apply_async); x and out are float64 device arrays of N elements
+        whatever the solver's dtype.  Error 3 before any ``factor``, 9 (stale) after a later solve or preconditioner setter."""
+        _l.check(self.Lt.fd_csc_solver_apply_async(self.handle, self._f64(x, "x"), self._f64(out, "out")))
+
+    def factor_status(self):
+        """Synchronises.  {"flags": bit 1 a pivot of the last factorisation was zero or not finite}."""
+        f = C.c_int()
+        _l.check(self.Lt.fd_csc_solver_factor_status(self.handle, C.byref(f)))
+        return {"flags": f.value}
+
     def row_lists(self):
         """The solver's lists as int32 CUDA tensors (copies): row_ptr, row_col, row_slot, diag_slot; and the number of long rows."""
         ps = [C.c_void_p() for _ in range(4)]
@@ -891,6 +916,16 @@ class JfnkSolver:
         """N doubles on the device, the right preconditioner M = diag(d), read by every solve (the array is kept alive); None: none."""
         self._diag_keep = d
         _l.check(self.ctx.L.fd_jfnk_solver_set_diagonal(self.handle, self._dev(d, "d")))
+
+    def set_preconditioner(self, csc_solver):
+        """A ``CscSolver`` (float64, same context, same N) lent as the right preconditioner, or None to clear
+        (fd_jfnk_solver_set_csc_preconditioner).  Every following solve uses whatever that solver's last ``factor`` built -- lagged by
+        design: factor at x0, solve at any x -- and raises error 3 without a factorisation, 9 (stale) once a later solve or
+        preconditioner setter on the lent solver has invalidated it.  Not together with ``set_diagonal``.  The solver is kept alive."""
+        if csc_solver is not None and not isinstance(csc_solver, CscSolver):
+            raise TypeError("set_preconditioner takes a CscSolver or None")
+        _l.check(self.ctx.L.fd_jfnk_solver_set_csc_preconditioner(self.handle, None if csc_solver is None else csc_solver.handle))
+        self._pc_keep = csc_solver
 
     def set_lazy(self, f=None, quotient=True):
         """Install ``f``'s lazy JVP launcher (``f.lazy_jvp_fn``; a raw launcher is taken as it is, with ``quotient`` as its capability

@@ -168,6 +168,18 @@ __global__ void __launch_bounds__(kBlock) k_cs_init(CsView P, CsVecs V, double a
         if (done) __hip_atomic_store(words + W_DONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
+// fd_csc_solver_factor_async under the Jacobi preconditioner: d = alpha + beta J_ii as k_cs_init<0> forms it, into storage of the
+// factorisation's own; a d_i that is zero or not finite: breakdown in the factorisation's words
+__global__ void __launch_bounds__(kBlock) k_cs_fdiag(CsView P, double alpha, double beta, const real_t *__restrict__ nz, double *__restrict__ d,
+                                                     int *words)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= P.N) return;
+    const int q = P.diag[i];
+    const double di = q >= 0 ? alpha + beta * (double)nz[q] : alpha;
+    d[i] = di;
+    if (cs_bad_pivot(di)) cs_breakdown(words);
+}
 // p = r + beta (p - omega v), ph = p / d  (PC = 1: ph is k_cs_bapply's)
 template <int PC>
 __global__ void __launch_bounds__(kBlock) k_cs_p(int N, CsVecs V, const double *scal, const int *words)
@@ -452,8 +464,18 @@ struct fd_csc_solver : fdjac::CscHandle {      // d_vec: ten vectors of N double
     size_t gm_cap = 0;                 // doubles allocated
     int gm_m = 0;                      // the restart of the last GMRES solve, 0: none yet
     bool last_gmres = false;           // the last solve was a GMRES solve: its status reads the estimate
+    // the factorisation as an operation of its own (fd_csc_solver_factor_async / _apply_async; the matrix-free consumer borrows it):
+    // `gen` counts what invalidates one -- a solve, a preconditioner setter, another factor -- and fact_gen is its value at the last
+    // factor (0: none), so the factorisation stands while the two are equal
+    int elem_bytes = (int)sizeof(FDJAC_REAL);    // which element build made the handle (fd_jfnk_solver_set_csc_preconditioner asks)
+    uint64_t gen = 0, fact_gen = 0;
+    int fact_kind = FD_CSC_PRECOND_JACOBI, fact_bs = 0;      // what the last factor built
+    double *d_fdiag = nullptr;         // Jacobi: the N diagonals of the last factor (V.d is a solve's)
+    int *d_fwords = nullptr;           // 2 W_NWORDS: the factorisation's words (flags bit 1, done), then a block that stays zero
     ~fd_csc_solver()
     {
+        if (d_fdiag) (void)hipFree(d_fdiag);
+        if (d_fwords) (void)hipFree(d_fwords);
         if (d_gm) (void)hipFree(d_gm);
         if (d_minv) (void)hipFree(d_minv);
         if (d_ilu_int) (void)hipFree(d_ilu_int);
@@ -506,6 +528,7 @@ int fd_csc_solver_set_preconditioner(fd_csc_solver *s, int kind, int block_size)
         FD_REQUIRE(block_size >= 2 && block_size <= kCsBsMax, FD_ERR_ARG, "block_size = %d (2 .. %d)", block_size, kCsBsMax);
     s->pc_kind = kind;
     s->pc_bs = kind == FD_CSC_PRECOND_BLOCK_JACOBI ? block_size : 0;
+    s->gen += 1;
     return FD_OK;
 }
 
@@ -656,6 +679,7 @@ int fd_csc_solver_set_block_ilu(fd_csc_solver *s, int block_size)
     FD_REQUIRE(block_size >= 2 && block_size <= kCsIluBsMax, FD_ERR_ARG, "block_size = %d (2 .. %d)", block_size, kCsIluBsMax);
     FD_HIP_CHECK(hipSetDevice(s->ctx->device));
     FD_HIP_CHECK(hipStreamSynchronize(s->ctx->stream));
+    s->gen += 1;
     if (s->ilu_bs != block_size) {
         const int rc = ilu_build(s, block_size);
         if (rc != FD_OK) {               // the preconditioner of before stays selected; block ILU of another size has lost its schedule
@@ -704,6 +728,33 @@ int fd_csc_solver_row_lists(fd_csc_solver *s, const void **row_ptr, const void *
     if (nnz_out) *nnz_out = s->L.nnz;
     if (long_rows_out) *long_rows_out = s->L.nlong_r;
     return FD_OK;
+}
+
+// bs planes of N doubles in d_minv: allocated by the first solve or factor that needs them, grown when a larger block size comes
+static int csc_minv_reserve(fd_csc_solver *s, int bs)
+{
+    const size_t n = (size_t)s->L.N;
+    if (s->minv_cap >= (size_t)bs * n) return FD_OK;
+    FD_HIP_CHECK(hipStreamSynchronize(s->ctx->stream));
+    if (s->d_minv) (void)hipFree(s->d_minv);
+    s->d_minv = nullptr; s->minv_cap = 0; s->minv_bs = 0;
+    const hipError_t e = hipMalloc((void **)&s->d_minv, sizeof(double) * (size_t)bs * n);
+    if (e != hipSuccess) { (void)hipGetLastError(); FD_REQUIRE(false, FD_ERR_NOMEM, "block Jacobi: %d planes of %d doubles: %s", bs, (int)n, hipGetErrorString(e)); }
+    s->minv_cap = (size_t)bs * n;
+    return FD_OK;
+}
+static void csc_binv_launch(fd_csc_solver *s, int bs, double alpha, double beta, const real_t *nz, int *words)
+{
+    hipLaunchKernelGGL(k_cs_binv, dim3(cs_tiles(cs_tiles(s->L.N, bs), kCsBinvWaves)), dim3(kCsBinvWaves * 64),
+                       sizeof(double) * (size_t)kCsBinvWaves * (size_t)(bs * (2 * bs + 1) + bs), s->ctx->stream, cs_view(s->L, s->window), bs, alpha, beta, nz,
+                       s->d_minv, words);
+    s->minv_bs = bs;
+}
+static void csc_ilu_factor_launch(fd_csc_solver *s, double alpha, double beta, const real_t *nz, int *words)
+{
+    hipLaunchKernelGGL(k_cs_ilu_factor, dim3((unsigned)ilu_nblk(s, s->ilu_bs)), dim3(kBlock), 0, s->ctx->stream, cs_view(s->L, s->window), csc_ilu(s), alpha, beta,
+                       nz, s->d_ilu, s->d_ilu + (size_t)s->L.nnz, words);
+    s->ilu_factored = true;
 }
 
 template <typename TV, int MODE>
@@ -811,13 +862,10 @@ int fd_csc_solve_async(fd_csc_solver *s, double alpha, double beta, const void *
     const CsView P = cs_view(s->L, s->window);
     const unsigned gv = cs_tiles(N, kCsVecTile);
     const int bs = s->pc_kind == FD_CSC_PRECOND_BLOCK_JACOBI ? s->pc_bs : 0;
-    if (bs > 0 && s->minv_cap < (size_t)bs * n) {
-        FD_HIP_CHECK(hipStreamSynchronize(st));
-        if (s->d_minv) (void)hipFree(s->d_minv);
-        s->d_minv = nullptr; s->minv_cap = 0; s->minv_bs = 0;
-        const hipError_t e = hipMalloc((void **)&s->d_minv, sizeof(double) * (size_t)bs * n);
-        if (e != hipSuccess) { (void)hipGetLastError(); FD_REQUIRE(false, FD_ERR_NOMEM, "block Jacobi: %d planes of %d doubles: %s", bs, N, hipGetErrorString(e)); }
-        s->minv_cap = (size_t)bs * n;
+    s->gen += 1;      // whatever fd_csc_solver_factor_async left is this solve's from here on
+    if (bs > 0) {
+        const int rm = csc_minv_reserve(s, bs);
+        if (rm != FD_OK) return rm;
     }
     const bool gmres = s->method == FD_CSC_METHOD_GMRES;
     if (gmres && (s->gm_cap < gm_doubles(n, s->gm_restart, gv) || s->gm_m != s->gm_restart)) {
@@ -847,14 +895,8 @@ int fd_csc_solve_async(fd_csc_solver *s, double alpha, double beta, const void *
     // the start: init, then factor or invert
     if (blocks) hipLaunchKernelGGL(k_cs_init<1>, dim3(gv), dim3(kBlock), 0, st, P, V, alpha, beta, nz, (const real_t *)b, S.rtol, S.d_scal, S.d_words, S.d_part);
     else hipLaunchKernelGGL(k_cs_init<0>, dim3(gv), dim3(kBlock), 0, st, P, V, alpha, beta, nz, (const real_t *)b, S.rtol, S.d_scal, S.d_words, S.d_part);
-    if (ilu) {
-        hipLaunchKernelGGL(k_cs_ilu_factor, dim3(gi), dim3(kBlock), 0, st, P, I, alpha, beta, nz, s->d_ilu, s->d_ilu + (size_t)s->L.nnz, S.d_words);
-        s->ilu_factored = true;
-    } else if (bs > 0) {
-        hipLaunchKernelGGL(k_cs_binv, dim3(cs_tiles(cs_tiles(N, bs), kCsBinvWaves)), dim3(kCsBinvWaves * 64),
-                           sizeof(double) * (size_t)kCsBinvWaves * (size_t)(bs * (2 * bs + 1) + bs), st, P, bs, alpha, beta, nz, s->d_minv, S.d_words);
-        s->minv_bs = bs;
-    }
+    if (ilu) csc_ilu_factor_launch(s, alpha, beta, nz, S.d_words);
+    else if (bs > 0) csc_binv_launch(s, bs, alpha, beta, nz, S.d_words);
     s->last_gmres = gmres;
     if (gmres) {
         const CsGm G = csc_gm(s, s->gm_m);
@@ -902,6 +944,90 @@ int fd_csc_solve_async(fd_csc_solver *s, double alpha, double beta, const void *
     hipLaunchKernelGGL(k_cs_final, dim3(cs_tiles(N, kBlock)), dim3(kBlock), 0, st, N, (const double *)V.y, (real_t *)y, S.d_words, S.keep);
     FD_HIP_CHECK(hipGetLastError());
     S.solved = true;
+    return FD_OK;
+}
+
+// ---- the factorisation and its application as operations of their own ----------------------------------------------------------------
+// M for alpha I + beta J from whichever preconditioner is selected: the launches a solve runs behind its k_cs_init, on words of the
+// factorisation's own (a solve clears S.d_words), so the bits are those a solve with the same (alpha, beta, nzval) leaves
+int fd_csc_solver_factor_async(fd_csc_solver *s, double alpha, double beta, const void *nzval)
+{
+    FD_REQUIRE(s != nullptr, FD_ERR_ARG, "solver is NULL");
+    FD_REQUIRE(nzval || s->L.nnz == 0, FD_ERR_ARG, "nzval is NULL");
+    FD_HIP_CHECK(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    const int N = (int)s->L.N;
+    const real_t *nz = (const real_t *)nzval;
+    s->gen += 1;
+    s->fact_gen = 0;
+    const char *who = "csc solver factor";
+    if (!s->d_fwords) {
+        CSC_TRY(who, hipMalloc((void **)&s->d_fwords, sizeof(int) * 2 * W_NWORDS));
+        CSC_TRY(who, hipMemsetAsync(s->d_fwords, 0, sizeof(int) * 2 * W_NWORDS, st));
+    }
+    const int kind = s->pc_kind, bs = s->pc_bs;
+    if (kind == FD_CSC_PRECOND_JACOBI && !s->d_fdiag) CSC_TRY(who, hipMalloc((void **)&s->d_fdiag, sizeof(double) * (size_t)N));
+    if (kind == FD_CSC_PRECOND_BLOCK_JACOBI) {
+        const int rm = csc_minv_reserve(s, bs);
+        if (rm != FD_OK) return rm;
+    }
+    FD_HIP_CHECK(hipMemsetAsync(s->d_fwords, 0, sizeof(int) * W_NWORDS, st));
+    if (kind == kCsPcIlu) csc_ilu_factor_launch(s, alpha, beta, nz, s->d_fwords);
+    else if (kind == FD_CSC_PRECOND_BLOCK_JACOBI) csc_binv_launch(s, bs, alpha, beta, nz, s->d_fwords);
+    else hipLaunchKernelGGL(k_cs_fdiag, dim3(cs_tiles(N, kBlock)), dim3(kBlock), 0, st, cs_view(s->L, s->window), alpha, beta, nz, s->d_fdiag, s->d_fwords);
+    FD_HIP_CHECK(hipGetLastError());
+    s->fact_kind = kind; s->fact_bs = bs;
+    s->fact_gen = s->gen;
+    return FD_OK;
+}
+
+// is the factorisation of the last fd_csc_solver_factor_async still in the solver's buffers?  FD_OK, or the code with its message
+static int csc_factor_valid(const fd_csc_solver *s)
+{
+    FD_REQUIRE(s->fact_gen != 0, FD_ERR_UNSUPPORTED, "fd_csc_solver_factor_async has not run on this solver");
+    FD_REQUIRE(s->fact_gen == s->gen, FD_ERR_STALE,
+               "the factorisation is stale: a solve or a preconditioner setter came after fd_csc_solver_factor_async and its buffers are no longer that factorisation's");
+    return FD_OK;
+}
+// out = M^-1 x with the solver's own apply kernels: WHICH 0 on `words` (W_DONE ends it), 1 also on `cycle over`
+static void csc_factor_apply(fd_csc_solver *s, int which, const double *x, double *out, const int *words)
+{
+    hipStream_t st = s->ctx->stream;
+    const int N = (int)s->L.N;
+    const unsigned gv = cs_tiles(N, kCsVecTile);
+    if (s->fact_kind == kCsPcIlu) {
+        hipLaunchKernelGGL(which ? k_cs_ilu_apply<1> : k_cs_ilu_apply<0>, dim3((unsigned)ilu_nblk(s, s->ilu_bs)), dim3(kBlock), 0, st, cs_view(s->L, s->window),
+                           csc_ilu(s), (const double *)s->d_ilu, (const double *)(s->d_ilu + (size_t)s->L.nnz), x, out, words);
+    } else if (s->fact_kind == FD_CSC_PRECOND_BLOCK_JACOBI) {
+        hipLaunchKernelGGL(which ? k_cs_bapply<1> : k_cs_bapply<0>, dim3(gv), dim3(kBlock), 0, st, N, s->fact_bs, (const double *)s->d_minv, x, out, words);
+    } else {
+        hipLaunchKernelGGL(k_gm_scale<true>, dim3(gv), dim3(kBlock), 0, st, N, x, (const double *)s->d_fdiag, out, words);
+    }
+}
+
+// out = M^-1 x, N doubles each in either element build, unguarded: the words it runs on stay zero
+int fd_csc_solver_apply_async(fd_csc_solver *s, const void *x, void *out)
+{
+    FD_REQUIRE(s && x && out, FD_ERR_ARG, "NULL argument");
+    FD_REQUIRE(out != x, FD_ERR_ARG, "out must not be x");
+    const int rv = csc_factor_valid(s);
+    if (rv != FD_OK) return rv;
+    FD_HIP_CHECK(hipSetDevice(s->ctx->device));
+    csc_factor_apply(s, 0, (const double *)x, (double *)out, s->d_fwords + W_NWORDS);
+    FD_HIP_CHECK(hipGetLastError());
+    return FD_OK;
+}
+
+// synchronises; flags bit 1: a pivot of the last factorisation was zero or not finite
+int fd_csc_solver_factor_status(fd_csc_solver *s, int *flags)
+{
+    FD_REQUIRE(s != nullptr, FD_ERR_ARG, "solver is NULL");
+    FD_REQUIRE(s->d_fwords != nullptr, FD_ERR_UNSUPPORTED, "fd_csc_solver_factor_async has not run on this solver");
+    FD_HIP_CHECK(hipSetDevice(s->ctx->device));
+    FD_HIP_CHECK(hipStreamSynchronize(s->ctx->stream));
+    int w[W_NWORDS];
+    FD_HIP_CHECK(hipMemcpy(w, s->d_fwords, sizeof w, hipMemcpyDeviceToHost));
+    if (flags) *flags = w[W_FLAGS] & 2;
     return FD_OK;
 }
 

@@ -81,6 +81,9 @@
 #define fd_csc_solver_ilu_factors fd32_csc_solver_ilu_factors
 #define fd_csc_solver_set_method fd32_csc_solver_set_method
 #define fd_csc_solver_gmres_basis fd32_csc_solver_gmres_basis
+#define fd_csc_solver_factor_async fd32_csc_solver_factor_async
+#define fd_csc_solver_apply_async fd32_csc_solver_apply_async
+#define fd_csc_solver_factor_status fd32_csc_solver_factor_status
 #define fd_csc_matvec_async fd32_csc_matvec_async
 #define fd_csc_solve_async fd32_csc_solve_async
 #define fd_csc_solver_status fd32_csc_solver_status

@@ -12,6 +12,11 @@
 // are.  The order is the paired one when x is aligned to a pair (z is the solver's own and always is): jvp_enqueue's rule on (x, z),
 // wherever v_j = V + j N and d sit -- off a pair they are read element by element.  Up to kSmallN: k_gm_scale<true>, then k_jvp_small.
 // Without a diagonal z is v_j in place and the JVP's own dot reads it there: for an odd N its variant alternates with j.
+// A LENT FACTORISATION (fd_jfnk_solver_set_csc_preconditioner): M is what a sparse consumer's fd_csc_solver_factor_async last built --
+// lagged by design, checked for validity before anything is enqueued.  Its Jacobi kind IS the diagonal path on the factored diagonal;
+// block ILU applies with the lender's k_cs_ilu_apply and leaves the dot to the JVP; block Jacobi above kSmallN runs k_jf_open_blocks,
+// k_jf_open with k_cs_bapply's sum in place of the division (up to kSmallN: k_cs_bapply, then k_jvp_small).  The cycle's end is the
+// sparse consumer's: k_gm_combine<0>, the apply, k_gm_yadd.  tests/jfnk_pc_model.py composes the existing models of all of it.
 // THE REST is the sparse consumer's GMRES word for word: y0 = 0, CGS2, the rotations, the back substitution, the restart through the
 // same operator (r = b - A(x) y), flags, NaN in y after a failure unless the policy keeps the iterate.
 // After `cycle over` the kernels here do nothing (gm_idle), but the caller's f! is still launched by the steps already enqueued: what it
@@ -27,6 +32,7 @@ struct fd_jfnk_solver {
     double *d_vec = nullptr;           // r | z | w | u | y | fx: ld doubles each
     double *d_gm = nullptr;            // fdjac_cscgmres.hip: CsGm
     const double *d_diag = nullptr;    // the caller's diagonal, or NULL
+    fd_csc_solver *pc = nullptr;       // a sparse consumer's handle lent as the right preconditioner, or NULL (never both)
     double relstep = -1.0, absstep = -1.0, dir = 1.0;
     int64_t applications = 0, base_evaluations = 0;
     bool have_state = false;
@@ -86,6 +92,74 @@ __global__ void __launch_bounds__(kBlock) k_jf_open(const double *__restrict__ x
     }
 }
 
+// z = Minv v over the block-Jacobi planes of a lent fd_csc_solver (k_cs_bapply's sum: from +0.0, c ascending, one multiply and one add,
+// short last block), and this workgroup's sum of x_i z_i in k_dot_partial<PAIRED>'s order, on its grid.  Trip k of workgroup b covers
+// the consecutive elements that k_dot_partial gives the workgroup on that trip: 512 from 2 (b 256 + k stride) when PAIRED (a
+// pair per thread, z stored 16 bytes at a time), 256 from b 256 + k stride otherwise (x off a pair).  v for that range, widened to
+// whole blocks, goes through LDS element by element wherever it sits.  The odd-N tail is thread 0 of workgroup 0's, as in k_jf_open.
+template <bool PAIRED>
+__global__ void __launch_bounds__(kBlock) k_jf_open_blocks(const double *__restrict__ x, const double *__restrict__ v, const double *__restrict__ minv,
+                                                           int bs, int64_t n, double *__restrict__ z, double *__restrict__ partial, const int *words)
+{
+    constexpr int PER = PAIRED ? 2 : 1;
+    __shared__ double s_v[2 * kBlock + 2 * (kCsBsMax - 1)];
+    if (gm_idle(words)) return;
+    typedef double d2_t __attribute__((ext_vector_type(2)));
+    double acc = 0.0;
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    const int64_t nloop = PAIRED ? (n >> 1) : n;                  // pairs, or elements
+    // one element of z: its block's row of Minv times the block's v (from LDS: `sv` holds v from element w0 on)
+    const auto row = [=](int64_t e, const double *sv, int64_t w0) {
+        const int64_t b0 = e / bs * bs;
+        const int nb = n - b0 < bs ? (int)(n - b0) : bs;
+        const double *m = minv + e, *vb = sv + (b0 - w0);
+        double t = 0.0;
+#pragma unroll 8
+        for (int c = 0; c < nb; ++c) t += m[(size_t)c * (size_t)n] * vb[c];
+        return t;
+    };
+    for (int64_t base = (int64_t)blockIdx.x * kBlock; base < nloop; base += stride) {      // (the same trips in every thread: barriers)
+        const int64_t e0 = base * PER, e1 = e0 + kBlock * PER < nloop * PER ? e0 + kBlock * PER : nloop * PER;
+        const int64_t w0 = e0 / bs * bs;
+        int64_t w1 = (e1 + bs - 1) / bs * bs;
+        if (w1 > n) w1 = n;
+        for (int64_t i = w0 + threadIdx.x; i < w1; i += kBlock) s_v[i - w0] = v[i];
+        __syncthreads();
+        const int64_t i = base + threadIdx.x;
+        if (i < nloop) {
+            if (PAIRED) {
+                const d2_t a = reinterpret_cast<const d2_t *>(x)[i];
+                const d2_t q = {row(2 * i, s_v, w0), row(2 * i + 1, s_v, w0)};
+                reinterpret_cast<d2_t *>(z)[i] = q;
+                acc += a.x * q.x;
+                acc += a.y * q.y;
+            } else {
+                const double q = row(i, s_v, w0);
+                z[i] = q;
+                acc += x[i] * q;
+            }
+        }
+        __syncthreads();
+    }
+    if (PAIRED && (n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        const int64_t e = n - 1, b0 = e / bs * bs;
+        double q = 0.0;
+        for (int c = 0; c < (int)(n - b0); ++c) q += minv[(size_t)c * (size_t)n + e] * v[b0 + c];
+        z[e] = q;
+        acc += x[e] * q;
+    }
+    __shared__ double red[kBlock / 64];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+        for (int w = 0; w < kBlock / 64; ++w) t += red[w];
+        partial[blockIdx.x] = t;
+    }
+}
+
 // w = alpha z + beta q with q = (a - b) / e, e = eps[0] or 2 eps[0] exactly as k_jvp_diff forms it; b == NULL: a holds q already (a lazy
 // launcher's quotient; a may be w).  mode 3: nothing once the cycle is over; 4: nothing once the solve is; words == NULL: unguarded.
 template <bool VEC>
@@ -118,9 +192,10 @@ __global__ void __launch_bounds__(kBlock) k_jf_close(const double *a, const doub
     }
 }
 
-// the start of a solve: r = b, y = 0, ||b||^2, and the diagonal's check -- k_cs_init<0> with the caller's d in place of the pattern's
+// the start of a solve: r = b, y = 0, ||b||^2, and the diagonal's check -- k_cs_init<0> with the caller's d in place of the pattern's;
+// fwords: the words of a lent factorisation (NULL: none), whose flag bit 1 ends the solve here as a bad d_e does
 __global__ void __launch_bounds__(kBlock) k_jf_init(int N, const double *__restrict__ d, const double *__restrict__ b, double *__restrict__ r,
-                                                    double *__restrict__ y, double rtol, double *scal, int *words, double *part)
+                                                    double *__restrict__ y, double rtol, double *scal, int *words, double *part, const int *fwords)
 {
     __shared__ double s_w[kBlock / 64];
     const int i0 = blockIdx.x * kCsVecTile + threadIdx.x;
@@ -134,6 +209,7 @@ __global__ void __launch_bounds__(kBlock) k_jf_init(int N, const double *__restr
         r[i] = bi; y[i] = 0.0;
         mine[0] += bi * bi;
     }
+    if (fwords && threadIdx.x == 0 && (cs_word(fwords, W_FLAGS) & 2)) bad = true;
     if (bad) atomicOr(words + W_FLAGS, 2);
     if (cs_finish<1>(mine, part, words, tot, s_w) && threadIdx.x == 0) {
         scal[S_BNORM2] = tot[0];
@@ -280,7 +356,23 @@ int fd_jfnk_solver_set_lazy_f(fd_jfnk_solver *s, fd_f_launch_lazy_jvp lazy, int 
 int fd_jfnk_solver_set_diagonal(fd_jfnk_solver *s, const void *d_dev)
 {
     FD_REQUIRE(s != nullptr, FD_ERR_ARG, "solver is NULL");
+    FD_REQUIRE(d_dev == nullptr || s->pc == nullptr, FD_ERR_ARG, "a csc preconditioner is set: clear it first (fd_jfnk_solver_set_csc_preconditioner(solver, NULL))");
     s->d_diag = (const double *)d_dev;
+    return FD_OK;
+}
+
+// the right preconditioner M of a lent sparse consumer: whatever its last fd_csc_solver_factor_async built, reused by every solve
+int fd_jfnk_solver_set_csc_preconditioner(fd_jfnk_solver *s, fd_csc_solver *pc)
+{
+    FD_REQUIRE(s != nullptr, FD_ERR_ARG, "solver is NULL");
+    if (pc) {
+        FD_REQUIRE(s->d_diag == nullptr, FD_ERR_ARG, "a diagonal is set: clear it first (fd_jfnk_solver_set_diagonal(solver, NULL))");
+        FD_REQUIRE(pc->elem_bytes == (int)sizeof(double), FD_ERR_ARG, "the preconditioner must be a Float64 fd_csc_solver (this one holds %d-byte elements)",
+                   pc->elem_bytes);
+        FD_REQUIRE(pc->ctx == s->ctx, FD_ERR_ARG, "the preconditioner lives on another context");
+        FD_REQUIRE(pc->L.N == s->N, FD_ERR_SHAPE, "the preconditioner has N = %lld, the solver N = %lld", (long long)pc->L.N, (long long)s->N);
+    }
+    s->pc = pc;
     return FD_OK;
 }
 
@@ -303,13 +395,20 @@ int fd_jfnk_solve_async(fd_jfnk_solver *s, double alpha, double beta, fd_f_launc
 {
     FD_REQUIRE(s && f && x && b && y, FD_ERR_ARG, "NULL argument");
     FD_REQUIRE(y != x, FD_ERR_ARG, "y must not be x");
+    fd_csc_solver *pc = s->pc;
+    if (pc) {      // (before anything is enqueued)
+        const int rv = csc_factor_valid(pc);
+        if (rv != FD_OK) return rv;
+    }
     FD_HIP_CHECK(hipSetDevice(s->ctx->device));
     hipStream_t st = s->ctx->stream;
     CscSolveState &S = s->S;
     const int N = (int)s->N;
     const size_t ld = (size_t)s->ld;
     const unsigned gv = cs_tiles(N, kCsVecTile);
-    const double *xd = (const double *)x, *d = s->d_diag;
+    // a lent factorisation: the Jacobi kind IS the diagonal path on the factored diagonal; blocks / ILU go through the lender's applies
+    const bool pc_blocks = pc && pc->fact_kind != FD_CSC_PRECOND_JACOBI, pc_bjac = pc && pc->fact_kind == FD_CSC_PRECOND_BLOCK_JACOBI;
+    const double *xd = (const double *)x, *d = pc ? (pc_blocks ? nullptr : pc->d_fdiag) : s->d_diag;
     CsVecs V = {};
     V.r = s->d_vec; V.p = s->d_vec + ld; V.v = s->d_vec + 2 * ld; V.s = s->d_vec + 3 * ld; V.y = s->d_vec + 4 * ld; V.d = const_cast<double *>(d);
     const CsGm G = gm_view(s->d_gm, (size_t)N, s->m);
@@ -320,12 +419,24 @@ int fd_jfnk_solve_async(fd_jfnk_solver *s, double alpha, double beta, fd_f_launc
         const int rb = jf_base(s, f, fctx, xd, (const double *)f_in, &fin, &own);
         if (rb != FD_OK) return rb;
         FD_HIP_CHECK(hipMemsetAsync(S.d_words, 0, sizeof(int) * W_NWORDS, st));
-        hipLaunchKernelGGL(k_jf_init, dim3(gv), dim3(kBlock), 0, st, N, d, (const double *)b, V.r, V.y, S.rtol, S.d_scal, S.d_words, S.d_part);
-        const bool fused = d != nullptr && !(s->jp->small_ok && s->N <= kSmallN);
+        hipLaunchKernelGGL(k_jf_init, dim3(gv), dim3(kBlock), 0, st, N, d, (const double *)b, V.r, V.y, S.rtol, S.d_scal, S.d_words, S.d_part,
+                           pc ? (const int *)pc->d_fwords : (const int *)nullptr);
+        const bool fused = (d != nullptr || pc_bjac) && !(s->jp->small_ok && s->N <= kSmallN);
         bool partials = false;
         return csc_gmres_iterate(st, S, N, G, (const double *)b, V,
             [&](const double *vj, double *z, const double **zj) {      // z = v_j / d, or v_j itself
                 partials = false;
+                if (pc_blocks) {
+                    *zj = z;
+                    if (!pc_bjac || !fused) { csc_factor_apply(pc, 1, vj, z, words); return FD_OK; }
+                    const bool paired = ((((uintptr_t)xd) | ((uintptr_t)z)) & kPairMask) == 0;
+                    fd_pick<false, true>(paired, [&](auto PAIRED) {
+                        hipLaunchKernelGGL(k_jf_open_blocks<PAIRED()>, dim3(s->jp->nparts), dim3(kBlock), 0, st, xd, vj, (const double *)pc->d_minv, pc->fact_bs,
+                                           (int64_t)N, z, s->jp->d_partial, words);
+                    });
+                    partials = true;
+                    return FD_OK;
+                }
                 if (!d) { *zj = vj; return FD_OK; }
                 *zj = z;
                 if (!fused) {
@@ -347,8 +458,12 @@ int fd_jfnk_solve_async(fd_jfnk_solver *s, double alpha, double beta, fd_f_launc
                 partials = false;
                 return jf_operator(s, alpha, beta, f, fctx, xd, fin, own, v, w, hp, words, mode);
             },
-            [&](double *, double *) {      // y = y + u / d, or y = y + u
-                if (d) hipLaunchKernelGGL(k_gm_combine<1>, dim3(gv), dim3(kBlock), 0, st, N, G, d, V.y, words);
+            [&](double *u, double *z) {      // y = y + u / d, or y = y + u; blocks / ILU: the sparse consumer's three launches
+                if (pc_blocks) {
+                    hipLaunchKernelGGL(k_gm_combine<0>, dim3(gv), dim3(kBlock), 0, st, N, G, d, u, words);
+                    csc_factor_apply(pc, 0, u, z, words);
+                    hipLaunchKernelGGL(k_gm_yadd, dim3(gv), dim3(kBlock), 0, st, N, V.y, (const double *)z, words);
+                } else if (d) hipLaunchKernelGGL(k_gm_combine<1>, dim3(gv), dim3(kBlock), 0, st, N, G, d, V.y, words);
                 else hipLaunchKernelGGL(k_gm_combine<2>, dim3(gv), dim3(kBlock), 0, st, N, G, d, V.y, words);
                 return FD_OK;
             });

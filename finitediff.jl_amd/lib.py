@@ -86,10 +86,11 @@ EXPORTS = (
     "fd_blocktridiag_solve_async",
     "fd_csc_solver_create", "fd_csc_solver_destroy", "fd_csc_matvec_async", "fd_csc_solver_set_options", "fd_csc_solver_set_policy", "fd_csc_solve_async", "fd_csc_solver_status", "fd_csc_solver_row_lists",
     "fd_csc_solver_set_preconditioner", "fd_csc_solver_block_inverses", "fd_csc_solver_set_block_ilu", "fd_csc_solver_ilu_levels", "fd_csc_solver_ilu_factors", "fd_csc_solver_set_method", "fd_csc_solver_gmres_basis",
+    "fd_csc_solver_factor_async", "fd_csc_solver_apply_async", "fd_csc_solver_factor_status",
     "fd_csc_lsq_create", "fd_csc_lsq_destroy", "fd_csc_lsq_matvec_async", "fd_csc_lsq_set_options", "fd_csc_lsq_set_policy", "fd_csc_lsq_solve_async", "fd_csc_lsq_status", "fd_csc_lsq_row_lists", "fd_csc_lsq_long_columns",
     "fd_csc_tr_create", "fd_csc_tr_destroy", "fd_csc_tr_set_options", "fd_csc_tr_set_policy", "fd_csc_tr_matvec_async", "fd_csc_tr_step_async", "fd_csc_tr_status",
     "fd_jfnk_solver_create", "fd_jfnk_solver_destroy", "fd_jfnk_solver_set_options", "fd_jfnk_solver_set_policy", "fd_jfnk_solver_set_steps", "fd_jfnk_solver_set_lazy_f",
-    "fd_jfnk_solver_set_diagonal", "fd_jfnk_apply_async", "fd_jfnk_solve_async", "fd_jfnk_solver_status", "fd_jfnk_solver_counts", "fd_jfnk_solver_basis",
+    "fd_jfnk_solver_set_diagonal", "fd_jfnk_solver_set_csc_preconditioner", "fd_jfnk_apply_async", "fd_jfnk_solve_async", "fd_jfnk_solver_status", "fd_jfnk_solver_counts", "fd_jfnk_solver_basis",
     "fd_objective_compile", "fd_objective_destroy", "fd_objective_counts", "fd_hess_plan_create", "fd_hess_plan_destroy",
     "fd_hess_plan_info", "fd_hess_plan_pattern", "fd_hessian_async", "fd_hessian", "fd_gradient_async", "fd_gradient",
 )
@@ -113,6 +114,7 @@ TYPED = (
     "fd_blocktridiag_solve_async",
     "fd_csc_solver_create", "fd_csc_solver_destroy", "fd_csc_matvec_async", "fd_csc_solver_set_options", "fd_csc_solver_set_policy", "fd_csc_solve_async", "fd_csc_solver_status", "fd_csc_solver_row_lists",
     "fd_csc_solver_set_preconditioner", "fd_csc_solver_block_inverses", "fd_csc_solver_set_block_ilu", "fd_csc_solver_ilu_levels", "fd_csc_solver_ilu_factors", "fd_csc_solver_set_method", "fd_csc_solver_gmres_basis",
+    "fd_csc_solver_factor_async", "fd_csc_solver_apply_async", "fd_csc_solver_factor_status",
     "fd_csc_lsq_create", "fd_csc_lsq_destroy", "fd_csc_lsq_matvec_async", "fd_csc_lsq_set_options", "fd_csc_lsq_set_policy", "fd_csc_lsq_solve_async", "fd_csc_lsq_status", "fd_csc_lsq_row_lists", "fd_csc_lsq_long_columns",
 )
 EXPORTS = EXPORTS + tuple("fd32_" + n[3:] for n in TYPED)
@@ -301,6 +303,9 @@ def load():
     L.fd_csc_solver_ilu_factors.argtypes = [vp, pp, pp, C.POINTER(i64), C.POINTER(i32)]
     L.fd_csc_solver_set_method.argtypes = [vp, i32, i32]
     L.fd_csc_solver_gmres_basis.argtypes = [vp, pp, pp, C.POINTER(i32), C.POINTER(i32)]
+    L.fd_csc_solver_factor_async.argtypes = [vp, dbl, dbl, vp]
+    L.fd_csc_solver_apply_async.argtypes = [vp, vp, vp]
+    L.fd_csc_solver_factor_status.argtypes = [vp, C.POINTER(i32)]
     L.fd_csc_lsq_create.argtypes = [vp, i64, i64, vp, vp, i32, i32, i32, pp]
     L.fd_csc_lsq_destroy.argtypes = [vp]
     L.fd_csc_lsq_matvec_async.argtypes = [vp, vp, vp, vp, i32]
@@ -324,6 +329,7 @@ def load():
     L.fd_jfnk_solver_set_steps.argtypes = [vp, dbl, dbl, dbl]
     L.fd_jfnk_solver_set_lazy_f.argtypes = [vp, F_LAUNCH_LAZY_JVP, i32]
     L.fd_jfnk_solver_set_diagonal.argtypes = [vp, vp]
+    L.fd_jfnk_solver_set_csc_preconditioner.argtypes = [vp, vp]
     L.fd_jfnk_apply_async.argtypes = [vp, dbl, dbl, F_LAUNCH, vp, vp, vp, vp, vp]
     L.fd_jfnk_solve_async.argtypes = [vp, dbl, dbl, F_LAUNCH, vp, vp, vp, vp, vp]
     L.fd_jfnk_solver_status.argtypes = [vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(dbl), C.POINTER(dbl)]

@@ -794,6 +794,21 @@ int fd_banded_solve_async(fd_banded_solver *solver, double alpha, double beta, c
  *                         columns as Arnoldi gave them (column j at H + j * (restart + 1)), that solve's restart, and the columns the
  *                         last cycle completed (v_0 .. v_len-1 and columns 0 .. len-1 are valid; reading it synchronises).  Any out
  *                         pointer may be NULL.  The layout may change with the solver.
+ *   fd_csc_solver_factor_async  THE FACTORISATION AS AN OPERATION OF ITS OWN: M for alpha*I + beta*J from whichever preconditioner is
+ *                         selected, by the launches and in the arithmetic of a solve -- Jacobi: the N diagonals alpha + beta*J_ii (alpha
+ *                         where the diagonal is not stored) into storage of the factorisation's own; block Jacobi: the inverses
+ *                         (fd_csc_solver_block_inverses reads them); block ILU(0): the factors (fd_csc_solver_ilu_factors) -- so the
+ *                         bits are those a solve with the same (alpha, beta, nzval) leaves.  A pivot that is zero or not finite raises
+ *                         bit 1 of fd_csc_solver_factor_status, in words of the factorisation's own that no solve clears.
+ *   fd_csc_solver_apply_async   out = M^-1 x with that factorisation.  x and out are N DOUBLES in either element build (the consumer's
+ *                         arithmetic is Float64 throughout); out must not be x (FD_ERR_ARG).  Unguarded: it runs whatever any solve's
+ *                         status says.  Before any fd_csc_solver_factor_async: FD_ERR_UNSUPPORTED.
+ *                         THE GENERATION RULE: the handle counts what invalidates a factorisation -- fd_csc_solve_async (it factors
+ *                         into the same buffers), fd_csc_solver_set_preconditioner, fd_csc_solver_set_block_ilu, and
+ *                         fd_csc_solver_factor_async itself.  fd_csc_solver_apply_async after any of the first three that came later
+ *                         than the last factor is FD_ERR_STALE with a message, and nothing is enqueued: factor again.
+ *   fd_csc_solver_factor_status  synchronises; flags bit 1: a pivot of the last factorisation was zero or not finite
+ *                         (FD_ERR_UNSUPPORTED before the first factor).
  * Everything is enqueued on the context's stream; fd_csc_solver_create and fd_csc_solver_status synchronise it.  Without a device
  * fd_csc_solver_create is FD_ERR_NODEVICE. */
 #define FD_CSC_METHOD_BICGSTAB       0   /* the default */
@@ -820,6 +835,9 @@ int fd_csc_solver_ilu_levels(fd_csc_solver *solver, const void **lev_fwd_dev, co
 int fd_csc_solver_ilu_factors(fd_csc_solver *solver, const void **lu_dev, const void **u_dev, int64_t *nblocks, int *block_size);
 int fd_csc_solver_set_method(fd_csc_solver *solver, int method, int restart);
 int fd_csc_solver_gmres_basis(fd_csc_solver *solver, const void **V_dev, const void **H_dev, int *restart, int *last_cycle_len);
+int fd_csc_solver_factor_async(fd_csc_solver *solver, double alpha, double beta, const void *nzval);
+int fd_csc_solver_apply_async(fd_csc_solver *solver, const void *x, void *out);
+int fd_csc_solver_factor_status(fd_csc_solver *solver, int *flags);
 
 /* ---- the MATRIX-FREE consumer: (alpha*I + beta*J(x)) y = b by restarted GMRES on the finite-difference JVP, J never stored --------------
  * For an f! whose Jacobian pattern is dense, unknown or too wide to colour: the operator is  A(x) z = alpha*z + beta*q,  q what
@@ -835,7 +853,20 @@ int fd_csc_solver_gmres_basis(fd_csc_solver *solver, const void **V_dev, const v
  *   fd_jfnk_solver_set_steps   relstep, absstep, dir as fd_jvp_async takes them (relstep <= 0: the default; absstep < 0: relstep).
  *   fd_jfnk_solver_set_lazy_f  the lazy JVP launcher of f! and its FD_LAZY_JVP_CAP_* bits; NULL clears (caps must be 0 then).
  *   fd_jfnk_solver_set_diagonal  N doubles d, read by every solve: the right preconditioner M = diag(d) (z = v_j / d, y += u / d).  NULL
- *                         (the default): none.  A d_e that is zero or not finite is a breakdown before the first step.
+ *                         (the default): none.  A d_e that is zero or not finite is a breakdown before the first step.  FD_ERR_ARG
+ *                         (non-NULL) while a csc preconditioner is set: clear that one first.
+ *   fd_jfnk_solver_set_csc_preconditioner  PRECONDITIONED BY A STORED J: the right preconditioner M is the factorisation a sparse
+ *                         consumer holds (fd_csc_solver_factor_async: Jacobi, block Jacobi or block ILU(0) of alpha0*I + beta0*J(x0) as
+ *                         a CSC plan stored it).  pc must be a Float64 fd_csc_solver on the same fd_ctx (else FD_ERR_ARG) with the same
+ *                         N (else FD_ERR_SHAPE); FD_ERR_ARG while a diagonal is set; NULL clears.  THE HANDLE IS LENT, not owned: the
+ *                         caller keeps it alive while it is set, and destroys it.  THE FACTORISATION IS LAGGED BY DESIGN: it is whatever
+ *                         the caller last passed to fd_csc_solver_factor_async, and every following fd_jfnk_solve_async reuses it at
+ *                         any x, alpha, beta -- the operator is the current one, only M is old.  Each solve checks the generation
+ *                         rule of fd_csc_solver_apply_async before it enqueues anything: no factorisation on pc is FD_ERR_UNSUPPORTED,
+ *                         one that a later solve or setter of pc invalidated is FD_ERR_STALE.  A factorisation whose status has bit 1
+ *                         ends every such solve at once: flags bit 1, no iteration, y NaN unless the policy keeps the iterate.  The
+ *                         vectors stay Float64: z = M^-1 v_j by the lender's own kernels (block Jacobi above 16384 elements: one
+ *                         kernel that also leaves the JVP's dot), y += M^-1 (V t) at a cycle's end.
  *   fd_jfnk_apply_async   w = A(x) z; w must not be z or x.  The diagonal plays no part.
  *   fd_jfnk_solve_async   GMRES(restart) exactly as fd_csc_solver_set_method describes it (y0 = 0, CGS2, the estimate, the restart through the
  *                         explicit r = b - A(x) y, max_iterations caps the Arnoldi steps, b = 0: y = 0 with 0 iterations, ||b||^2 not
@@ -856,6 +887,7 @@ int fd_jfnk_solver_set_policy(fd_jfnk_solver *solver, int keep_unconverged);
 int fd_jfnk_solver_set_steps(fd_jfnk_solver *solver, double relstep, double absstep, double dir);
 int fd_jfnk_solver_set_lazy_f(fd_jfnk_solver *solver, fd_f_launch_lazy_jvp lazy, int caps);
 int fd_jfnk_solver_set_diagonal(fd_jfnk_solver *solver, const void *d_dev);
+int fd_jfnk_solver_set_csc_preconditioner(fd_jfnk_solver *solver, fd_csc_solver *pc);
 int fd_jfnk_apply_async(fd_jfnk_solver *solver, double alpha, double beta, fd_f_launch f, void *fctx, const void *x, const void *f_in,
                         const void *z, void *w);
 int fd_jfnk_solve_async(fd_jfnk_solver *solver, double alpha, double beta, fd_f_launch f, void *fctx, const void *x, const void *f_in,
@@ -1165,6 +1197,9 @@ int fd32_csc_solver_ilu_levels(fd32_csc_solver *solver, const void **lev_fwd_dev
 int fd32_csc_solver_ilu_factors(fd32_csc_solver *solver, const void **lu_dev, const void **u_dev, int64_t *nblocks, int *block_size);
 int fd32_csc_solver_set_method(fd32_csc_solver *solver, int method, int restart);
 int fd32_csc_solver_gmres_basis(fd32_csc_solver *solver, const void **V_dev, const void **H_dev, int *restart, int *last_cycle_len);
+int fd32_csc_solver_factor_async(fd32_csc_solver *solver, double alpha, double beta, const void *nzval);
+int fd32_csc_solver_apply_async(fd32_csc_solver *solver, const void *x, void *out);      /* x, out: N doubles */
+int fd32_csc_solver_factor_status(fd32_csc_solver *solver, int *flags);
 typedef struct fd32_csc_lsq fd32_csc_lsq;
 int fd32_csc_lsq_create(fd_ctx *ctx, int64_t M, int64_t N, const void *colptr, const void *rowval, int idx_bytes, int idx_base, int idx_kind,
                       fd32_csc_lsq **out);

@@ -9,12 +9,12 @@ raises if the HIP library or a GPU is missing.
 from . import patterns  # noqa: F401  (numpy-only helpers; safe without a GPU)
 from . import lib  # noqa: F401  (ctypes binding; loads libfdjac.so on first use)
 from .api import (BandedBlockBandedMatrix, BandedMatrix, BlockBandedMatrix, Bidiagonal, BuiltinF, Comm, Context, DevicePatternCSC, Diagonal, JacobianCache, JitF, JitTerms, BitcodeF, TrackedCSC, TrackedVector, P2P, Plan, SymTridiagonal,  # noqa: F401
-                  SparseMatrixCSC, TorchF, Tridiagonal, TridiagSolver, BandedSolver, CscSolver, CscLeastSquares, CscTrustRegion, BlockTridiagSolver, JfnkSolver, JVPCache, ObjectiveF, HessianCache, GradientCache, default_relstep, finite_difference_jacobian,
+                  SparseMatrixCSC, TorchF, Tridiagonal, TridiagSolver, BandedSolver, CscSolver, CscLeastSquares, CscTrustRegion, BlockTridiagSolver, JfnkSolver, JfTrustRegion, JVPCache, ObjectiveF, HessianCache, GradientCache, default_relstep, finite_difference_jacobian,
                   finite_difference_jacobian_b,
                   finite_difference_jvp_b, finite_difference_hessian, finite_difference_hessian_b, finite_difference_gradient,
                   finite_difference_gradient_b, make_plan, make_plan_csc_device, matrix_colors, matrix_colors_device, check_colors_device)
 
 __all__ = ["patterns", "lib", "BandedBlockBandedMatrix", "BandedMatrix", "BlockBandedMatrix", "Bidiagonal", "BuiltinF", "Comm", "Context", "DevicePatternCSC", "Diagonal", "JacobianCache", "JitF", "JitTerms", "BitcodeF", "TrackedCSC", "TrackedVector", "P2P", "Plan", "SymTridiagonal",
-           "SparseMatrixCSC", "TorchF", "Tridiagonal", "TridiagSolver", "BandedSolver", "CscSolver", "CscLeastSquares", "CscTrustRegion", "BlockTridiagSolver", "JfnkSolver", "JVPCache", "ObjectiveF", "HessianCache", "GradientCache", "default_relstep", "finite_difference_jacobian", "finite_difference_jacobian_b",
+           "SparseMatrixCSC", "TorchF", "Tridiagonal", "TridiagSolver", "BandedSolver", "CscSolver", "CscLeastSquares", "CscTrustRegion", "BlockTridiagSolver", "JfnkSolver", "JfTrustRegion", "JVPCache", "ObjectiveF", "HessianCache", "GradientCache", "default_relstep", "finite_difference_jacobian", "finite_difference_jacobian_b",
            "finite_difference_jvp_b", "finite_difference_hessian", "finite_difference_hessian_b",
            "finite_difference_gradient", "finite_difference_gradient_b", "make_plan", "make_plan_csc_device", "matrix_colors", "matrix_colors_device", "check_colors_device"]

@@ -980,6 +980,99 @@ class JfnkSolver:
         return V, H, k.value
 
 
+class JfTrustRegion:
+    """fd_jftr: the matrix-free trust-region consumer.  ``step`` enqueues the Steihaug-Toint truncated-CG solution of
+    min g.y + 1/2 y.B y, ||y||_W <= radius, B = lam*I + beta*J(x), where J(x) v is the finite-difference JVP of the gradient ``f`` at ``x``
+    -- the Hessian is never stored, so f needs no pattern and no colouring -- and ``apply`` enqueues w = lam*v + beta*J(x) v.  W = I, or
+    diag(m) after ``set_diagonal(m)`` (m > 0, which also preconditions).  Float64, square f, device arrays; ``f`` as ``JfnkSolver`` takes
+    it.  B is symmetric only up to the quotient's noise.  A step that runs out of iterations (``status()`` flags bit 0) or breaks down
+    (bit 1) fills y and r_out with NaN unless ``set_policy(True)``; a step that ends on the boundary is a success."""
+
+    def __init__(self, N, fdtype="forward", ctx=None):
+        self.ctx = ctx or Context.default()
+        self.N, self.fdtype = int(N), _norm_fdtype(fdtype)
+        self.dtype = np.dtype(np.float64)
+        h = C.c_void_p()
+        _l.check(self.ctx.L.fd_jftr_create(self.ctx.handle, self.N, _l.FDTYPES[self.fdtype], C.byref(h)))
+        self.handle = h
+        self._fin = weakref.finalize(self, self.ctx.L.fd_jftr_destroy, h)
+        self._lazy_keep = self._diag_keep = None
+
+    def _dev(self, a, what):
+        if a is None:
+            return None
+        p, k, _keep = _ptr(a, what, self.dtype)
+        if k != _l.DEVICE:
+            raise ValueError("the matrix-free trust-region consumer takes device arrays")
+        if int(np.prod(a.shape)) != self.N:
+            raise ValueError("%s must hold N = %d elements" % (what, self.N))      # DimensionMismatch
+        return p
+
+    _launcher = staticmethod(JfnkSolver._launcher)
+
+    def set_options(self, rtol=1e-10, max_iterations=500):
+        _l.check(self.ctx.L.fd_jftr_set_options(self.handle, float(rtol), int(max_iterations)))
+
+    def set_policy(self, keep_unconverged):
+        _l.check(self.ctx.L.fd_jftr_set_policy(self.handle, 1 if keep_unconverged else 0))
+
+    def set_steps(self, relstep=None, absstep=None, dir=True):
+        """The JVP's steps as ``finite_difference_jvp_b`` takes them (None: the defaults)."""
+        _l.check(self.ctx.L.fd_jftr_set_steps(self.handle, -1.0 if relstep is None else float(relstep),
+                                              -1.0 if absstep is None else float(absstep), float(dir)))
+
+    def set_diagonal(self, m):
+        """N doubles on the device, m > 0: W = diag(m), norm and preconditioner of every step (the array is kept alive); None: W = I."""
+        self._diag_keep = m
+        _l.check(self.ctx.L.fd_jftr_set_diagonal(self.handle, self._dev(m, "m")))
+
+    def set_lazy(self, f=None, quotient=True):
+        """Install ``f``'s lazy JVP launcher, as ``JfnkSolver.set_lazy``."""
+        if f is not None and not hasattr(f, "lazy_jvp_fn") and not isinstance(f, _l.F_LAUNCH_LAZY_JVP):
+            f = None
+        if isinstance(f, _l.F_LAUNCH_LAZY_JVP):
+            lz, caps = f, int(quotient)
+        else:
+            lz = getattr(f, "lazy_jvp_fn", None) if f is not None else None
+            caps = int(getattr(f, "lazy_jvp_caps", 0)) if (lz is not None and quotient) else 0
+        self._lazy_keep = lz            # (the ctypes function object must outlive the calls)
+        _l.check(self.ctx.L.fd_jftr_set_lazy_f(self.handle, lz if lz is not None else _l.F_LAUNCH_LAZY_JVP(), caps if lz is not None else 0))
+
+    def _checked(self, f, rc):
+        err = getattr(f, "error", None)
+        if err is not None:
+            f.error = None
+            raise err
+        _l.check(rc)
+
+    def apply(self, f, x, v, w, lam=0.0, beta=1.0, f_in=None):
+        """Enqueue w = lam*v + beta*J(x) v (fd_jftr_apply_async)."""
+        fn, fctx = self._launcher(f)
+        self._checked(f, self.ctx.L.fd_jftr_apply_async(self.handle, float(lam), float(beta), fn, fctx, self._dev(x, "x"), self._dev(f_in, "f_in"),
+                                                        self._dev(v, "v"), self._dev(w, "w")))
+
+    def step(self, f, x, g, y, radius, lam=0.0, beta=1.0, f_in=None, r_out=None):
+        """Enqueue the trust-region step into y (fd_jftr_step_async); ``radius`` > 0 or ``float("inf")``; ``g`` may be ``f_in``;
+        ``r_out`` (N elements) receives the recurred model gradient g + B y."""
+        fn, fctx = self._launcher(f)
+        self._checked(f, self.ctx.L.fd_jftr_step_async(self.handle, float(lam), float(beta), float(radius), fn, fctx, self._dev(x, "x"),
+                                                       self._dev(f_in, "f_in"), self._dev(g, "g"), self._dev(y, "y"), self._dev(r_out, "r_out")))
+
+    def status(self):
+        """Synchronises.  The record of ``CscTrustRegion.status`` with B in place of H + lam*I."""
+        f, e, it = C.c_int(), C.c_int(), C.c_int64()
+        r, gn, sn, pr = C.c_double(), C.c_double(), C.c_double(), C.c_double()
+        _l.check(self.ctx.L.fd_jftr_status(self.handle, C.byref(f), C.byref(e), C.byref(it), C.byref(r), C.byref(gn), C.byref(sn), C.byref(pr)))
+        return {"flags": f.value, "exit": e.value, "iterations": it.value, "resid": r.value, "g_norm": gn.value, "step_norm": sn.value,
+                "pred": pr.value}
+
+    def counts(self):
+        """Synchronises.  (``apply`` calls plus the products that the steps used, base evaluations f(x)) since creation."""
+        a, b = C.c_int64(), C.c_int64()
+        _l.check(self.ctx.L.fd_jftr_counts(self.handle, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+
 class BlockTridiagSolver:
     """fd_blocktridiag_solver: (alpha*I + beta*J) y = b on the device for a block-tridiagonal J of ``nblk`` dense ``b x b`` blocks
     (b <= 32) in ``BlockBandedMatrix`` data (block bandwidths (1, 1), uniform block sizes) -- the storage a block-banded plan fills

@@ -310,3 +310,5 @@ int fd_csc_tr_status(fd_csc_tr *s, int *flags_out, int *exit_out, int64_t *itera
     if (pred_out) *pred_out = sc[TR_PRED];
     return FD_OK;
 }
+
+#include "fdjac_jftr.hip"      // the matrix-free trust-region consumer (fd_jftr_*): this file's recurrence on the finite-difference JVP

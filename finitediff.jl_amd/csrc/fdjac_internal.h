@@ -308,7 +308,8 @@ __device__ __forceinline__ int eps_rescale_exp(double t, double relstep, double 
 //   FDJAC_WIN_PERIODIC / FDJAC_TILE_ORDER (which decompression kernel a hand-over plan compiles to), FDJAC_COLOR_BATCH (rounds per
 //   read-back of the device colouring, 1..8) / FDJAC_COLOR_TAIL (0: no one-workgroup tail) / FDJAC_COLOR_STATS (1: one line of
 //   round and launch counts on stderr per fd_color_columns_device call), FDJAC_CSC_WINDOW (0: the sparse consumer's row product reads v
-//   from memory only, no LDS window) / FDJAC_CSC_BATCH (iterations per record read back of fd_csc_solve_async, fd_csc_lsq_solve_async and fd_csc_tr_step_async, 1..64).
+//   from memory only, no LDS window) / FDJAC_CSC_BATCH (iterations per record read back of fd_csc_solve_async, fd_csc_lsq_solve_async and fd_csc_tr_step_async, 1..64),
+//   FDJAC_JFTR_FUSE (0: fd_jftr_step_async runs k_tr_p and the JVP's own dot above kSmallN instead of k_jt_p; read at fd_jftr_create).
 // They are read through this ONE function, and only in a process that opted in with FDJAC_TEST_SWITCHES=1 (tests/conftest.py sets it):
 // a production process ignores them altogether -- there every choice is the plan builder's.  (Operational variables are not gated:
 // FDJAC_RCCL_LIB, FDJAC_HIPRTC_LIB, FDJAC_P2P_TIMEOUT_MS, FDJAC_PLAN_THREADS, FDJAC_PLAN_TIMING.)

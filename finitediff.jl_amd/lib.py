@@ -91,6 +91,8 @@ EXPORTS = (
     "fd_csc_tr_create", "fd_csc_tr_destroy", "fd_csc_tr_set_options", "fd_csc_tr_set_policy", "fd_csc_tr_matvec_async", "fd_csc_tr_step_async", "fd_csc_tr_status",
     "fd_jfnk_solver_create", "fd_jfnk_solver_destroy", "fd_jfnk_solver_set_options", "fd_jfnk_solver_set_policy", "fd_jfnk_solver_set_steps", "fd_jfnk_solver_set_lazy_f",
     "fd_jfnk_solver_set_diagonal", "fd_jfnk_solver_set_csc_preconditioner", "fd_jfnk_apply_async", "fd_jfnk_solve_async", "fd_jfnk_solver_status", "fd_jfnk_solver_counts", "fd_jfnk_solver_basis",
+    "fd_jftr_create", "fd_jftr_destroy", "fd_jftr_set_options", "fd_jftr_set_policy", "fd_jftr_set_steps", "fd_jftr_set_lazy_f", "fd_jftr_set_diagonal",
+    "fd_jftr_apply_async", "fd_jftr_step_async", "fd_jftr_status", "fd_jftr_counts",
     "fd_objective_compile", "fd_objective_destroy", "fd_objective_counts", "fd_hess_plan_create", "fd_hess_plan_destroy",
     "fd_hess_plan_info", "fd_hess_plan_pattern", "fd_hessian_async", "fd_hessian", "fd_gradient_async", "fd_gradient",
 )
@@ -335,6 +337,17 @@ def load():
     L.fd_jfnk_solver_status.argtypes = [vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(dbl), C.POINTER(dbl)]
     L.fd_jfnk_solver_counts.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     L.fd_jfnk_solver_basis.argtypes = [vp, pp, pp, C.POINTER(i32), C.POINTER(i32)]
+    L.fd_jftr_create.argtypes = [vp, i64, i32, pp]
+    L.fd_jftr_destroy.argtypes = [vp]
+    L.fd_jftr_set_options.argtypes = [vp, dbl, i32]
+    L.fd_jftr_set_policy.argtypes = [vp, i32]
+    L.fd_jftr_set_steps.argtypes = [vp, dbl, dbl, dbl]
+    L.fd_jftr_set_lazy_f.argtypes = [vp, F_LAUNCH_LAZY_JVP, i32]
+    L.fd_jftr_set_diagonal.argtypes = [vp, vp]
+    L.fd_jftr_apply_async.argtypes = [vp, dbl, dbl, F_LAUNCH, vp, vp, vp, vp, vp]
+    L.fd_jftr_step_async.argtypes = [vp, dbl, dbl, dbl, F_LAUNCH, vp, vp, vp, vp, vp, vp]
+    L.fd_jftr_status.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64), C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl)]
+    L.fd_jftr_counts.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     L.fd_tridiag_solver_create.argtypes = [vp, i64, i64, i64, i32, pp]
     L.fd_tridiag_solver_destroy.argtypes = [vp]
     L.fd_tridiag_solver_status.argtypes = [vp, C.POINTER(i32)]

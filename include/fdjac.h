@@ -977,6 +977,57 @@ int fd_csc_tr_step_async(fd_csc_tr *tr, double lambda, double radius, int norm_k
 int fd_csc_tr_status(fd_csc_tr *tr, int *flags_out, int *exit_out, int64_t *iterations_out, double *resid_out, double *g_norm_out,
                      double *step_norm_out, double *pred_out);
 
+/* ---- the MATRIX-FREE TRUST-REGION consumer: the Steihaug-Toint step on the finite-difference JVP of a gradient, H never stored ---------
+ * For an objective whose gradient is an ordinary vector f! (any launcher route) and whose Hessian is dense, unknown or too wide to
+ * colour:  min q(y) = g.y + 1/2 y.B y  subject to  ||y||_W <= radius,  B = lambda*I + beta*J(x),  J(x) v what fd_jvp_async returns for
+ * (x, v) with the consumer's steps and fdtype -- on whichever of its routes, the same bits.  lambda >= 0 and finite; beta finite and not
+ * 0 (beta = -1 turns a negative-definite J into a positive-definite B).  W = I, or diag(m) with the caller's m > 0 (fd_jftr_set_diagonal),
+ * which also preconditions the iteration.  f is square (M = N); Float64 only (no fd32_ twin); x, f_in, g, v, w, y, r_out and m are DEVICE
+ * arrays of N doubles.  In the forward arm f(x) is evaluated once per call (one launch of f!: a "base evaluation") when f_in is NULL; a
+ * given f_in is taken to be f(x); the central arm ignores it.  DESIGN.md 4.13 has the launches; tests/jftr_model.py composes the models.
+ * B IS SYMMETRIC ONLY UP TO THE QUOTIENT'S NOISE (about eps / eps_fd relative): the recurred r_out and pred are exact for the
+ * recurrence, not for the true Hessian.  No warm start (y0 = 0), no graph capture.
+ *   fd_jftr_create        N in 1 .. 2^31 - 1025 (else FD_ERR_SHAPE); fdtype FD_FORWARD or FD_CENTRAL (FD_COMPLEX: FD_ERR_UNSUPPORTED with
+ *                         the JVP's message).  Allocates the JVP's scratch and seven vectors; synchronises.
+ *   fd_jftr_set_options / _set_policy   as fd_csc_tr_set_options / _set_policy (rtol default 1e-10, max_iterations 500).
+ *   fd_jftr_set_steps     relstep, absstep, dir as fd_jvp_async takes them (relstep <= 0: the default; absstep < 0: relstep).
+ *   fd_jftr_set_lazy_f    the lazy JVP launcher of f! and its FD_LAZY_JVP_CAP_* bits; NULL clears (caps must be 0 then).
+ *   fd_jftr_set_diagonal  N doubles m, read at the start of every step (the caller keeps them alive): W = diag(m), z = r / m.  NULL (the
+ *                         default): W = I.  An m_j that is <= 0 or not finite is a breakdown before the first iteration.
+ *   fd_jftr_apply_async   w = lambda*v + beta*q, q exactly what fd_jvp_async gives for (x, v): two multiplications and one addition.  w
+ *                         must not be v or x.  m plays no part.
+ *   fd_jftr_step_async    the truncated conjugate-gradient iteration of fd_csc_tr_step_async from y0 = 0 with the operator above in
+ *                         place of the stored product: inside the region it stops once the recurred ||g + B y||_2 <= rtol * ||g||_2, on
+ *                         the boundary when the next iterate would leave the region, or on the boundary along a direction with
+ *                         p.B p <= 0.  g is required and may be f_in; y or r_out may be g; neither may be x; r_out may be NULL.  g = 0:
+ *                         y = 0, no iteration.  radius = +Inf (or radius^2 = +Inf in Float64): no boundary.  Every scalar stays on the
+ *                         device; the iterations are enqueued in batches, one 16-byte record per batch reaches the host.  Steps
+ *                         enqueued after the end change nothing that the result reads, BUT THE CALLER'S f! IS STILL LAUNCHED by them
+ *                         (on scratch points; what it writes is not read).  One call may be in flight per handle.  A NULL f, x, g or y,
+ *                         lambda < 0 or not finite, beta 0 or not finite, radius <= 0 or NaN is FD_ERR_ARG, and nothing is enqueued.
+ *   fd_jftr_status        synchronises; the outputs of fd_csc_tr_status with B in place of H + lambda I: flags (bit 0: the iterations ran
+ *                         out; bit 1: breakdown -- a bad m_j, p.B p or r.z not finite, or exit 3), exit 0..3, the iterations of the last
+ *                         step, the recurred ||g + B y||_2, ||g||_2, ||y||_W and pred = -1/2 sum y_j (g_j + r_j).  After bit 0 or bit 1, y
+ *                         and r_out are NaN unless fd_jftr_set_policy(tr, 1).  Any out pointer may be NULL.
+ *   fd_jftr_counts        applications: the fd_jftr_apply_async calls plus the products that the steps USED (counted on the device;
+ *                         asking for them synchronises) -- launches enqueued after a step's end are not among them; base_evaluations:
+ *                         the launches of f! for f(x).  Both since creation. */
+typedef struct fd_jftr fd_jftr;
+int fd_jftr_create(fd_ctx *ctx, int64_t N, int fdtype, fd_jftr **out);
+int fd_jftr_destroy(fd_jftr *tr);
+int fd_jftr_set_options(fd_jftr *tr, double rtol, int max_iterations);
+int fd_jftr_set_policy(fd_jftr *tr, int keep_unconverged);
+int fd_jftr_set_steps(fd_jftr *tr, double relstep, double absstep, double dir);
+int fd_jftr_set_lazy_f(fd_jftr *tr, fd_f_launch_lazy_jvp lazy, int caps);
+int fd_jftr_set_diagonal(fd_jftr *tr, const void *m_dev);
+int fd_jftr_apply_async(fd_jftr *tr, double lambda, double beta, fd_f_launch f, void *fctx, const void *x, const void *f_in, const void *v,
+                        void *w);
+int fd_jftr_step_async(fd_jftr *tr, double lambda, double beta, double radius, fd_f_launch f, void *fctx, const void *x, const void *f_in,
+                       const void *g, void *y, void *r_out);
+int fd_jftr_status(fd_jftr *tr, int *flags_out, int *exit_out, int64_t *iterations_out, double *resid_out, double *g_norm_out,
+                   double *step_norm_out, double *pred_out);
+int fd_jftr_counts(fd_jftr *tr, int64_t *applications, int64_t *base_evaluations);
+
 /* ---- the consumer for block-banded Jacobians: (alpha*I + beta*J) y = b for a BLOCK-TRIDIAGONAL J (round 6) ---------------------------
  * J = nblk x nblk dense blocks of block_size x block_size (<= 32), block bandwidths (1, 1), in BlockBandedMatrix data as a
  * fd_plan_create_blockbanded plan of uniform block sizes fills it (block column J's in-band blocks stacked into one column-major

@@ -668,9 +668,15 @@ class CscSolver(_CscConsumer):
         _l.check(self.Lt.fd_csc_matvec_async(self.handle, float(alpha), float(beta), self._vals(J), self._dev(v, "v"), self._dev(y, "y"),
                                              1 if transpose else 0))
 
-    def solve(self, J, b, y, alpha=1.0, beta=-1.0):
-        """Enqueue y = (alpha*I + beta*J)^-1 b on the context's stream (fd_csc_solve_async)."""
-        _l.check(self.Lt.fd_csc_solve_async(self.handle, float(alpha), float(beta), self._vals(J), self._dev(b, "b"), self._dev(y, "y")))
+    def solve(self, J, b, y, alpha=1.0, beta=-1.0, y0=None):
+        """Enqueue y = (alpha*I + beta*J)^-1 b on the context's stream (fd_csc_solve_async).  ``y0`` (N elements on the device, read
+        only): the initial guess (fd_csc_solve_from_async); it may be ``y`` itself -- a solve continued in place -- or ``b``.  The
+        stopping rule stays relative to ||b||; a y0 that already meets it comes back unchanged with 0 iterations."""
+        if y0 is None:
+            _l.check(self.Lt.fd_csc_solve_async(self.handle, float(alpha), float(beta), self._vals(J), self._dev(b, "b"), self._dev(y, "y")))
+        else:
+            _l.check(self.Lt.fd_csc_solve_from_async(self.handle, float(alpha), float(beta), self._vals(J), self._dev(b, "b"), self._dev(y0, "y0"),
+                                                     self._dev(y, "y")))
 
     def status(self):
         """Synchronises.  {"flags": bit 0 not converged | bit 1 breakdown, "iterations", "resid": ||r||_2 of the recurrence, "bnorm"}."""
@@ -940,9 +946,9 @@ class JfnkSolver:
         self._lazy_keep = lz            # (the ctypes function object must outlive the calls)
         _l.check(self.ctx.L.fd_jfnk_solver_set_lazy_f(self.handle, lz if lz is not None else _l.F_LAUNCH_LAZY_JVP(), caps if lz is not None else 0))
 
-    def _call(self, entry, f, x, f_in, a, b, alpha, beta):
+    def _call(self, entry, f, x, f_in, a, b, alpha, beta, *more):
         fn, fctx = self._launcher(f)
-        rc = entry(self.handle, float(alpha), float(beta), fn, fctx, self._dev(x, "x"), self._dev(f_in, "f_in"), a, b)
+        rc = entry(self.handle, float(alpha), float(beta), fn, fctx, self._dev(x, "x"), self._dev(f_in, "f_in"), a, b, *more)
         err = getattr(f, "error", None)
         if err is not None:
             f.error = None
@@ -953,9 +959,13 @@ class JfnkSolver:
         """Enqueue w = alpha*z + beta*J(x) z (fd_jfnk_apply_async)."""
         self._call(self.ctx.L.fd_jfnk_apply_async, f, x, f_in, self._dev(z, "z"), self._dev(w, "w"), alpha, beta)
 
-    def solve(self, f, x, b, y, alpha=1.0, beta=-1.0, f_in=None):
-        """Enqueue y = (alpha*I + beta*J(x))^-1 b (fd_jfnk_solve_async)."""
-        self._call(self.ctx.L.fd_jfnk_solve_async, f, x, f_in, self._dev(b, "b"), self._dev(y, "y"), alpha, beta)
+    def solve(self, f, x, b, y, alpha=1.0, beta=-1.0, f_in=None, y0=None):
+        """Enqueue y = (alpha*I + beta*J(x))^-1 b (fd_jfnk_solve_async).  ``y0`` (N doubles on the device, read only): the initial
+        guess (fd_jfnk_solve_from_async: one more application of the operator); it may be ``y``, ``b`` or ``x``."""
+        if y0 is None:
+            self._call(self.ctx.L.fd_jfnk_solve_async, f, x, f_in, self._dev(b, "b"), self._dev(y, "y"), alpha, beta)
+        else:
+            self._call(self.ctx.L.fd_jfnk_solve_from_async, f, x, f_in, self._dev(b, "b"), self._dev(y0, "y0"), alpha, beta, self._dev(y, "y"))
 
     def status(self):
         """Synchronises.  {"flags": bit 0 the iterations ran out | bit 1 breakdown, "iterations", "resid": the last estimate, "bnorm"}."""

@@ -47,6 +47,10 @@ constexpr int kCsBatchDefault = 8;     // iterations enqueued per record read ba
 // words of a solve, in device memory (the first four are the record the host reads per batch)
 enum { W_DONE = 0, W_EARLY, W_FLAGS, W_ITERS, W_TICKET, W_FINAL, W_NWORDS = 8 };
 
+// W_FLAGS: bit 1 (2) is the breakdown the status reports; the bits above it are INTERNAL to the solve's kernels -- GMRES keeps 4 and 8
+// (fdjac_cscgmres.hip), and kCsYZero says that the accumulator is not the result: a warm start found b = 0, the final kernel writes y = 0.
+// The host's record carries the word as it is: test single bits of CsRecord::flags, never flags != 0.
+constexpr int kCsYZero = 16;
 struct CsRecord { int done, early, flags, iters; };       // what the host reads per batch (the first four words)
 
 struct CsView {                        // the pattern as the kernels see it: CscLists by value (what a consumer did not ask for is NULL)
@@ -165,10 +169,11 @@ __device__ __forceinline__ double cs_strided_sum(int n, FA a, FV v, double *s_w,
 // The long lines of a product go first: workgroup i sums line long_rows[i] (COLS: long_cols[i]) and writes y there; the tile kernel that
 // follows takes the value from y.  What is written: the sum t (CS_LONG_SUM); alpha v_i + beta t (CS_LONG_AXPBY: the sparse solver's rows);
 // t, and g_i = sum a^2 into g (CS_LONG_SUM_G: the start of a least-squares solve).  words: NULL, or the solve whose `done` ends the kernel.
+// TY: y's type when it is not v's (the warm start of a solve: v = y0 in the element type, y = A y0 kept in Float64).
 enum { CS_LONG_SUM = 0, CS_LONG_AXPBY, CS_LONG_SUM_G };
-template <bool COLS, int EPI, typename TV>
+template <bool COLS, int EPI, typename TV, typename TY = TV>
 __global__ void __launch_bounds__(kBlock) k_cs_long(CsView P, double alpha, double beta, const real_t *__restrict__ nz, const TV *__restrict__ v,
-                                                    TV *__restrict__ y, double *__restrict__ g, const int *words)
+                                                    TY *__restrict__ y, double *__restrict__ g, const int *words)
 {
     __shared__ double s_w[kBlock / 64];
     if (words && cs_word(words, W_DONE)) return;
@@ -179,18 +184,18 @@ __global__ void __launch_bounds__(kBlock) k_cs_long(CsView P, double alpha, doub
     const double t = cs_strided_sum<EPI == CS_LONG_SUM_G>(n, [&](int k) { return cs_entry<COLS>(P, nz, a + k); },
                                                           [&](int k) { return (double)v[cs_meets<COLS>(P, a + k)]; }, s_w, &tg);
     if (threadIdx.x == 0) {
-        y[i] = (TV)(EPI == CS_LONG_AXPBY ? alpha * (double)v[i] + beta * t : t);
+        y[i] = (TY)(EPI == CS_LONG_AXPBY ? alpha * (double)v[i] + beta * t : t);
         if (EPI == CS_LONG_SUM_G) g[i] = tg;
     }
 }
 
 // ... enqueued for the pattern's long lines, if it has any.  alpha, beta: CS_LONG_AXPBY alone reads them; g: CS_LONG_SUM_G alone writes it
-template <bool COLS, int EPI, typename TV>
-inline void cs_launch_long(hipStream_t st, const CsView &P, const real_t *nz, const TV *v, TV *y, const int *words, double alpha = 0.0,
+template <bool COLS, int EPI, typename TV, typename TY>
+inline void cs_launch_long(hipStream_t st, const CsView &P, const real_t *nz, const TV *v, TY *y, const int *words, double alpha = 0.0,
                            double beta = 0.0, double *g = nullptr)
 {
     const int n = COLS ? P.nlong_c : P.nlong_r;
-    if (n > 0) hipLaunchKernelGGL((k_cs_long<COLS, EPI, TV>), dim3((unsigned)n), dim3(kBlock), 0, st, P, alpha, beta, nz, v, y, g, words);
+    if (n > 0) hipLaunchKernelGGL((k_cs_long<COLS, EPI, TV, TY>), dim3((unsigned)n), dim3(kBlock), 0, st, P, alpha, beta, nz, v, y, g, words);
 }
 
 // A tile of 256 lines per workgroup: this lane's line is order[tile0 + lane] (negative: none).  A line of at most kCsLong entries is

@@ -160,14 +160,15 @@ __global__ void __launch_bounds__(kBlock) k_gm_scale(int N, const double *__rest
         if (i < N) out[i] = x[i] / (BYVEC ? d[i] : by);
     }
 }
-// the start of a cycle: v_0 = r / gamma, g_0 = gamma.  FIRST: gamma^2 = ||b||^2 (k_cs_init's), and the tolerance and the first estimate
-// are set whatever the start kernels found; later cycles take what k_gm_resid left
-template <bool FIRST>
+// the start of a cycle: v_0 = r / gamma, g_0 = gamma.  FIRST 1: gamma^2 = ||b||^2 (k_cs_init's), and the tolerance and the first estimate
+// are set whatever the start kernels found; 2 (a warm start): gamma^2 = ||r0||^2 as the warm start kernel left it in S_GAMMA2, the
+// tolerance still from ||b||; later cycles (0) take what k_gm_resid left
+template <int FIRST>
 __global__ void __launch_bounds__(kBlock) k_gm_start(int N, const double *__restrict__ r, CsGm G, double rtol, double *scal, const int *words)
 {
-    const double gamma = sqrt(scal[FIRST ? S_BNORM2 : S_GAMMA2]);
+    const double gamma = sqrt(scal[FIRST == 1 ? S_BNORM2 : S_GAMMA2]);
     if (FIRST && blockIdx.x == 0 && threadIdx.x == 0) {
-        scal[S_GTOL] = rtol * gamma;
+        scal[S_GTOL] = rtol * (FIRST == 1 ? gamma : sqrt(scal[S_BNORM2]));
         scal[S_GRES] = gamma;
     }
     if (cs_word(words, W_DONE)) return;
@@ -346,7 +347,7 @@ __global__ void __launch_bounds__(kBlock) k_gm_final(int N, const double *__rest
         *klast = words[W_GM_K];
     }
     if (i >= N) return;
-    y[i] = (real_t)((flags && !keep) ? __longlong_as_double(0x7FF8000000000000ll) : yacc[i]);
+    y[i] = (real_t)((flags && !keep) ? __longlong_as_double(0x7FF8000000000000ll) : ((f & kCsYZero) ? 0.0 : yacc[i]));
 }
 
 }  // namespace fdjac

@@ -168,6 +168,60 @@ __global__ void __launch_bounds__(kBlock) k_cs_init(CsView P, CsVecs V, double a
         if (done) __hip_atomic_store(words + W_DONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
+// THE WARM START (fd_csc_solve_from_async with a y0): one launch in k_cs_init's place, on its grid.  A workgroup takes its tile of
+// kCsVecTile elements as kCsVecTile / 256 sub-tiles of 256 rows: each sub-tile is a k_cs_rows tile (lane i takes row
+// row_order[sub-tile + i], a row of at most kCsLong entries is summed there in ascending column, a longer one takes what k_cs_long left
+// in wl; y0 is read from memory: the bits do not depend on a window), w = alpha y0 + beta acc stays Float64 and crosses LDS once into
+// row order.  Thread t then holds elements t, t + 256, ... of the tile as in k_cs_init, so ||b||^2 and ||r0||^2 are dot_vec's sums:
+// r0 = b - w (one subtraction), r = rhat = r0, p = v = 0, the accumulator y = (double)y0, d as in k_cs_init, and one cs_finish<2>.
+// The last workgroup: S_BNORM2, S_TOL2 from ||b||^2; rho = ||r0||^2 (S_GAMMA2 too: k_gm_start<2> opens the first GMRES cycle on it).
+// b = 0: done, and kCsYZero in the flags makes the final kernel write y = 0 whatever y0 holds.  Then a bad diagonal; ||b||^2 or
+// ||r0||^2 not finite: breakdown (a NaN in y0 ends here); ||r0||^2 <= tol^2: done, 0 iterations, y = y0.
+template <int PC>
+__global__ void __launch_bounds__(kBlock) k_cs_init_from(CsView P, CsVecs V, double alpha, double beta, const real_t *__restrict__ nz,
+                                                         const real_t *__restrict__ b, const real_t *__restrict__ y0, const double *wl,
+                                                         double rtol, double *scal, int *words, double *part)
+{
+    __shared__ double s_out[kBlock];
+    __shared__ double s_w[kBlock / 64];
+    const int t0 = blockIdx.x * kCsVecTile;
+    double mine[2] = {0.0, 0.0}, tot[2];
+    bool bad = false;
+    for (int k = 0; k < kCsVecTile / kBlock; ++k) {
+        const int r0 = t0 + k * kBlock;
+        if (r0 >= P.N) break;                                                    // (the same in every thread: barriers below)
+        cs_tile_lines<false, false>(P, r0, nz, wl, nullptr, s_out, nullptr, [=](int i) { return (double)y0[i]; },
+                                    [=](int r, double acc) { return alpha * (double)y0[r] + beta * acc; });
+        const int i = r0 + threadIdx.x;
+        if (i < P.N) {
+            const double bi = (double)b[i], ri = bi - s_out[threadIdx.x];
+            if (PC == 0) {
+                const int q = P.diag[i];
+                const double d = q >= 0 ? alpha + beta * (double)nz[q] : alpha;
+                bad = bad || cs_bad_pivot(d);
+                V.d[i] = d;
+            }
+            V.r[i] = ri; V.rhat[i] = ri; V.p[i] = 0.0; V.v[i] = 0.0; V.y[i] = (double)y0[i];
+            mine[0] += bi * bi;
+            mine[1] += ri * ri;
+        }
+        __syncthreads();                                                         // s_out is the next sub-tile's
+    }
+    if (bad) atomicOr(words + W_FLAGS, 2);
+    if (cs_finish<2>(mine, part, words, tot, s_w) && threadIdx.x == 0) {
+        const bool zero = tot[0] == 0.0;                                          // b = 0: y = 0 and r = b
+        const double rn2 = zero ? tot[0] : tot[1];
+        scal[S_RHO] = rn2; scal[S_RHO_OLD] = 1.0; scal[S_ALPHA] = 1.0; scal[S_OMEGA] = 1.0;
+        scal[S_BNORM2] = tot[0]; scal[S_RNORM2] = rn2; scal[S_SNORM2] = 0.0; scal[S_GAMMA2] = rn2;
+        scal[S_TOL2] = (rtol * rtol) * tot[0];
+        int done = 0;
+        if (zero) { atomicOr(words + W_FLAGS, kCsYZero); done = 1; }
+        else if (cs_word(words, W_FLAGS) & 2) done = 1;
+        else if (cs_not_finite(tot[0]) || cs_not_finite(rn2)) { atomicOr(words + W_FLAGS, 2); done = 1; }
+        else if (rn2 <= (rtol * rtol) * tot[0]) done = 1;                        // y0 is good enough: y = y0, no iteration
+        if (done) __hip_atomic_store(words + W_DONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
 // fd_csc_solver_factor_async under the Jacobi preconditioner: d = alpha + beta J_ii as k_cs_init<0> forms it, into storage of the
 // factorisation's own; a d_i that is zero or not finite: breakdown in the factorisation's words
 __global__ void __launch_bounds__(kBlock) k_cs_fdiag(CsView P, double alpha, double beta, const real_t *__restrict__ nz, double *__restrict__ d,
@@ -433,14 +487,16 @@ __global__ void __launch_bounds__(kBlock) k_cs_ilu_apply(CsView P, CsIlu I, cons
     }
     for (int t = threadIdx.x; t < n; t += kBlock) out[b0 + t] = s_z[t];
 }
-// the end: bit 0 when the iterations ran out; y, or NaN after a failure unless the caller keeps the last iterate
+// the end: bit 0 when the iterations ran out; y, or NaN after a failure unless the caller keeps the last iterate (kCsYZero: a warm start
+// found b = 0, the iterate is 0 and not the accumulator).  THE ONLY KERNEL OF A SOLVE THAT WRITES y: y0 may be y, y0 and y may be b.
 __global__ void __launch_bounds__(kBlock) k_cs_final(int N, const double *__restrict__ yacc, real_t *__restrict__ y, int *words, int keep)
 {
-    const int flags = (cs_word(words, W_FLAGS) & 2) | (cs_word(words, W_DONE) ? 0 : 1);
+    const int f = cs_word(words, W_FLAGS);
+    const int flags = (f & 2) | (cs_word(words, W_DONE) ? 0 : 1);
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i == 0) words[W_FINAL] = flags;
     if (i >= N) return;
-    y[i] = (real_t)((flags && !keep) ? __longlong_as_double(0x7FF8000000000000ll) : yacc[i]);
+    y[i] = (real_t)((flags && !keep) ? __longlong_as_double(0x7FF8000000000000ll) : ((f & kCsYZero) ? 0.0 : yacc[i]));
 }
 
 }  // namespace fdjac
@@ -789,7 +845,8 @@ int fd_csc_matvec_async(fd_csc_solver *s, double alpha, double beta, const void 
 //   product(mode, v, w) w = A v; mode 3: a step's product (nothing once the cycle is over), 4: the explicit residual's (once the solve is)
 //   add(u, z)           the cycle's end behind k_gm_tri: y = y + M^-1 (V t) over the columns W_GM_UPD counts
 template <class PC, class PR, class AD>
-static int csc_gmres_iterate(hipStream_t st, CscSolveState &S, int N, const CsGm &G, const real_t *b, const CsVecs &V, PC precond, PR product, AD add)
+static int csc_gmres_iterate(hipStream_t st, CscSolveState &S, int N, const CsGm &G, const real_t *b, const CsVecs &V, bool warm, PC precond, PR product,
+                             AD add)
 {
     const int m = G.m;
     const size_t n = (size_t)N;
@@ -797,7 +854,8 @@ static int csc_gmres_iterate(hipStream_t st, CscSolveState &S, int N, const CsGm
     double *z = V.p, *w = V.v, *u = V.s, *npart = G.part + (size_t)(m + 1) * G.ntile;
     int *words = S.d_words;
     int rc = FD_OK;
-    hipLaunchKernelGGL(k_gm_start<true>, dim3(gv), dim3(kBlock), 0, st, N, (const double *)V.r, G, S.rtol, S.d_scal, (const int *)words);
+    // the first cycle: on r = b, or (warm: a y0 was given) on the r0 = b - A y0 and the ||r0||^2 that the warm start left
+    hipLaunchKernelGGL(warm ? k_gm_start<2> : k_gm_start<1>, dim3(gv), dim3(kBlock), 0, st, N, (const double *)V.r, G, S.rtol, S.d_scal, (const int *)words);
     const auto step = [&](int j) {      // the sparse consumer: 10 launches (+ 1 with long rows)
         const double *vj = G.V + (size_t)j * n, *zj = nullptr;
         if ((rc = precond(vj, z, &zj)) != FD_OK) return;
@@ -820,7 +878,7 @@ static int csc_gmres_iterate(hipStream_t st, CscSolveState &S, int N, const CsGm
         hipLaunchKernelGGL(k_gm_close, dim3(1), dim3(64), 0, st, words);
         if ((rc = product(4, (const double *)V.y, w)) != FD_OK) return;
         hipLaunchKernelGGL(k_gm_resid, dim3(gv), dim3(kBlock), 0, st, N, b, (const double *)w, V.r, S.d_scal, words, S.d_part);
-        hipLaunchKernelGGL(k_gm_start<false>, dim3(gv), dim3(kBlock), 0, st, N, (const double *)V.r, G, S.rtol, S.d_scal, (const int *)words);
+        hipLaunchKernelGGL(k_gm_start<0>, dim3(gv), dim3(kBlock), 0, st, N, (const double *)V.r, G, S.rtol, S.d_scal, (const int *)words);
     };
     // batches as in CscSolveState::run, but a batch ends where its cycle does, and the cycle's end goes with it
     int enq = 0, j = 0, nb = 0;
@@ -849,6 +907,13 @@ static int csc_gmres_iterate(hipStream_t st, CscSolveState &S, int N, const CsGm
 }
 
 int fd_csc_solve_async(fd_csc_solver *s, double alpha, double beta, const void *nzval, const void *b, void *y)
+{
+    return fd_csc_solve_from_async(s, alpha, beta, nzval, b, nullptr, y);
+}
+
+// y0 == NULL: the cold start, launch for launch.  Otherwise k_cs_init_from stands where k_cs_init stood (behind k_cs_long on y0 when the
+// pattern has long rows); everything behind the start is the same solve.  y is written by the final kernel alone.
+int fd_csc_solve_from_async(fd_csc_solver *s, double alpha, double beta, const void *nzval, const void *b, const void *y0, void *y)
 {
     FD_REQUIRE(s && b && y && (nzval || s->L.nnz == 0), FD_ERR_ARG, "NULL argument");
     FD_HIP_CHECK(hipSetDevice(s->ctx->device));
@@ -893,14 +958,20 @@ int fd_csc_solve_async(fd_csc_solver *s, double alpha, double beta, const void *
         else if (bs > 0) hipLaunchKernelGGL(which ? k_cs_bapply<1> : k_cs_bapply<0>, dim3(gv), dim3(kBlock), 0, st, N, bs, (const double *)s->d_minv, x, out, words);
     };
     // the start: init, then factor or invert
-    if (blocks) hipLaunchKernelGGL(k_cs_init<1>, dim3(gv), dim3(kBlock), 0, st, P, V, alpha, beta, nz, (const real_t *)b, S.rtol, S.d_scal, S.d_words, S.d_part);
+    if (y0) {      // w = A y0 of the long rows into V.t (nothing reads t before the iteration's second product writes it), then the fused start
+        cs_launch_long<false, CS_LONG_AXPBY>(st, P, nz, (const real_t *)y0, V.t, nullptr, alpha, beta);
+        fd_pick<0, 1>(blocks ? 1 : 0, [&](auto PCK) {
+            hipLaunchKernelGGL(k_cs_init_from<PCK()>, dim3(gv), dim3(kBlock), 0, st, P, V, alpha, beta, nz, (const real_t *)b, (const real_t *)y0,
+                               (const double *)V.t, S.rtol, S.d_scal, S.d_words, S.d_part);
+        });
+    } else if (blocks) hipLaunchKernelGGL(k_cs_init<1>, dim3(gv), dim3(kBlock), 0, st, P, V, alpha, beta, nz, (const real_t *)b, S.rtol, S.d_scal, S.d_words, S.d_part);
     else hipLaunchKernelGGL(k_cs_init<0>, dim3(gv), dim3(kBlock), 0, st, P, V, alpha, beta, nz, (const real_t *)b, S.rtol, S.d_scal, S.d_words, S.d_part);
     if (ilu) csc_ilu_factor_launch(s, alpha, beta, nz, S.d_words);
     else if (bs > 0) csc_binv_launch(s, bs, alpha, beta, nz, S.d_words);
     s->last_gmres = gmres;
     if (gmres) {
         const CsGm G = csc_gm(s, s->gm_m);
-        const int rc = csc_gmres_iterate(st, S, N, G, (const real_t *)b, V,
+        const int rc = csc_gmres_iterate(st, S, N, G, (const real_t *)b, V, y0 != nullptr,
             [&](const double *vj, double *z, const double **zj) {      // z = M^-1 v_j
                 if (blocks) apply(1, vj, z);
                 else hipLaunchKernelGGL(k_gm_scale<true>, dim3(gv), dim3(kBlock), 0, st, N, vj, (const double *)V.d, z, words);

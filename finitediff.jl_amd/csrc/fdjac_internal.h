@@ -86,6 +86,7 @@
 #define fd_csc_solver_factor_status fd32_csc_solver_factor_status
 #define fd_csc_matvec_async fd32_csc_matvec_async
 #define fd_csc_solve_async fd32_csc_solve_async
+#define fd_csc_solve_from_async fd32_csc_solve_from_async
 #define fd_csc_solver_status fd32_csc_solver_status
 #define fd_csc_lsq fd32_csc_lsq
 #define fd_csc_lsq_create fd32_csc_lsq_create

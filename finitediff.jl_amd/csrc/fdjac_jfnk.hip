@@ -17,7 +17,8 @@
 // block ILU applies with the lender's k_cs_ilu_apply and leaves the dot to the JVP; block Jacobi above kSmallN runs k_jf_open_blocks,
 // k_jf_open with k_cs_bapply's sum in place of the division (up to kSmallN: k_cs_bapply, then k_jvp_small).  The cycle's end is the
 // sparse consumer's: k_gm_combine<0>, the apply, k_gm_yadd.  tests/jfnk_pc_model.py composes the existing models of all of it.
-// THE REST is the sparse consumer's GMRES word for word: y0 = 0, CGS2, the rotations, the back substitution, the restart through the
+// THE REST is the sparse consumer's GMRES word for word: y0 = 0 (or the caller's: fd_jfnk_solve_from_async, k_jf_from below), CGS2,
+// the rotations, the back substitution, the restart through the
 // same operator (r = b - A(x) y), flags, NaN in y after a failure unless the policy keeps the iterate.
 // After `cycle over` the kernels here do nothing (gm_idle), but the caller's f! is still launched by the steps already enqueued: what it
 // writes is scratch that nothing reads.
@@ -221,6 +222,39 @@ __global__ void __launch_bounds__(kBlock) k_jf_init(int N, const double *__restr
     }
 }
 
+// the warm start behind w = A(x) y0 (one application of the operator, k_jf_init before it): r0 = b - w (one subtraction), the
+// accumulator y = y0, ||r0||^2 in dot_vec's order; the last workgroup leaves gamma^2 = ||r0||^2 for k_gm_start<2> and ends the solve on
+// ||r0||^2 not finite (breakdown: a NaN in y0) or ||r0||^2 <= rtol^2 ||b||^2 (y = y0, no iteration).  Nothing once k_jf_init has ended
+// the solve (b = 0: y stays 0; a bad preconditioner; ||b||^2 not finite).
+__global__ void __launch_bounds__(kBlock) k_jf_from(int N, const double *__restrict__ b, const double *__restrict__ w, const double *__restrict__ y0,
+                                                    double *__restrict__ r, double *__restrict__ y, double rtol, double *scal, int *words, double *part,
+                                                    int keep)
+{
+    __shared__ double s_w[kBlock / 64];
+    const int i0 = blockIdx.x * kCsVecTile + threadIdx.x;
+    if (cs_word(words, W_DONE)) {      // k_jf_init has ended the solve: w is not read (it may hold anything) and k_gm_start<2> reports ||b||
+        if (blockIdx.x == 0 && threadIdx.x == 0) scal[S_GAMMA2] = scal[S_BNORM2];
+        // under the keep policy the iterate of a breakdown before the first step is y0 (not after b = 0)
+        if (keep && (cs_word(words, W_FLAGS) & 2) && scal[S_BNORM2] != 0.0)
+            for (int k = 0; k < kCsVecTile / kBlock; ++k)
+                if (i0 + k * kBlock < N) y[i0 + k * kBlock] = y0[i0 + k * kBlock];
+        return;
+    }
+    double mine[1] = {0.0}, tot[1];
+    for (int k = 0; k < kCsVecTile / kBlock; ++k) {
+        const int i = i0 + k * kBlock;
+        if (i >= N) continue;
+        const double ri = b[i] - w[i];
+        r[i] = ri; y[i] = y0[i];
+        mine[0] += ri * ri;
+    }
+    if (cs_finish<1>(mine, part, words, tot, s_w) && threadIdx.x == 0) {
+        scal[S_GAMMA2] = tot[0];
+        if (cs_not_finite(tot[0])) cs_breakdown(words);
+        else if (tot[0] <= (rtol * rtol) * scal[S_BNORM2]) __hip_atomic_store(words + W_DONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
 int balanced_grid(int64_t tiles, int64_t cap);
 
 struct JfOp {      // one application of the operator: what the closing kernel needs
@@ -393,6 +427,15 @@ int fd_jfnk_apply_async(fd_jfnk_solver *s, double alpha, double beta, fd_f_launc
 int fd_jfnk_solve_async(fd_jfnk_solver *s, double alpha, double beta, fd_f_launch f, void *fctx, const void *x, const void *f_in, const void *b,
                         void *y)
 {
+    return fd_jfnk_solve_from_async(s, alpha, beta, f, fctx, x, f_in, b, nullptr, y);
+}
+
+// y0 == NULL: the cold start, launch for launch.  Otherwise, behind k_jf_init: one application of the operator on y0 (the JVP's own
+// launches) and k_jf_from; the first cycle then opens on r0 (k_gm_start<2>).  With a preconditioner the host reads the record behind
+// k_jf_init first (one synchronisation): a solve that k_jf_init has ended -- a bad pivot above all -- enqueues and counts no product.
+int fd_jfnk_solve_from_async(fd_jfnk_solver *s, double alpha, double beta, fd_f_launch f, void *fctx, const void *x, const void *f_in, const void *b,
+                             const void *y0, void *y)
+{
     FD_REQUIRE(s && f && x && b && y, FD_ERR_ARG, "NULL argument");
     FD_REQUIRE(y != x, FD_ERR_ARG, "y must not be x");
     fd_csc_solver *pc = s->pc;
@@ -414,16 +457,36 @@ int fd_jfnk_solve_async(fd_jfnk_solver *s, double alpha, double beta, fd_f_launc
     const CsGm G = gm_view(s->d_gm, (size_t)N, s->m);
     const int *words = S.d_words;
     const auto run = [&]() -> int {
-        const double *fin;
-        bool own;
-        const int rb = jf_base(s, f, fctx, xd, (const double *)f_in, &fin, &own);
-        if (rb != FD_OK) return rb;
+        const double *fin = nullptr;
+        bool own = false;
+        if (!y0) {
+            const int rb = jf_base(s, f, fctx, xd, (const double *)f_in, &fin, &own);
+            if (rb != FD_OK) return rb;
+        }
         FD_HIP_CHECK(hipMemsetAsync(S.d_words, 0, sizeof(int) * W_NWORDS, st));
         hipLaunchKernelGGL(k_jf_init, dim3(gv), dim3(kBlock), 0, st, N, d, (const double *)b, V.r, V.y, S.rtol, S.d_scal, S.d_words, S.d_part,
                            pc ? (const int *)pc->d_fwords : (const int *)nullptr);
+        if (y0) {
+            if (d || pc) {      // the preconditioner's verdict before anything of the operator is enqueued
+                FD_HIP_CHECK(hipMemcpyAsync(&S.h_rec[0], S.d_words, sizeof(CsRecord), hipMemcpyDeviceToHost, st));
+                FD_HIP_CHECK(hipStreamSynchronize(st));
+                if (S.h_rec[0].done) {      // (no product: V.v holds whatever the last solve left, and k_jf_from does not read it once `done`)
+                    hipLaunchKernelGGL(k_jf_from, dim3(gv), dim3(kBlock), 0, st, N, (const double *)b, (const double *)V.v, (const double *)y0, V.r, V.y,
+                                       S.rtol, S.d_scal, S.d_words, S.d_part, S.keep);
+                    hipLaunchKernelGGL(k_gm_start<2>, dim3(gv), dim3(kBlock), 0, st, N, (const double *)V.r, G, S.rtol, S.d_scal, words);
+                    return FD_OK;
+                }
+            }
+            const int rb = jf_base(s, f, fctx, xd, (const double *)f_in, &fin, &own);
+            if (rb != FD_OK) return rb;
+            const int ro = jf_operator(s, alpha, beta, f, fctx, xd, fin, own, (const double *)y0, V.v, false, words, 4);
+            if (ro != FD_OK) return ro;
+            hipLaunchKernelGGL(k_jf_from, dim3(gv), dim3(kBlock), 0, st, N, (const double *)b, (const double *)V.v, (const double *)y0, V.r, V.y, S.rtol,
+                               S.d_scal, S.d_words, S.d_part, S.keep);
+        }
         const bool fused = (d != nullptr || pc_bjac) && !(s->jp->small_ok && s->N <= kSmallN);
         bool partials = false;
-        return csc_gmres_iterate(st, S, N, G, (const double *)b, V,
+        return csc_gmres_iterate(st, S, N, G, (const double *)b, V, y0 != nullptr,
             [&](const double *vj, double *z, const double **zj) {      // z = v_j / d, or v_j itself
                 partials = false;
                 if (pc_blocks) {

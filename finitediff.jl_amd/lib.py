@@ -84,13 +84,13 @@ EXPORTS = (
     "fd_banded_solver_create", "fd_banded_solver_destroy", "fd_banded_solver_set_policy", "fd_banded_solver_status", "fd_banded_solve_async",
     "fd_blocktridiag_solver_create", "fd_blocktridiag_solver_destroy", "fd_blocktridiag_solver_set_policy", "fd_blocktridiag_solver_status",
     "fd_blocktridiag_solve_async",
-    "fd_csc_solver_create", "fd_csc_solver_destroy", "fd_csc_matvec_async", "fd_csc_solver_set_options", "fd_csc_solver_set_policy", "fd_csc_solve_async", "fd_csc_solver_status", "fd_csc_solver_row_lists",
+    "fd_csc_solver_create", "fd_csc_solver_destroy", "fd_csc_matvec_async", "fd_csc_solver_set_options", "fd_csc_solver_set_policy", "fd_csc_solve_async", "fd_csc_solve_from_async", "fd_csc_solver_status", "fd_csc_solver_row_lists",
     "fd_csc_solver_set_preconditioner", "fd_csc_solver_block_inverses", "fd_csc_solver_set_block_ilu", "fd_csc_solver_ilu_levels", "fd_csc_solver_ilu_factors", "fd_csc_solver_set_method", "fd_csc_solver_gmres_basis",
     "fd_csc_solver_factor_async", "fd_csc_solver_apply_async", "fd_csc_solver_factor_status",
     "fd_csc_lsq_create", "fd_csc_lsq_destroy", "fd_csc_lsq_matvec_async", "fd_csc_lsq_set_options", "fd_csc_lsq_set_policy", "fd_csc_lsq_solve_async", "fd_csc_lsq_status", "fd_csc_lsq_row_lists", "fd_csc_lsq_long_columns",
     "fd_csc_tr_create", "fd_csc_tr_destroy", "fd_csc_tr_set_options", "fd_csc_tr_set_policy", "fd_csc_tr_matvec_async", "fd_csc_tr_step_async", "fd_csc_tr_status",
     "fd_jfnk_solver_create", "fd_jfnk_solver_destroy", "fd_jfnk_solver_set_options", "fd_jfnk_solver_set_policy", "fd_jfnk_solver_set_steps", "fd_jfnk_solver_set_lazy_f",
-    "fd_jfnk_solver_set_diagonal", "fd_jfnk_solver_set_csc_preconditioner", "fd_jfnk_apply_async", "fd_jfnk_solve_async", "fd_jfnk_solver_status", "fd_jfnk_solver_counts", "fd_jfnk_solver_basis",
+    "fd_jfnk_solver_set_diagonal", "fd_jfnk_solver_set_csc_preconditioner", "fd_jfnk_apply_async", "fd_jfnk_solve_async", "fd_jfnk_solve_from_async", "fd_jfnk_solver_status", "fd_jfnk_solver_counts", "fd_jfnk_solver_basis",
     "fd_jftr_create", "fd_jftr_destroy", "fd_jftr_set_options", "fd_jftr_set_policy", "fd_jftr_set_steps", "fd_jftr_set_lazy_f", "fd_jftr_set_diagonal",
     "fd_jftr_apply_async", "fd_jftr_step_async", "fd_jftr_status", "fd_jftr_counts",
     "fd_objective_compile", "fd_objective_destroy", "fd_objective_counts", "fd_hess_plan_create", "fd_hess_plan_destroy",
@@ -114,7 +114,7 @@ TYPED = (
     "fd_banded_solver_create", "fd_banded_solver_destroy", "fd_banded_solver_set_policy", "fd_banded_solver_status", "fd_banded_solve_async",
     "fd_blocktridiag_solver_create", "fd_blocktridiag_solver_destroy", "fd_blocktridiag_solver_set_policy", "fd_blocktridiag_solver_status",
     "fd_blocktridiag_solve_async",
-    "fd_csc_solver_create", "fd_csc_solver_destroy", "fd_csc_matvec_async", "fd_csc_solver_set_options", "fd_csc_solver_set_policy", "fd_csc_solve_async", "fd_csc_solver_status", "fd_csc_solver_row_lists",
+    "fd_csc_solver_create", "fd_csc_solver_destroy", "fd_csc_matvec_async", "fd_csc_solver_set_options", "fd_csc_solver_set_policy", "fd_csc_solve_async", "fd_csc_solve_from_async", "fd_csc_solver_status", "fd_csc_solver_row_lists",
     "fd_csc_solver_set_preconditioner", "fd_csc_solver_block_inverses", "fd_csc_solver_set_block_ilu", "fd_csc_solver_ilu_levels", "fd_csc_solver_ilu_factors", "fd_csc_solver_set_method", "fd_csc_solver_gmres_basis",
     "fd_csc_solver_factor_async", "fd_csc_solver_apply_async", "fd_csc_solver_factor_status",
     "fd_csc_lsq_create", "fd_csc_lsq_destroy", "fd_csc_lsq_matvec_async", "fd_csc_lsq_set_options", "fd_csc_lsq_set_policy", "fd_csc_lsq_solve_async", "fd_csc_lsq_status", "fd_csc_lsq_row_lists", "fd_csc_lsq_long_columns",
@@ -296,6 +296,7 @@ def load():
     L.fd_csc_solver_set_options.argtypes = [vp, dbl, i32]
     L.fd_csc_solver_set_policy.argtypes = [vp, i32]
     L.fd_csc_solve_async.argtypes = [vp, dbl, dbl, vp, vp, vp]
+    L.fd_csc_solve_from_async.argtypes = [vp, dbl, dbl, vp, vp, vp, vp]
     L.fd_csc_solver_status.argtypes = [vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(dbl), C.POINTER(dbl)]
     L.fd_csc_solver_row_lists.argtypes = [vp, pp, pp, pp, pp, C.POINTER(i64), C.POINTER(i64)]
     L.fd_csc_solver_set_preconditioner.argtypes = [vp, i32, i32]
@@ -334,6 +335,7 @@ def load():
     L.fd_jfnk_solver_set_csc_preconditioner.argtypes = [vp, vp]
     L.fd_jfnk_apply_async.argtypes = [vp, dbl, dbl, F_LAUNCH, vp, vp, vp, vp, vp]
     L.fd_jfnk_solve_async.argtypes = [vp, dbl, dbl, F_LAUNCH, vp, vp, vp, vp, vp]
+    L.fd_jfnk_solve_from_async.argtypes = [vp, dbl, dbl, F_LAUNCH, vp, vp, vp, vp, vp, vp]
     L.fd_jfnk_solver_status.argtypes = [vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(dbl), C.POINTER(dbl)]
     L.fd_jfnk_solver_counts.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     L.fd_jfnk_solver_basis.argtypes = [vp, pp, pp, C.POINTER(i32), C.POINTER(i32)]

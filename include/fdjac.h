@@ -733,6 +733,21 @@ int fd_banded_solve_async(fd_banded_solver *solver, double alpha, double beta, c
  *                         until ||r||_2 <= rtol * ||b||_2 (fd_csc_solver_set_options: rtol, default 1e-10; max_iterations, default 500).
  *                         Every scalar stays on the device; the iterations are enqueued in batches and the call waits only for one
  *                         16-byte record per batch, one batch behind the device.  b = 0: y = 0, no iteration.  y may be b.
+ *   fd_csc_solve_from_async  THE SAME SOLVE FROM AN INITIAL GUESS y0 (N elements of the library's type on the device, read only), with
+ *                         either method and any preconditioner.  y0 == NULL is fd_csc_solve_async itself: the same launches, the same
+ *                         bits.  ALIASING: y0 may be y (a solve continued in place), y0 may be b, y may be b: y is written by the
+ *                         solve's last kernel alone.  THE START: w = (alpha*I + beta*J) y0 in the row-wise product's order (a row of
+ *                         more than 32 entries by the workgroup's sum), kept in Float64 and not rounded to the element type;
+ *                         r0 = b - w, one subtraction per element; ||b||^2 and ||r0||^2 in the order of the solver's other dots.  The
+ *                         stopping rule stays relative to b (||r||_2 <= rtol * ||b||_2) and status reports ||b||_2 as bnorm.
+ *                         b = 0: y = 0 with no iteration, whatever y0 holds.  ||r0||^2 <= rtol^2 * ||b||^2: done at once, y = y0
+ *                         exactly, 0 iterations, resid = ||r0||_2.  ||b||^2 or ||r0||^2 not finite (a NaN in y0): breakdown (bit 1)
+ *                         before the first step; y is NaN, or y0 under fd_csc_solver_set_policy(solver, 1) -- no iterate exists yet.
+ *                         BiCGStab: r = rhat = r0, rho = ||r0||^2, p = v = 0, the iterate starts at (double)y0; GMRES: the first
+ *                         cycle opens on r0 as a restart opens on its explicit residual, the iterate at (double)y0; everything behind
+ *                         the start is the solve described here.  The start's product is no iteration.  The preconditioner is set up
+ *                         as in the cold start and a bad pivot still ends the solve before any step (resid is ||r0||_2 then).  ONE
+ *                         launch stands where the cold start's first stood (+ 1 when the pattern has long rows).
  *   fd_csc_solver_status  synchronises; flags bit 0: not converged within max_iterations; bit 1: breakdown (rho, rhat.v, t.t or a Jacobi
  *                         diagonal zero or not finite); the iterations of the last solve, its last recurrence residual norm and ||b||_2.
  *                         After either failure y is NaN, unless fd_csc_solver_set_policy(solver, 1): then y is the last iterate and the
@@ -788,7 +803,7 @@ int fd_banded_solve_async(fd_banded_solver *solver, double alpha, double beta, c
  *                         classical Gram-Schmidt applied twice (CGS2); every order is fixed (GMRES): the same bits every
  *                         call.  A step is 10 launches (+ 1 with long rows) and streams about 4 j + 16 vectors at column j.  The
  *                         first GMRES solve allocates (restart + 1) * N doubles for the basis and about 2 restart^2 + (restart + 2) *
- *                         ceil(N / 1024) doubles beside it; freed with the solver.  No flexible variant, no warm start.  NOT TIMED.
+ *                         ceil(N / 1024) doubles beside it; freed with the solver.  No flexible variant.  NOT TIMED.
  *   fd_csc_solver_gmres_basis  DIAGNOSTIC ONLY (FD_ERR_UNSUPPORTED before the first GMRES solve): device pointers, owned by the solver, to
  *                         the basis of the last cycle of the last GMRES solve (vector-major: v_i at V + i * N) and to its Hessenberg
  *                         columns as Arnoldi gave them (column j at H + j * (restart + 1)), that solve's restart, and the columns the
@@ -825,6 +840,7 @@ int fd_csc_matvec_async(fd_csc_solver *solver, double alpha, double beta, const 
 int fd_csc_solver_set_options(fd_csc_solver *solver, double rtol, int max_iterations);
 int fd_csc_solver_set_policy(fd_csc_solver *solver, int keep_unconverged);
 int fd_csc_solve_async(fd_csc_solver *solver, double alpha, double beta, const void *nzval, const void *b, void *y);
+int fd_csc_solve_from_async(fd_csc_solver *solver, double alpha, double beta, const void *nzval, const void *b, const void *y0, void *y);
 int fd_csc_solver_status(fd_csc_solver *solver, int *flags_out, int64_t *iterations_out, double *resid_out, double *bnorm_out);
 int fd_csc_solver_row_lists(fd_csc_solver *solver, const void **row_ptr, const void **row_col, const void **row_slot, const void **diag_slot,
                             int64_t *nnz_out, int64_t *long_rows_out);
@@ -868,13 +884,25 @@ int fd_csc_solver_factor_status(fd_csc_solver *solver, int *flags);
  *                         vectors stay Float64: z = M^-1 v_j by the lender's own kernels (block Jacobi above 16384 elements: one
  *                         kernel that also leaves the JVP's dot), y += M^-1 (V t) at a cycle's end.
  *   fd_jfnk_apply_async   w = A(x) z; w must not be z or x.  The diagonal plays no part.
- *   fd_jfnk_solve_async   GMRES(restart) exactly as fd_csc_solver_set_method describes it (y0 = 0, CGS2, the estimate, the restart through the
+ *   fd_jfnk_solve_async   GMRES(restart) exactly as fd_csc_solver_set_method describes it (y0 = 0 -- fd_jfnk_solve_from_async takes
+ *                         one --, CGS2, the estimate, the restart through the
  *                         explicit r = b - A(x) y, max_iterations caps the Arnoldi steps, b = 0: y = 0 with 0 iterations, ||b||^2 not
  *                         finite: breakdown), with the operator above in place of the stored product.  y may be b, not x.  The
  *                         iterations are enqueued in batches that never span a cycle; one 16-byte record per batch reaches the host.
  *                         Steps enqueued after the cycle is over change nothing that the result or the diagnostic reads, BUT THE
  *                         CALLER'S f! IS STILL LAUNCHED by them (on scratch points; what it writes is not read).  One call may be in
  *                         flight per solver.  The operator is only approximately linear: the estimate inherits that.
+ *   fd_jfnk_solve_from_async  THE SAME SOLVE FROM AN INITIAL GUESS y0 (N doubles on the device, read only); y0 == NULL is
+ *                         fd_jfnk_solve_async itself (the same launches, the same bits).  y0 may be y (continued in place), b or x; y may
+ *                         be b, not x: y is written by the solve's last kernel alone.  The rules of fd_csc_solve_from_async hold with
+ *                         w = A(x) y0, ONE application of the operator (the dot's order by fd_jvp_async's rule on x and y0 as they sit):
+ *                         it is no iteration, but counts in fd_jfnk_solver_counts as one application; f(x) is still evaluated once per
+ *                         call (forward arm, f_in NULL) and serves the start and the steps.  Launches: the cold start's, the
+ *                         application's own, and one kernel (r0, the iterate, ||r0||^2).  Once the opening kernel has ended the solve
+ *                         (b = 0, a bad d_e or factorisation, ||b||^2 not finite) nothing of y0 is applied and resid is ||b||_2 as in
+ *                         the cold start; WITH A PRECONDITIONER SET THE CALL SYNCHRONISES ONCE behind that kernel, so that such a solve
+ *                         enqueues and counts neither the application nor f(x); without one the application is enqueued, counted and
+ *                         ignored.  The generation checks on a lent factorisation run before anything is enqueued, as above.
  *   fd_jfnk_solver_status  synchronises; flags (bit 0: the iterations ran out; bit 1: breakdown), iterations, the last estimate, ||b||_2.
  *                         After a failure y is NaN unless fd_jfnk_solver_set_policy(solver, 1).
  *   fd_jfnk_solver_counts  operator applications and base evaluations enqueued since creation.
@@ -892,6 +920,8 @@ int fd_jfnk_apply_async(fd_jfnk_solver *solver, double alpha, double beta, fd_f_
                         const void *z, void *w);
 int fd_jfnk_solve_async(fd_jfnk_solver *solver, double alpha, double beta, fd_f_launch f, void *fctx, const void *x, const void *f_in,
                         const void *b, void *y);
+int fd_jfnk_solve_from_async(fd_jfnk_solver *solver, double alpha, double beta, fd_f_launch f, void *fctx, const void *x, const void *f_in,
+                             const void *b, const void *y0, void *y);
 int fd_jfnk_solver_status(fd_jfnk_solver *solver, int *flags, int64_t *iterations, double *resid, double *bnorm);
 int fd_jfnk_solver_counts(fd_jfnk_solver *solver, int64_t *applications, int64_t *base_evaluations);
 int fd_jfnk_solver_basis(fd_jfnk_solver *solver, const void **V_dev, const void **H_dev, int *restart, int *last_cycle_len);
@@ -1238,6 +1268,7 @@ int fd32_csc_matvec_async(fd32_csc_solver *solver, double alpha, double beta, co
 int fd32_csc_solver_set_options(fd32_csc_solver *solver, double rtol, int max_iterations);
 int fd32_csc_solver_set_policy(fd32_csc_solver *solver, int keep_unconverged);
 int fd32_csc_solve_async(fd32_csc_solver *solver, double alpha, double beta, const void *nzval, const void *b, void *y);
+int fd32_csc_solve_from_async(fd32_csc_solver *solver, double alpha, double beta, const void *nzval, const void *b, const void *y0, void *y);
 int fd32_csc_solver_status(fd32_csc_solver *solver, int *flags_out, int64_t *iterations_out, double *resid_out, double *bnorm_out);
 int fd32_csc_solver_row_lists(fd32_csc_solver *solver, const void **row_ptr, const void **row_col, const void **row_slot, const void **diag_slot,
                             int64_t *nnz_out, int64_t *long_rows_out);

@@ -243,19 +243,7 @@ def test_user_examples_cross_compile_against_the_public_headers_only(tmp_path):
                                "-o", str(tmp_path / (name + ".o"))])
 
 
-def _np_fingerprint(values, base=0):
-    # F(a) = sum_k mix(v_2k + (v_2k+1 << 32) + k*K) mod 2^64, mix(z) = (z ^ z >> 29) * C, ^ >> 32; a missing last partner = 0x7fffffff
-    # (csc/fdjac_match.hip), restated with numpy uint64 arithmetic
-    with np.errstate(over="ignore"):
-        v = (np.asarray(values, dtype=np.int64) - base).astype(np.uint64)
-        if v.size % 2:
-            v = np.concatenate([v, np.array([0x7fffffff], dtype=np.uint64)])
-        v0, v1 = v[0::2], v[1::2]
-        k = np.arange(v0.size, dtype=np.uint64)
-        z = v0 + (v1 << np.uint64(32)) + k * np.uint64(0xD6E8FEB86659FD93)
-        z = (z ^ (z >> np.uint64(29))) * np.uint64(0xBF58476D1CE4E5B9)
-        z = z ^ (z >> np.uint64(32))
-        return int(np.sum(z, dtype=np.uint64))
+from fingerprint_model import fingerprint as _np_fingerprint      # (csrc/fdjac_match.hip restated with numpy uint64 arithmetic)
 
 
 def test_pattern_fingerprint_host_path(L):

@@ -872,29 +872,32 @@ class CscTrustRegion(_CscConsumer):
                 "pred": pr.value}
 
 
-class JfnkSolver:
-    """fd_jfnk_solver: the matrix-free consumer.  ``solve`` enqueues y = (alpha*I + beta*J(x))^-1 b by restarted GMRES(``restart``) whose
-    product is the finite-difference JVP of ``f`` at ``x`` -- J is never stored, so f needs no pattern and no colouring -- and ``apply``
-    enqueues w = alpha*z + beta*J(x) z.  Float64, square f (M = N), device arrays.  ``f`` is a ``BuiltinF``, a compiled functor (``JitF``
-    ...) or a raw ``(launcher, context)`` pair, as ``finite_difference_jvp_b`` takes them; ``set_lazy(f)`` installs f's lazy JVP launcher.
-    A solve that runs out of iterations (``status()`` flags bit 0) or breaks down (bit 1) fills y with NaN unless ``set_policy(True)``."""
+class _MatrixFreeConsumer:
+    """What JfnkSolver and JfTrustRegion share: the handle, the marshalling of device vectors of N doubles and of ``f``, and the calls that
+    differ only in the C prefix."""
+    _prefix = None      # "fd_jfnk_solver" / "fd_jftr": <prefix>_create, _destroy, _set_options, _set_policy, _set_steps, _set_lazy_f
+    _noun = None        # in "the <noun> takes device arrays"
 
-    def __init__(self, N, fdtype="forward", restart=30, ctx=None):
+    def _create(self, N, fdtype, ctx, *more):
+        """<prefix>_create(ctx, N, fdtype, *more, &handle)."""
         self.ctx = ctx or Context.default()
         self.N, self.fdtype = int(N), _norm_fdtype(fdtype)
         self.dtype = np.dtype(np.float64)
         h = C.c_void_p()
-        _l.check(self.ctx.L.fd_jfnk_solver_create(self.ctx.handle, self.N, _l.FDTYPES[self.fdtype], int(restart), C.byref(h)))
+        _l.check(self._c("_create")(self.ctx.handle, self.N, _l.FDTYPES[self.fdtype], *more, C.byref(h)))
         self.handle = h
-        self._fin = weakref.finalize(self, self.ctx.L.fd_jfnk_solver_destroy, h)
+        self._fin = weakref.finalize(self, self._c("_destroy"), h)
         self._lazy_keep = self._diag_keep = None
+
+    def _c(self, suffix):
+        return getattr(self.ctx.L, self._prefix + suffix)
 
     def _dev(self, a, what):
         if a is None:
             return None
         p, k, _keep = _ptr(a, what, self.dtype)
         if k != _l.DEVICE:
-            raise ValueError("the matrix-free solver takes device arrays")
+            raise ValueError("the %s takes device arrays" % self._noun)
         if int(np.prod(a.shape)) != self.N:
             raise ValueError("%s must hold N = %d elements" % (what, self.N))      # DimensionMismatch
         return p
@@ -907,16 +910,49 @@ class JfnkSolver:
             raise TypeError("the matrix-free solver is Float64 only")
         return f.fn, f.fctx
 
+    def _checked(self, f, rc):
+        """The launcher's stored error (a Python f that raised) before the C call's own code."""
+        err = getattr(f, "error", None)
+        if err is not None:
+            f.error = None
+            raise err
+        _l.check(rc)
+
     def set_options(self, rtol=1e-10, max_iterations=500):
-        _l.check(self.ctx.L.fd_jfnk_solver_set_options(self.handle, float(rtol), int(max_iterations)))
+        _l.check(self._c("_set_options")(self.handle, float(rtol), int(max_iterations)))
 
     def set_policy(self, keep_unconverged):
-        _l.check(self.ctx.L.fd_jfnk_solver_set_policy(self.handle, 1 if keep_unconverged else 0))
+        _l.check(self._c("_set_policy")(self.handle, 1 if keep_unconverged else 0))
 
     def set_steps(self, relstep=None, absstep=None, dir=True):
         """The JVP's steps as ``finite_difference_jvp_b`` takes them (None: the defaults)."""
-        _l.check(self.ctx.L.fd_jfnk_solver_set_steps(self.handle, -1.0 if relstep is None else float(relstep),
-                                                     -1.0 if absstep is None else float(absstep), float(dir)))
+        _l.check(self._c("_set_steps")(self.handle, -1.0 if relstep is None else float(relstep), -1.0 if absstep is None else float(absstep),
+                                       float(dir)))
+
+    def set_lazy(self, f=None, quotient=True):
+        """Install ``f``'s lazy JVP launcher (``f.lazy_jvp_fn``; a raw launcher is taken as it is, with ``quotient`` as its capability
+        bits) or, with None or an f that has none, clear it.  ``quotient=False``: the launcher writes values, never the quotient."""
+        if f is not None and not hasattr(f, "lazy_jvp_fn") and not isinstance(f, _l.F_LAUNCH_LAZY_JVP):
+            f = None
+        if isinstance(f, _l.F_LAUNCH_LAZY_JVP):
+            lz, caps = f, int(quotient)
+        else:
+            lz = getattr(f, "lazy_jvp_fn", None) if f is not None else None
+            caps = int(getattr(f, "lazy_jvp_caps", 0)) if (lz is not None and quotient) else 0
+        self._lazy_keep = lz            # (the ctypes function object must outlive the calls)
+        _l.check(self._c("_set_lazy_f")(self.handle, lz if lz is not None else _l.F_LAUNCH_LAZY_JVP(), caps if lz is not None else 0))
+
+
+class JfnkSolver(_MatrixFreeConsumer):
+    """fd_jfnk_solver: the matrix-free consumer.  ``solve`` enqueues y = (alpha*I + beta*J(x))^-1 b by restarted GMRES(``restart``) whose
+    product is the finite-difference JVP of ``f`` at ``x`` -- J is never stored, so f needs no pattern and no colouring -- and ``apply``
+    enqueues w = alpha*z + beta*J(x) z.  Float64, square f (M = N), device arrays.  ``f`` is a ``BuiltinF``, a compiled functor (``JitF``
+    ...) or a raw ``(launcher, context)`` pair, as ``finite_difference_jvp_b`` takes them; ``set_lazy(f)`` installs f's lazy JVP launcher.
+    A solve that runs out of iterations (``status()`` flags bit 0) or breaks down (bit 1) fills y with NaN unless ``set_policy(True)``."""
+    _prefix, _noun = "fd_jfnk_solver", "matrix-free solver"
+
+    def __init__(self, N, fdtype="forward", restart=30, ctx=None):
+        self._create(N, fdtype, ctx, int(restart))
 
     def set_diagonal(self, d):
         """N doubles on the device, the right preconditioner M = diag(d), read by every solve (the array is kept alive); None: none."""
@@ -933,27 +969,9 @@ class JfnkSolver:
         _l.check(self.ctx.L.fd_jfnk_solver_set_csc_preconditioner(self.handle, None if csc_solver is None else csc_solver.handle))
         self._pc_keep = csc_solver
 
-    def set_lazy(self, f=None, quotient=True):
-        """Install ``f``'s lazy JVP launcher (``f.lazy_jvp_fn``; a raw launcher is taken as it is, with ``quotient`` as its capability
-        bits) or, with None or an f that has none, clear it.  ``quotient=False``: the launcher writes values, never the quotient."""
-        if f is not None and not hasattr(f, "lazy_jvp_fn") and not isinstance(f, _l.F_LAUNCH_LAZY_JVP):
-            f = None
-        if isinstance(f, _l.F_LAUNCH_LAZY_JVP):
-            lz, caps = f, int(quotient)
-        else:
-            lz = getattr(f, "lazy_jvp_fn", None) if f is not None else None
-            caps = int(getattr(f, "lazy_jvp_caps", 0)) if (lz is not None and quotient) else 0
-        self._lazy_keep = lz            # (the ctypes function object must outlive the calls)
-        _l.check(self.ctx.L.fd_jfnk_solver_set_lazy_f(self.handle, lz if lz is not None else _l.F_LAUNCH_LAZY_JVP(), caps if lz is not None else 0))
-
     def _call(self, entry, f, x, f_in, a, b, alpha, beta, *more):
         fn, fctx = self._launcher(f)
-        rc = entry(self.handle, float(alpha), float(beta), fn, fctx, self._dev(x, "x"), self._dev(f_in, "f_in"), a, b, *more)
-        err = getattr(f, "error", None)
-        if err is not None:
-            f.error = None
-            raise err
-        _l.check(rc)
+        self._checked(f, entry(self.handle, float(alpha), float(beta), fn, fctx, self._dev(x, "x"), self._dev(f_in, "f_in"), a, b, *more))
 
     def apply(self, f, x, z, w, alpha=1.0, beta=-1.0, f_in=None):
         """Enqueue w = alpha*z + beta*J(x) z (fd_jfnk_apply_async)."""
@@ -990,70 +1008,22 @@ class JfnkSolver:
         return V, H, k.value
 
 
-class JfTrustRegion:
+class JfTrustRegion(_MatrixFreeConsumer):
     """fd_jftr: the matrix-free trust-region consumer.  ``step`` enqueues the Steihaug-Toint truncated-CG solution of
     min g.y + 1/2 y.B y, ||y||_W <= radius, B = lam*I + beta*J(x), where J(x) v is the finite-difference JVP of the gradient ``f`` at ``x``
     -- the Hessian is never stored, so f needs no pattern and no colouring -- and ``apply`` enqueues w = lam*v + beta*J(x) v.  W = I, or
     diag(m) after ``set_diagonal(m)`` (m > 0, which also preconditions).  Float64, square f, device arrays; ``f`` as ``JfnkSolver`` takes
     it.  B is symmetric only up to the quotient's noise.  A step that runs out of iterations (``status()`` flags bit 0) or breaks down
     (bit 1) fills y and r_out with NaN unless ``set_policy(True)``; a step that ends on the boundary is a success."""
+    _prefix, _noun = "fd_jftr", "matrix-free trust-region consumer"
 
     def __init__(self, N, fdtype="forward", ctx=None):
-        self.ctx = ctx or Context.default()
-        self.N, self.fdtype = int(N), _norm_fdtype(fdtype)
-        self.dtype = np.dtype(np.float64)
-        h = C.c_void_p()
-        _l.check(self.ctx.L.fd_jftr_create(self.ctx.handle, self.N, _l.FDTYPES[self.fdtype], C.byref(h)))
-        self.handle = h
-        self._fin = weakref.finalize(self, self.ctx.L.fd_jftr_destroy, h)
-        self._lazy_keep = self._diag_keep = None
-
-    def _dev(self, a, what):
-        if a is None:
-            return None
-        p, k, _keep = _ptr(a, what, self.dtype)
-        if k != _l.DEVICE:
-            raise ValueError("the matrix-free trust-region consumer takes device arrays")
-        if int(np.prod(a.shape)) != self.N:
-            raise ValueError("%s must hold N = %d elements" % (what, self.N))      # DimensionMismatch
-        return p
-
-    _launcher = staticmethod(JfnkSolver._launcher)
-
-    def set_options(self, rtol=1e-10, max_iterations=500):
-        _l.check(self.ctx.L.fd_jftr_set_options(self.handle, float(rtol), int(max_iterations)))
-
-    def set_policy(self, keep_unconverged):
-        _l.check(self.ctx.L.fd_jftr_set_policy(self.handle, 1 if keep_unconverged else 0))
-
-    def set_steps(self, relstep=None, absstep=None, dir=True):
-        """The JVP's steps as ``finite_difference_jvp_b`` takes them (None: the defaults)."""
-        _l.check(self.ctx.L.fd_jftr_set_steps(self.handle, -1.0 if relstep is None else float(relstep),
-                                              -1.0 if absstep is None else float(absstep), float(dir)))
+        self._create(N, fdtype, ctx)
 
     def set_diagonal(self, m):
         """N doubles on the device, m > 0: W = diag(m), norm and preconditioner of every step (the array is kept alive); None: W = I."""
         self._diag_keep = m
         _l.check(self.ctx.L.fd_jftr_set_diagonal(self.handle, self._dev(m, "m")))
-
-    def set_lazy(self, f=None, quotient=True):
-        """Install ``f``'s lazy JVP launcher, as ``JfnkSolver.set_lazy``."""
-        if f is not None and not hasattr(f, "lazy_jvp_fn") and not isinstance(f, _l.F_LAUNCH_LAZY_JVP):
-            f = None
-        if isinstance(f, _l.F_LAUNCH_LAZY_JVP):
-            lz, caps = f, int(quotient)
-        else:
-            lz = getattr(f, "lazy_jvp_fn", None) if f is not None else None
-            caps = int(getattr(f, "lazy_jvp_caps", 0)) if (lz is not None and quotient) else 0
-        self._lazy_keep = lz            # (the ctypes function object must outlive the calls)
-        _l.check(self.ctx.L.fd_jftr_set_lazy_f(self.handle, lz if lz is not None else _l.F_LAUNCH_LAZY_JVP(), caps if lz is not None else 0))
-
-    def _checked(self, f, rc):
-        err = getattr(f, "error", None)
-        if err is not None:
-            f.error = None
-            raise err
-        _l.check(rc)
 
     def apply(self, f, x, v, w, lam=0.0, beta=1.0, f_in=None):
         """Enqueue w = lam*v + beta*J(x) v (fd_jftr_apply_async)."""

@@ -364,7 +364,8 @@ struct CscHandle {
         return FD_OK;
     }
 };
-// create: init(handle) builds it; after a failure nothing is left allocated
+// create: init(handle) builds it; after a failure nothing is left allocated.  H: a CscHandle, or the matrix-free consumers' MfHandle
+// (fdjac_mf_common.h) -- anything with a ctx that is NULL until it may be used, and a destructor that takes a half-built object
 template <class H, class F> int csc_handle_create(H **out, F init)
 {
     FD_REQUIRE(out != nullptr, FD_ERR_ARG, "NULL argument");

@@ -26,6 +26,7 @@
 //   k_gm_close          converged, broken down or out of iterations: `done`; otherwise the next cycle starts (above)
 // Nothing but the record of a batch goes to the host.  Launches per step: 10 (+ 1 with long rows); per cycle end: 8 (diagonal) or 10.
 #pragma once
+#include "fdjac_dotx.h"
 
 namespace fdjac {
 
@@ -45,12 +46,6 @@ struct CsGm {                          // the buffers of a GMRES solve as the ke
 };
 __device__ __forceinline__ bool gm_idle(const int *words) { return cs_word(words, W_DONE) || cs_word(words, W_EARLY); }
 __device__ __forceinline__ bool gm_ending(const int *words) { return cs_word(words, W_EARLY) && !cs_word(words, W_DONE); }
-__device__ __forceinline__ double gm_wave_sum(double x)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x = x + __shfl_down(x, off, 64);
-    return x;
-}
 // what _final does in the model: thread t adds part[t], part[t + 256], ... in order, then block_sum()
 __device__ __forceinline__ double gm_final_sum(const double *part, int n, double *s_w)
 {
@@ -88,7 +83,7 @@ __global__ void __launch_bounds__(kBlock) k_cs_gs_dots(int N, int nv, const doub
             double acc = 0.0;
 #pragma unroll
             for (int k = 0; k < kGsPer; ++k) acc += we[k] * ve[a][k];
-            acc = gm_wave_sum(acc);
+            acc = wave_sum(acc);      // (fdjac_dotx.h)
             if ((threadIdx.x & 63) == 0 && i0 + a < nv) s_ws[(i0 + a) * (kBlock / 64) + (threadIdx.x >> 6)] = acc;
         }
     }

@@ -39,6 +39,34 @@ static_assert(W_EXIT < W_NWORDS, "no free word");
 
 struct TrVecs { double *r, *q, *y, *p, *z, *m; };      // N doubles each
 
+// The step length and the exit of an iteration from kappa = p.q: taken by the last-arriving thread of the kernel that closes the product,
+// k_tr_rows<1> here and k_jt_close<true> of the matrix-free consumer (fdjac_jftr.hip).
+__device__ __forceinline__ void tr_decide(double kappa, double delta2, double *scal, int *words)
+{
+    const double ppp = scal[TR_PPP], pyp = scal[TR_PYP], pyy = scal[TR_PYY];
+    const double d = delta2 - pyy;
+    const double tau = d / (pyp + __dsqrt_rn(pyp * pyp + ppp * d));      // the root without cancellation (pi_yp >= 0)
+    if (cs_not_finite(kappa)) {
+        cs_breakdown(words);
+    } else if (kappa <= 0.0) {
+        if (cs_not_finite(delta2)) {          // negative curvature and no boundary to follow it to
+            words[W_EXIT] = 3;
+            cs_breakdown(words);
+        } else {
+            words[W_EXIT] = 2;
+            scal[TR_ALPHA] = tau;
+        }
+    } else {
+        const double al = scal[TR_GAMMA] / kappa;
+        if (pyy + 2.0 * al * pyp + al * al * ppp >= delta2) {
+            words[W_EXIT] = 1;
+            scal[TR_ALPHA] = tau;
+        } else {
+            scal[TR_ALPHA] = al;
+        }
+    }
+}
+
 // ---- the product -----------------------------------------------------------------------------------------------------------------------
 // The long rows first (k_cs_long<false, CS_LONG_SUM>), then the rows: a tile of 256 rows per workgroup, lane i takes row
 // row_order[tile * 256 + i]; v is read from memory; the sums cross LDS once (cs_tile_lines) so that y = sum + lambda v is written -- and
@@ -62,53 +90,25 @@ __global__ void __launch_bounds__(kBlock) k_tr_rows(CsView P, const double *__re
     }
     if (MODE == 1) {
         double mine[1] = {vr * yr}, tot[1];
-        if (cs_finish<1>(mine, part, words, tot, s_w) && threadIdx.x == 0) {
-            const double kappa = tot[0];
-            const double ppp = scal[TR_PPP], pyp = scal[TR_PYP], pyy = scal[TR_PYY];
-            const double d = delta2 - pyy;
-            const double tau = d / (pyp + __dsqrt_rn(pyp * pyp + ppp * d));      // the root without cancellation (pi_yp >= 0)
-            if (cs_not_finite(kappa)) {
-                cs_breakdown(words);
-            } else if (kappa <= 0.0) {
-                if (cs_not_finite(delta2)) {          // negative curvature and no boundary to follow it to
-                    words[W_EXIT] = 3;
-                    cs_breakdown(words);
-                } else {
-                    words[W_EXIT] = 2;
-                    scal[TR_ALPHA] = tau;
-                }
-            } else {
-                const double al = scal[TR_GAMMA] / kappa;
-                if (pyy + 2.0 * al * pyp + al * al * ppp >= delta2) {
-                    words[W_EXIT] = 1;
-                    scal[TR_ALPHA] = tau;
-                } else {
-                    scal[TR_ALPHA] = al;
-                }
-            }
-        }
+        if (cs_finish<1>(mine, part, words, tot, s_w) && threadIdx.x == 0) tr_decide(tot[0], delta2, scal, words);
     }
 }
 
 // ---- the vector kernels ----------------------------------------------------------------------------------------------------------------
-// the start of a solve
-__global__ void __launch_bounds__(kBlock) k_tr_start(CsView P, int kind, const double *__restrict__ nz, const double *__restrict__ g, TrVecs V,
-                                                     double lambda, double rtol, double *scal, int *words, double *part)
+// The start of a solve, for this consumer and the matrix-free one (k_jt_start, fdjac_jftr.hip).  weight(i, bad) returns m_i and sets
+// bad where that consumer's test on it fails.
+template <class FW>
+__device__ __forceinline__ void tr_start_body(int N, const double *__restrict__ g, const TrVecs &V, double rtol, double *scal, int *words, double *part,
+                                              double *s_w, FW weight)
 {
-    __shared__ double s_w[kBlock / 64];
     const int i0 = blockIdx.x * kCsVecTile + threadIdx.x;
     double mine[3] = {0.0, 0.0, 0.0}, tot[3];
     bool bad = false;
 #pragma unroll
     for (int k = 0; k < kCsVecTile / kBlock; ++k) {
         const int i = i0 + k * kBlock;
-        if (i >= P.N) continue;
-        double m = 1.0;
-        if (kind) {
-            const int s = P.diag[i];
-            m = fabs(s >= 0 ? nz[s] : 0.0) + lambda;
-            bad = bad || cs_bad_pivot(m);
-        }
+        if (i >= N) continue;
+        const double m = weight(i, bad);
         const double r = g[i];
         const double z = r / m;
         const double p = -z;
@@ -122,10 +122,23 @@ __global__ void __launch_bounds__(kBlock) k_tr_start(CsView P, int kind, const d
         scal[TR_TOL2] = (rtol * rtol) * tot[1];
         int done = 0;
         if (tot[1] == 0.0) done = 1;                                             // g = 0: y = 0, no iteration
-        else if (cs_word(words, W_FLAGS) & 2) done = 1;                          // an m_j that is zero or not finite
+        else if (cs_word(words, W_FLAGS) & 2) done = 1;                          // an m_j that failed the consumer's test
         else if (cs_not_finite(tot[0])) { atomicOr(words + W_FLAGS, 2); done = 1; }   // gamma
         if (done) __hip_atomic_store(words + W_DONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
+}
+// ... with m_j = |H_jj| + lambda (kind 1: zero or not finite is a breakdown), or 1
+__global__ void __launch_bounds__(kBlock) k_tr_start(CsView P, int kind, const double *__restrict__ nz, const double *__restrict__ g, TrVecs V,
+                                                     double lambda, double rtol, double *scal, int *words, double *part)
+{
+    __shared__ double s_w[kBlock / 64];
+    tr_start_body(P.N, g, V, rtol, scal, words, part, s_w, [&](int i, bool &bad) {
+        if (!kind) return 1.0;
+        const int s = P.diag[i];
+        const double m = fabs(s >= 0 ? nz[s] : 0.0) + lambda;
+        bad = bad || cs_bad_pivot(m);
+        return m;
+    });
 }
 // y = y + alpha p, r = r + alpha q, z = r / m, gamma' = r.z, rho = r.r
 __global__ void __launch_bounds__(kBlock) k_tr_update(int N, TrVecs V, double *scal, int *words, double *part)

@@ -23,15 +23,9 @@
 // (FD_ERR_COMM from the next call) and stores NaNs instead of hanging the device.
 #pragma once
 #include "fdjac_internal.h"
+#include "fdjac_dotx.h"      // wave_sum
 
 namespace fdjac {
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
 
 template <typename CT> __device__ __forceinline__ void load_color_pair(const CT *p, int &c0, int &c1);
 template <> __device__ __forceinline__ void load_color_pair<uint8_t>(const uint8_t *p, int &c0, int &c1)

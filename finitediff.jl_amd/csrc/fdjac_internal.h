@@ -586,7 +586,7 @@ struct fd_plan {
     std::vector<float> samples[FD_NSTAGES];    // the individual spans (fd_plan_get_timing_samples), capped
 };
 
-// ---- the JVP plan (fdjac_jvp.hip) and the way into jvp_enqueue's pieces for a caller inside the library (fdjac_jfnk.hip) ----------
+// ---- the JVP plan (fdjac_jvp.hip) and the way into jvp_enqueue's pieces for a caller inside the library (fdjac_mf_common.h) ----
 struct fd_jvp_plan {
     fd_ctx *ctx = nullptr;
     int fdtype = 0;

@@ -1,47 +1,43 @@
 // The MATRIX-FREE consumer (fd_jfnk_*): (alpha I + beta J(x)) y = b by the restarted GMRES of fdjac_cscgmres.hip on the
 // operator itself,  A(x) z = alpha z + beta q,  q = the finite-difference JVP of fdjac_jvp.hip for (x, z) -- no pattern, no colouring, no
 // stored J.  A piece of fdjac_cscsolve.hip (included there, in the Float64 build only): the GMRES kernels, CscSolveState, the words and
-// the scalars are that file's, the host loop is csc_gmres_iterate(); the JVP's launches are jvp_enqueue's, entered through JvpHooks
-// (fdjac_internal.h).  tests/jfnk_model.py restates every order in numpy and the GPU tests compare bits.
+// the scalars are that file's, the host loop is csc_gmres_iterate(); the handle's scaffold and the way into jvp_enqueue (JvpHooks) are
+// MfHandle's (fdjac_mf_common.h), shared with fdjac_jftr.hip.  tests/jfnk_model.py restates every order in numpy and the GPU tests
+// compare bits.
 //
 // THE OPERATOR.  q is what fd_jvp_async gives for (x, z) with the solver's steps and fdtype, on whichever route jvp_enqueue takes (small,
 // materialised, lazy values, lazy quotient); then w_e = alpha z_e + beta q_e, two multiplications and one addition.  The closing kernel
 // k_jf_close forms the quotient as k_jvp_diff does and the combination in the same pass: it stands where k_jvp_diff stood.
 // THE STEP'S z.  With a diagonal d (right preconditioner M = diag(d)) and N above kSmallN, k_jf_open reads x, v_j and d once, stores
-// z = v_j / d and leaves the partial sums of dot(x, z) on k_dot_partial's grid and in its per-thread order; k_jvp_eps takes them as they
-// are.  The order is the paired one when x is aligned to a pair (z is the solver's own and always is): jvp_enqueue's rule on (x, z),
-// wherever v_j = V + j N and d sit -- off a pair they are read element by element.  Up to kSmallN: k_gm_scale<true>, then k_jvp_small.
-// Without a diagonal z is v_j in place and the JVP's own dot reads it there: for an odd N its variant alternates with j.
+// z = v_j / d and leaves the partial sums of dot(x, z) on k_dot_partial's grid and in its order (fdjac_dotx.h: one traversal, one tail);
+// k_jvp_eps takes them as they are.  The order is the paired one when x is aligned to a pair (z is the solver's own and always is):
+// jvp_enqueue's rule on (x, z), wherever v_j = V + j N and d sit -- off a pair they are read element by element.  Up to kSmallN:
+// k_gm_scale<true>, then k_jvp_small.  Without a diagonal z is v_j in place and the JVP's own dot reads it there: for an odd N its
+// variant alternates with j.
 // A LENT FACTORISATION (fd_jfnk_solver_set_csc_preconditioner): M is what a sparse consumer's fd_csc_solver_factor_async last built --
 // lagged by design, checked for validity before anything is enqueued.  Its Jacobi kind IS the diagonal path on the factored diagonal;
 // block ILU applies with the lender's k_cs_ilu_apply and leaves the dot to the JVP; block Jacobi above kSmallN runs k_jf_open_blocks,
 // k_jf_open with k_cs_bapply's sum in place of the division (up to kSmallN: k_cs_bapply, then k_jvp_small).  The cycle's end is the
 // sparse consumer's: k_gm_combine<0>, the apply, k_gm_yadd.  tests/jfnk_pc_model.py composes the existing models of all of it.
-// THE REST is the sparse consumer's GMRES word for word: y0 = 0 (or the caller's: fd_jfnk_solve_from_async, k_jf_from below), CGS2,
-// the rotations, the back substitution, the restart through the
-// same operator (r = b - A(x) y), flags, NaN in y after a failure unless the policy keeps the iterate.
+// THE REST is the sparse consumer's GMRES (csc_gmres_iterate): y0 = 0 (or the caller's: fd_jfnk_solve_from_async, k_jf_from below),
+// CGS2, the rotations, the back substitution, the restart through the same operator (r = b - A(x) y), flags, NaN in y after a failure
+// unless the policy keeps the iterate.
 // After `cycle over` the kernels here do nothing (gm_idle), but the caller's f! is still launched by the steps already enqueued: what it
 // writes is scratch that nothing reads.
 #pragma once
+#include "fdjac_mf_common.h"
 
-struct fd_jfnk_solver {
-    fd_ctx *ctx = nullptr;
-    int64_t N = 0, ld = 0;             // ld: N rounded up to 32 (every vector of d_vec starts on a pair)
-    int fdtype = FD_FORWARD, m = 30;
-    fdjac::CscSolveState S;
-    fd_jvp_plan *jp = nullptr;
-    double *d_vec = nullptr;           // r | z | w | u | y | fx: ld doubles each
+struct fd_jfnk_solver : fdjac::MfHandle {      // d_vec: r | z | w | u | y | fx
+    int m = 30;                        // the restart
     double *d_gm = nullptr;            // fdjac_cscgmres.hip: CsGm
-    const double *d_diag = nullptr;    // the caller's diagonal, or NULL
-    fd_csc_solver *pc = nullptr;       // a sparse consumer's handle lent as the right preconditioner, or NULL (never both)
-    double relstep = -1.0, absstep = -1.0, dir = 1.0;
-    int64_t applications = 0, base_evaluations = 0;
-    bool have_state = false;
+    fd_csc_solver *pc = nullptr;       // a sparse consumer's handle lent as the right preconditioner, or NULL (never with d_diag)
+    int64_t applications = 0;
+    ~fd_jfnk_solver() { if (d_gm) (void)hipFree(d_gm); }
 };
 
 namespace fdjac {
 
-// z = v / d, and this workgroup's sum of x_i z_i in k_dot_partial<PAIRED>'s order (fdjac_jvp.hip): the same loop, the same shuffle tree.
+// z = v / d, and this workgroup's sum of x_i z_i in k_dot_partial<PAIRED>'s order: dotx_for_each and dotx_finish, as there.
 // PAIRED is jvp_enqueue's own rule on the operands of the dot (x and z on a pair), so q is what fd_jvp_async gives for (x, z) wherever
 // v and d sit; VLOAD: v and d are on a pair too and are read 16 bytes at a time, otherwise element by element (the same values).
 template <bool PAIRED, bool VLOAD>
@@ -50,11 +46,9 @@ __global__ void __launch_bounds__(kBlock) k_jf_open(const double *__restrict__ x
 {
     if (gm_idle(words)) return;
     typedef double d2_t __attribute__((ext_vector_type(2)));
-    double acc = 0.0;
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    if (PAIRED) {
-        const int64_t n2 = n >> 1;
-        for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n2; i += stride) {
+    double acc[1] = {0.0};
+    dotx_for_each<PAIRED>(n,
+        [&](int64_t i) {
             const d2_t a = reinterpret_cast<const d2_t *>(x)[i];
             d2_t b, c;
             if (VLOAD) {
@@ -66,38 +60,25 @@ __global__ void __launch_bounds__(kBlock) k_jf_open(const double *__restrict__ x
             }
             const d2_t q = {b.x / c.x, b.y / c.y};
             reinterpret_cast<d2_t *>(z)[i] = q;
-            acc += a.x * q.x;
-            acc += a.y * q.y;
-        }
-        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-            const double q = v[n - 1] / d[n - 1];
-            z[n - 1] = q;
-            acc += x[n - 1] * q;
-        }
-    } else {
-        for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+            acc[0] += a.x * q.x;
+            acc[0] += a.y * q.y;
+        },
+        [&](int64_t i) {
             const double q = v[i] / d[i];
             z[i] = q;
-            acc += x[i] * q;
-        }
-    }
-    __shared__ double red[kBlock / 64];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int w = 0; w < kBlock / 64; ++w) t += red[w];
-        partial[blockIdx.x] = t;
-    }
+            acc[0] += x[i] * q;
+        });
+    __shared__ double red[1][kBlock / 64];
+    dotx_finish<1>(acc, red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = acc[0];
 }
 
 // z = Minv v over the block-Jacobi planes of a lent fd_csc_solver (k_cs_bapply's sum: from +0.0, c ascending, one multiply and one add,
 // short last block), and this workgroup's sum of x_i z_i in k_dot_partial<PAIRED>'s order, on its grid.  Trip k of workgroup b covers
 // the consecutive elements that k_dot_partial gives the workgroup on that trip: 512 from 2 (b 256 + k stride) when PAIRED (a
 // pair per thread, z stored 16 bytes at a time), 256 from b 256 + k stride otherwise (x off a pair).  v for that range, widened to
-// whole blocks, goes through LDS element by element wherever it sits.  The odd-N tail is thread 0 of workgroup 0's, as in k_jf_open.
+// whole blocks, goes through LDS element by element wherever it sits.  The trips must be the same in every thread (barriers), so the loop
+// is this kernel's own; the odd-N tail is thread 0 of workgroup 0's and the sum's tail is dotx_finish, as in k_jf_open.
 template <bool PAIRED>
 __global__ void __launch_bounds__(kBlock) k_jf_open_blocks(const double *__restrict__ x, const double *__restrict__ v, const double *__restrict__ minv,
                                                            int bs, int64_t n, double *__restrict__ z, double *__restrict__ partial, const int *words)
@@ -106,7 +87,7 @@ __global__ void __launch_bounds__(kBlock) k_jf_open_blocks(const double *__restr
     __shared__ double s_v[2 * kBlock + 2 * (kCsBsMax - 1)];
     if (gm_idle(words)) return;
     typedef double d2_t __attribute__((ext_vector_type(2)));
-    double acc = 0.0;
+    double acc[1] = {0.0};
     const int64_t stride = (int64_t)gridDim.x * kBlock;
     const int64_t nloop = PAIRED ? (n >> 1) : n;                  // pairs, or elements
     // one element of z: its block's row of Minv times the block's v (from LDS: `sv` holds v from element w0 on)
@@ -132,12 +113,12 @@ __global__ void __launch_bounds__(kBlock) k_jf_open_blocks(const double *__restr
                 const d2_t a = reinterpret_cast<const d2_t *>(x)[i];
                 const d2_t q = {row(2 * i, s_v, w0), row(2 * i + 1, s_v, w0)};
                 reinterpret_cast<d2_t *>(z)[i] = q;
-                acc += a.x * q.x;
-                acc += a.y * q.y;
+                acc[0] += a.x * q.x;
+                acc[0] += a.y * q.y;
             } else {
                 const double q = row(i, s_v, w0);
                 z[i] = q;
-                acc += x[i] * q;
+                acc[0] += x[i] * q;
             }
         }
         __syncthreads();
@@ -147,18 +128,11 @@ __global__ void __launch_bounds__(kBlock) k_jf_open_blocks(const double *__restr
         double q = 0.0;
         for (int c = 0; c < (int)(n - b0); ++c) q += minv[(size_t)c * (size_t)n + e] * v[b0 + c];
         z[e] = q;
-        acc += x[e] * q;
+        acc[0] += x[e] * q;
     }
-    __shared__ double red[kBlock / 64];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int w = 0; w < kBlock / 64; ++w) t += red[w];
-        partial[blockIdx.x] = t;
-    }
+    __shared__ double red[1][kBlock / 64];
+    dotx_finish<1>(acc, red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = acc[0];
 }
 
 // w = alpha z + beta q with q = (a - b) / e, e = eps[0] or 2 eps[0] exactly as k_jvp_diff forms it; b == NULL: a holds q already (a lazy
@@ -285,23 +259,10 @@ static int jf_operator(fd_jfnk_solver *s, double alpha, double beta, fd_f_launch
                        const double *z, double *w, bool have_partials, const int *words, int mode)
 {
     JfOp op = {s, alpha, beta, z, w, words, mode};
-    JvpHooks hk = {have_partials, own_base, &op, jf_close};
     s->applications += 1;
-    return jvp_enqueue_hooked(s->jp, f, fctx, x, z, fin, s->relstep, s->absstep, s->dir, w, &hk);
+    return s->enqueue(f, fctx, x, z, fin, own_base, w, have_partials, &op, jf_close);
 }
-// f(x) once per call in the forward arm without f_in: one launch of f!
-static int jf_base(fd_jfnk_solver *s, fd_f_launch f, void *fctx, const double *x, const double *f_in, const double **fin, bool *own)
-{
-    *fin = nullptr; *own = false;
-    if (s->fdtype != FD_FORWARD) return FD_OK;
-    if (f_in) { *fin = f_in; return FD_OK; }
-    double *fx = s->d_vec + 5 * s->ld;
-    const int rc = f(fctx, fx, x, 1, s->N, s->ld, 0, s->N, 0, (void *)s->ctx->stream);
-    FD_REQUIRE(rc == 0, FD_ERR_CALLBACK, "f! launcher returned %d", rc);
-    s->base_evaluations += 1;
-    *fin = fx; *own = true;
-    return FD_OK;
-}
+constexpr int kJfBaseSlot = 5;      // d_vec: r | z | w | u | y | fx
 
 }  // namespace fdjac
 
@@ -309,56 +270,20 @@ extern "C" {
 
 int fd_jfnk_solver_create(fd_ctx *ctx, int64_t N, int fdtype, int restart, fd_jfnk_solver **out)
 {
-    // (every range check stands before the first use of ctx: tests/test_jfnk_model_cpu.py sends them a context that is never dereferenced)
-    FD_REQUIRE(ctx && out, FD_ERR_ARG, "NULL argument");
-    *out = nullptr;
-    FD_REQUIRE(N >= 1 && N <= (int64_t)0x7FFFFFFF - kCsVecTile, FD_ERR_SHAPE, "N = %lld (1 .. 2^31 - 1025)", (long long)N);
-    if (fdtype != FD_FORWARD && fdtype != FD_CENTRAL) {
-        set_error("finite_difference_jvp doesn't support :complex-mode finite diff");
-        return FD_ERR_UNSUPPORTED;
-    }
-    FD_REQUIRE(restart >= 1 && restart <= kGmMax, FD_ERR_ARG, "restart = %d (1 .. %d)", restart, kGmMax);
-    FD_HIP_CHECK(hipSetDevice(ctx->device));
-    fd_jfnk_solver *s = new (std::nothrow) fd_jfnk_solver();
-    FD_REQUIRE(s != nullptr, FD_ERR_NOMEM, "out of host memory");
-    s->ctx = ctx; s->N = N; s->ld = (N + 31) / 32 * 32; s->fdtype = fdtype; s->m = restart;
-    const auto build = [&]() -> int {
+    return csc_handle_create(out, [&](fd_jfnk_solver *s) -> int {
         const char *who = "jfnk solver";
-        const int rc = fd_jvp_plan_create(ctx, N, N, fdtype, &s->jp);
+        const int ra = mf_check_args(ctx, N, fdtype);      // (first, as init has them: the restart's check comes after N's and fdtype's)
+        if (ra != FD_OK) return ra;
+        FD_REQUIRE(restart >= 1 && restart <= kGmMax, FD_ERR_ARG, "restart = %d (1 .. %d)", restart, kGmMax);
+        const int rc = s->init(ctx, who, N, fdtype, kJfBaseSlot + 1, S_NSCAL, 2 * (int64_t)cs_tiles(N, kBlock));
         if (rc != FD_OK) return rc;
-        CSC_TRY(who, hipMalloc((void **)&s->d_vec, sizeof(double) * 6 * (size_t)s->ld));
+        s->m = restart;
         CSC_TRY(who, hipMalloc((void **)&s->d_gm, sizeof(double) * gm_doubles((size_t)N, restart, cs_tiles(N, kCsVecTile))));
-        const int rs = s->S.create(who, ctx->stream, S_NSCAL, 2 * (int64_t)cs_tiles(N, kBlock));
-        if (rs != FD_OK) return rs;
-        s->have_state = true;
         return FD_OK;
-    };
-    const int rc = build();
-    if (rc != FD_OK) {
-        (void)hipStreamSynchronize(ctx->stream);
-        s->S.free();
-        if (s->jp) (void)fd_jvp_plan_destroy(s->jp);
-        if (s->d_vec) (void)hipFree(s->d_vec);
-        if (s->d_gm) (void)hipFree(s->d_gm);
-        delete s;
-        return rc;
-    }
-    *out = s;
-    return FD_OK;
+    });
 }
 
-int fd_jfnk_solver_destroy(fd_jfnk_solver *s)
-{
-    if (!s) return FD_OK;
-    (void)hipSetDevice(s->ctx->device);
-    (void)hipStreamSynchronize(s->ctx->stream);
-    s->S.free();
-    (void)fd_jvp_plan_destroy(s->jp);
-    (void)hipFree(s->d_vec);
-    (void)hipFree(s->d_gm);
-    delete s;
-    return FD_OK;
-}
+int fd_jfnk_solver_destroy(fd_jfnk_solver *s) { return csc_handle_destroy(s); }
 
 int fd_jfnk_solver_set_options(fd_jfnk_solver *s, double rtol, int max_iterations)
 {
@@ -375,16 +300,13 @@ int fd_jfnk_solver_set_policy(fd_jfnk_solver *s, int keep_unconverged)
 int fd_jfnk_solver_set_steps(fd_jfnk_solver *s, double relstep, double absstep, double dir)
 {
     FD_REQUIRE(s != nullptr, FD_ERR_ARG, "solver is NULL");
-    s->relstep = relstep; s->absstep = absstep; s->dir = dir;
-    return FD_OK;
+    return s->set_steps(relstep, absstep, dir);
 }
 
 int fd_jfnk_solver_set_lazy_f(fd_jfnk_solver *s, fd_f_launch_lazy_jvp lazy, int caps)
 {
     FD_REQUIRE(s != nullptr, FD_ERR_ARG, "solver is NULL");
-    FD_REQUIRE(lazy != nullptr || caps == 0, FD_ERR_ARG, "no lazy launcher installed");
-    const int rc = fd_jvp_plan_set_lazy_f(s->jp, lazy);
-    return rc != FD_OK ? rc : fd_jvp_plan_set_lazy_caps(s->jp, caps);
+    return s->set_lazy(lazy, caps);
 }
 
 int fd_jfnk_solver_set_diagonal(fd_jfnk_solver *s, const void *d_dev)
@@ -418,7 +340,7 @@ int fd_jfnk_apply_async(fd_jfnk_solver *s, double alpha, double beta, fd_f_launc
     FD_HIP_CHECK(hipSetDevice(s->ctx->device));
     const double *fin;
     bool own;
-    int rc = jf_base(s, f, fctx, (const double *)x, (const double *)f_in, &fin, &own);
+    int rc = s->base(f, fctx, (const double *)x, (const double *)f_in, kJfBaseSlot, &fin, &own);
     if (rc == FD_OK) rc = jf_operator(s, alpha, beta, f, fctx, (const double *)x, fin, own, (const double *)z, (double *)w, false, nullptr, 0);
     if (rc != FD_OK) (void)hipStreamSynchronize(s->ctx->stream);
     return rc;
@@ -447,20 +369,19 @@ int fd_jfnk_solve_from_async(fd_jfnk_solver *s, double alpha, double beta, fd_f_
     hipStream_t st = s->ctx->stream;
     CscSolveState &S = s->S;
     const int N = (int)s->N;
-    const size_t ld = (size_t)s->ld;
     const unsigned gv = cs_tiles(N, kCsVecTile);
     // a lent factorisation: the Jacobi kind IS the diagonal path on the factored diagonal; blocks / ILU go through the lender's applies
     const bool pc_blocks = pc && pc->fact_kind != FD_CSC_PRECOND_JACOBI, pc_bjac = pc && pc->fact_kind == FD_CSC_PRECOND_BLOCK_JACOBI;
     const double *xd = (const double *)x, *d = pc ? (pc_blocks ? nullptr : pc->d_fdiag) : s->d_diag;
     CsVecs V = {};
-    V.r = s->d_vec; V.p = s->d_vec + ld; V.v = s->d_vec + 2 * ld; V.s = s->d_vec + 3 * ld; V.y = s->d_vec + 4 * ld; V.d = const_cast<double *>(d);
+    V.r = s->vec(0); V.p = s->vec(1); V.v = s->vec(2); V.s = s->vec(3); V.y = s->vec(4); V.d = const_cast<double *>(d);
     const CsGm G = gm_view(s->d_gm, (size_t)N, s->m);
     const int *words = S.d_words;
     const auto run = [&]() -> int {
         const double *fin = nullptr;
         bool own = false;
         if (!y0) {
-            const int rb = jf_base(s, f, fctx, xd, (const double *)f_in, &fin, &own);
+            const int rb = s->base(f, fctx, xd, (const double *)f_in, kJfBaseSlot, &fin, &own);
             if (rb != FD_OK) return rb;
         }
         FD_HIP_CHECK(hipMemsetAsync(S.d_words, 0, sizeof(int) * W_NWORDS, st));
@@ -477,7 +398,7 @@ int fd_jfnk_solve_from_async(fd_jfnk_solver *s, double alpha, double beta, fd_f_
                     return FD_OK;
                 }
             }
-            const int rb = jf_base(s, f, fctx, xd, (const double *)f_in, &fin, &own);
+            const int rb = s->base(f, fctx, xd, (const double *)f_in, kJfBaseSlot, &fin, &own);
             if (rb != FD_OK) return rb;
             const int ro = jf_operator(s, alpha, beta, f, fctx, xd, fin, own, (const double *)y0, V.v, false, words, 4);
             if (ro != FD_OK) return ro;

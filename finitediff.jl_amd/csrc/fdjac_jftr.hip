@@ -2,19 +2,19 @@
 //     min g.y + 1/2 y.B y   subject to   ||y||_W <= Delta,     B = lambda I + beta J(x),
 // J(x) v the finite-difference JVP of fdjac_jvp.hip for the caller's f! (the gradient) at x -- no pattern, no colouring, no stored H.
 // W = I or diag(m) with the caller's m > 0, which also preconditions.  A piece of fdjac_csctr.hip (included at its end, Float64 only):
-// CscSolveState, the words, the TR_* scalars, W_EXIT, k_tr_update, k_tr_p and k_tr_final are that file's, unchanged; the JVP's launches
-// are jvp_enqueue's, entered through JvpHooks (fdjac_internal.h) as fdjac_jfnk.hip enters them.  tests/jftr_model.py composes the
-// existing models of all of it and the GPU tests compare bits.
+// CscSolveState, the words, the TR_* scalars, W_EXIT, tr_start_body, tr_decide, k_tr_update, k_tr_p and k_tr_final are that file's; the
+// handle's scaffold and the way into jvp_enqueue (JvpHooks) are MfHandle's (fdjac_mf_common.h), shared with fdjac_jfnk.hip.
+// tests/jftr_model.py composes the existing models of all of it and the GPU tests compare bits.
 //
 // THE OPERATOR.  q is what fd_jvp_async gives for (x, v) with the consumer's steps and fdtype, on whichever route jvp_enqueue takes;
 // then w_e = lambda v_e + beta q_e, two multiplications and one addition.  k_jt_close stands where k_jvp_diff stood: the quotient as
 // k_jvp_diff forms it, the combination, and -- inside a step -- kappa = p.q as a vector-kernel dot (tiles of kCsVecTile, thread t adds
-// t, t + 256, t + 512, t + 768, cs_finish<1>), whose last-arriving workgroup takes k_tr_rows<1>'s decision word for word.
+// t, t + 256, t + 512, t + 768, cs_finish<1>), whose last-arriving workgroup takes k_tr_rows<1>'s decision (tr_decide).
 // THE DIRECTION.  Above kSmallN k_jt_p<PAIRED> computes p = -z + beta_k p and, in the same traversal, leaves the partial sums of
-// dot(x, p) on k_dot_partial's grid and in its per-thread order (the loop, the shuffle tree and the red[] sum of k_jf_open), so that the
+// dot(x, p) on k_dot_partial's grid and in its order (fdjac_dotx.h: one traversal, one tail), so that the
 // JVP that follows skips its dot launch and the operator stays bit-equal to fd_jvp_async on (x, p).  PAIRED is jvp_enqueue's rule on x
 // (p is the consumer's own and always starts on a pair).  pi_pp, pi_yp, pi_yy = sum (w p) p, sum (w y) p, sum (w y) y are formed in
-// THAT traversal too: per thread in its element order, per workgroup by the same tree and red[] sum, and the last-arriving workgroup
+// THAT traversal too: per thread in its element order, per workgroup by the same tail, and the last-arriving workgroup
 // (an integer ticket) adds the workgroups' sums IN ASCENDING WORKGROUP INDEX from +0.0.  THIS ORDER DIFFERS FROM k_tr_p's (tiles of
 // kCsVecTile, cs_finish<3>), so the three scalars -- and what follows from them -- differ in the last bits between the two routes.
 // Up to kSmallN (or with the small route off and the fusion switched off): k_tr_p, then the JVP's own dot (k_jvp_small / k_dot_partial).
@@ -23,57 +23,28 @@
 // policy keeps the iterate, pred = -1/2 sum y (g + r).  After `done` the caller's f! is still launched by the steps already enqueued:
 // what it writes is scratch that nothing reads.  Nothing is contracted into an FMA, no floating-point atomics, no grid-wide barrier.
 #pragma once
+#include "fdjac_mf_common.h"
 
-struct fd_jftr {
-    fd_ctx *ctx = nullptr;
-    int64_t N = 0, ld = 0;             // ld: N rounded up to 32 (every vector of d_vec starts on a pair)
-    int fdtype = FD_FORWARD;
-    fdjac::CscSolveState S;
-    fd_jvp_plan *jp = nullptr;
-    double *d_vec = nullptr;           // r | q | y | p | z | m | fx: ld doubles each
+struct fd_jftr : fdjac::MfHandle {             // d_vec: r | q | y | p | z | m | fx; d_diag: the caller's m, or NULL (W = I)
     unsigned long long *d_napp = nullptr;      // the products a step has used, counted by k_jt_close's deciding thread
-    const double *d_diag = nullptr;    // the caller's m, or NULL (W = I)
-    double relstep = -1.0, absstep = -1.0, dir = 1.0;
-    int64_t applies = 0, base_evaluations = 0;      // fd_jftr_apply_async calls; launches of f! for f(x)
-    bool fuse_p = true;                // k_jt_p above kSmallN (FDJAC_JFTR_FUSE=0: k_tr_p and the JVP's own dot)
+    int64_t applies = 0;                       // fd_jftr_apply_async calls
+    bool fuse_p = true;                        // k_jt_p above kSmallN (FDJAC_JFTR_FUSE=0: k_tr_p and the JVP's own dot)
+    ~fd_jftr() { if (d_napp) (void)hipFree(d_napp); }
 };
 
 namespace fdjac {
 
-// the start of a step: k_tr_start with the caller's m in place of the pattern's diagonal, or 1; an m_j <= 0 or not finite is a breakdown
+// the start of a step: tr_start_body with the caller's m, or 1; an m_j <= 0 or not finite is a breakdown
 __global__ void __launch_bounds__(kBlock) k_jt_start(int N, const double *__restrict__ d, const double *__restrict__ g, TrVecs V, double rtol,
                                                      double *scal, int *words, double *part)
 {
     __shared__ double s_w[kBlock / 64];
-    const int i0 = blockIdx.x * kCsVecTile + threadIdx.x;
-    double mine[3] = {0.0, 0.0, 0.0}, tot[3];
-    bool bad = false;
-#pragma unroll
-    for (int k = 0; k < kCsVecTile / kBlock; ++k) {
-        const int i = i0 + k * kBlock;
-        if (i >= N) continue;
-        double m = 1.0;
-        if (d) {
-            m = d[i];
-            bad = bad || !(m > 0.0 && m < __builtin_huge_val());
-        }
-        const double r = g[i];
-        const double z = r / m;
-        const double p = -z;
-        V.m[i] = m; V.r[i] = r; V.z[i] = z; V.p[i] = p; V.y[i] = 0.0;
-        mine[0] += r * z; mine[1] += r * r; mine[2] += (m * p) * p;
-    }
-    if (bad) atomicOr(words + W_FLAGS, 2);
-    if (cs_finish<3>(mine, part, words, tot, s_w) && threadIdx.x == 0) {
-        scal[TR_GAMMA] = tot[0]; scal[TR_PPP] = tot[2]; scal[TR_PYP] = 0.0; scal[TR_PYY] = 0.0; scal[TR_ALPHA] = 0.0; scal[TR_BETA] = 0.0;
-        scal[TR_RHO] = tot[1]; scal[TR_RHO0] = tot[1];
-        scal[TR_TOL2] = (rtol * rtol) * tot[1];
-        int done = 0;
-        if (tot[1] == 0.0) done = 1;                                             // g = 0: y = 0, no iteration
-        else if (cs_word(words, W_FLAGS) & 2) done = 1;                          // an m_j that is not positive and finite
-        else if (cs_not_finite(tot[0])) { atomicOr(words + W_FLAGS, 2); done = 1; }   // gamma
-        if (done) __hip_atomic_store(words + W_DONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    tr_start_body(N, g, V, rtol, scal, words, part, s_w, [&](int i, bool &bad) {
+        if (!d) return 1.0;
+        const double m = d[i];
+        bad = bad || !(m > 0.0 && m < __builtin_huge_val());
+        return m;
+    });
 }
 
 // The close hook.  q_i = lambda p_i + beta ((a_i - b_i) / e), e = eps[0] or 2 eps[0] exactly as k_jvp_diff forms it; b == NULL: a holds
@@ -102,35 +73,14 @@ __global__ void __launch_bounds__(kBlock) k_jt_close(const double *a, const doub
     if (!STEP) return;
     if (cs_finish<1>(mine, part, words, tot, s_w) && threadIdx.x == 0) {
         *napp = *napp + 1;
-        const double kappa = tot[0];
-        const double ppp = scal[TR_PPP], pyp = scal[TR_PYP], pyy = scal[TR_PYY];
-        const double d = delta2 - pyy;
-        const double tau = d / (pyp + __dsqrt_rn(pyp * pyp + ppp * d));      // the root without cancellation (pi_yp >= 0)
-        if (cs_not_finite(kappa)) {
-            cs_breakdown(words);
-        } else if (kappa <= 0.0) {
-            if (cs_not_finite(delta2)) {          // negative curvature and no boundary to follow it to
-                words[W_EXIT] = 3;
-                cs_breakdown(words);
-            } else {
-                words[W_EXIT] = 2;
-                scal[TR_ALPHA] = tau;
-            }
-        } else {
-            const double al = scal[TR_GAMMA] / kappa;
-            if (pyy + 2.0 * al * pyp + al * al * ppp >= delta2) {
-                words[W_EXIT] = 1;
-                scal[TR_ALPHA] = tau;
-            } else {
-                scal[TR_ALPHA] = al;
-            }
-        }
+        tr_decide(tot[0], delta2, scal, words);
     }
 }
 
-// p = -z + beta_k p on k_dot_partial<PAIRED>'s grid: this workgroup's sum of x_i p_i in that kernel's order goes to partial[] (what
-// k_jvp_eps reads), and its sums of (w p) p, (w y) p, (w y) y -- the same traversal, the same tree -- to part[d * gridDim.x + block];
-// the last-arriving workgroup adds those in ascending workgroup index.  z, p, y and w are the consumer's own (on a pair).
+// p = -z + beta_k p on k_dot_partial<PAIRED>'s grid: this workgroup's sum of x_i p_i in that kernel's order (dotx_for_each, dotx_finish)
+// goes to partial[] (what k_jvp_eps reads), and its sums of (w p) p, (w y) p, (w y) y -- the same traversal, the same tail -- to
+// part[d * gridDim.x + block]; the last-arriving workgroup adds those in ascending workgroup index.  z, p, y and w are the consumer's own
+// (on a pair).
 template <bool PAIRED>
 __global__ void __launch_bounds__(kBlock) k_jt_p(const double *__restrict__ x, int64_t n, TrVecs V, double *__restrict__ partial, double *scal,
                                                  int *words, double *part)
@@ -148,10 +98,8 @@ __global__ void __launch_bounds__(kBlock) k_jt_p(const double *__restrict__ x, i
         acc[1] += (wi * pn) * pn; acc[2] += (wi * yi) * pn; acc[3] += (wi * yi) * yi;
         return pn;
     };
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    if (PAIRED) {
-        const int64_t n2 = n >> 1;
-        for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n2; i += stride) {
+    dotx_for_each<PAIRED>(n,
+        [&](int64_t i) {
             const d2_t xv = reinterpret_cast<const d2_t *>(x)[i];
             const d2_t zv = reinterpret_cast<const d2_t *>(V.z)[i], pv = reinterpret_cast<const d2_t *>(V.p)[i];
             const d2_t wv = reinterpret_cast<const d2_t *>(V.m)[i], yv = reinterpret_cast<const d2_t *>(V.y)[i];
@@ -159,26 +107,13 @@ __global__ void __launch_bounds__(kBlock) k_jt_p(const double *__restrict__ x, i
             pn.x = one(xv.x, zv.x, pv.x, wv.x, yv.x);
             pn.y = one(xv.y, zv.y, pv.y, wv.y, yv.y);
             reinterpret_cast<d2_t *>(V.p)[i] = pn;
-        }
-        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) V.p[n - 1] = one(x[n - 1], V.z[n - 1], V.p[n - 1], V.m[n - 1], V.y[n - 1]);
-    } else {
-        for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) V.p[i] = one(x[i], V.z[i], V.p[i], V.m[i], V.y[i]);
-    }
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) acc[d] += __shfl_down(acc[d], off, 64);
-        if ((threadIdx.x & 63) == 0) red[d][threadIdx.x >> 6] = acc[d];
-    }
-    __syncthreads();
+        },
+        [&](int64_t i) { V.p[i] = one(x[i], V.z[i], V.p[i], V.m[i], V.y[i]); });
+    dotx_finish<4>(acc, red);
     const int nb = gridDim.x;
     if (threadIdx.x == 0) {
-        for (int d = 0; d < 4; ++d) {
-            double t = 0.0;
-            for (int w = 0; w < kBlock / 64; ++w) t += red[d][w];
-            if (d == 0) partial[blockIdx.x] = t;
-            else part[(size_t)(d - 1) * nb + blockIdx.x] = t;
-        }
+        partial[blockIdx.x] = acc[0];
+        for (int d = 1; d < 4; ++d) part[(size_t)(d - 1) * nb + blockIdx.x] = acc[d];
         __threadfence();
         const int old = __hip_atomic_fetch_add(words + W_TICKET, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
         s_last = old == nb - 1;
@@ -231,82 +166,29 @@ static int jt_operator(fd_jftr *s, double lambda, double beta, double delta2, fd
                        bool own_base, const double *p, double *q, bool have_partials, bool step)
 {
     JtOp op = {s, lambda, beta, delta2, p, q, step};
-    JvpHooks hk = {have_partials, own_base, &op, jt_close};
-    return jvp_enqueue_hooked(s->jp, f, fctx, x, p, fin, s->relstep, s->absstep, s->dir, q, &hk);
+    return s->enqueue(f, fctx, x, p, fin, own_base, q, have_partials, &op, jt_close);
 }
-// f(x) once per call in the forward arm without f_in: one launch of f!
-static int jt_base(fd_jftr *s, fd_f_launch f, void *fctx, const double *x, const double *f_in, const double **fin, bool *own)
-{
-    *fin = nullptr; *own = false;
-    if (s->fdtype != FD_FORWARD) return FD_OK;
-    if (f_in) { *fin = f_in; return FD_OK; }
-    double *fx = s->d_vec + 6 * s->ld;
-    const int rc = f(fctx, fx, x, 1, s->N, s->ld, 0, s->N, 0, (void *)s->ctx->stream);
-    FD_REQUIRE(rc == 0, FD_ERR_CALLBACK, "f! launcher returned %d", rc);
-    s->base_evaluations += 1;
-    *fin = fx; *own = true;
-    return FD_OK;
-}
-static TrVecs jt_vecs(const fd_jftr *s)
-{
-    const size_t ld = (size_t)s->ld;
-    return TrVecs{s->d_vec, s->d_vec + ld, s->d_vec + 2 * ld, s->d_vec + 3 * ld, s->d_vec + 4 * ld, s->d_vec + 5 * ld};
-}
+constexpr int kJtBaseSlot = 6;      // d_vec: r | q | y | p | z | m | fx
+static TrVecs jt_vecs(const fd_jftr *s) { return TrVecs{s->vec(0), s->vec(1), s->vec(2), s->vec(3), s->vec(4), s->vec(5)}; }
 static bool jt_beta_ok(double beta) { return beta != 0.0 && std::fabs(beta) < HUGE_VAL; }      // (a NaN fails the comparison)
 
 }  // namespace fdjac
 
 int fd_jftr_create(fd_ctx *ctx, int64_t N, int fdtype, fd_jftr **out)
 {
-    // (every range check stands before the first use of ctx: tests/test_jftr_model_cpu.py sends them a context that is never dereferenced)
-    FD_REQUIRE(ctx && out, FD_ERR_ARG, "NULL argument");
-    *out = nullptr;
-    FD_REQUIRE(N >= 1 && N <= (int64_t)0x7FFFFFFF - kCsVecTile, FD_ERR_SHAPE, "N = %lld (1 .. 2^31 - 1025)", (long long)N);
-    if (fdtype != FD_FORWARD && fdtype != FD_CENTRAL) {
-        set_error("finite_difference_jvp doesn't support :complex-mode finite diff");
-        return FD_ERR_UNSUPPORTED;
-    }
-    FD_HIP_CHECK(hipSetDevice(ctx->device));
-    fd_jftr *s = new (std::nothrow) fd_jftr();
-    FD_REQUIRE(s != nullptr, FD_ERR_NOMEM, "out of host memory");
-    s->ctx = ctx; s->N = N; s->ld = (N + 31) / 32 * 32; s->fdtype = fdtype;
-    { const char *e = test_switch("FDJAC_JFTR_FUSE"); s->fuse_p = !(e && *e && atoi(e) == 0); }
-    const auto build = [&]() -> int {
+    return csc_handle_create(out, [&](fd_jftr *s) -> int {
         const char *who = "fd_jftr_create";
-        const int rc = fd_jvp_plan_create(ctx, N, N, fdtype, &s->jp);
+        // (the partial sums: 3 dots on at most ceil(N / 256) workgroups -- k_jt_p's grid, the JVP plan's nparts, is no larger)
+        const int rc = s->init(ctx, who, N, fdtype, kJtBaseSlot + 1, TR_NSCAL, 3 * (int64_t)cs_tiles(N, kBlock));
         if (rc != FD_OK) return rc;
-        CSC_TRY(who, hipMalloc((void **)&s->d_vec, sizeof(double) * 7 * (size_t)s->ld));
+        { const char *e = test_switch("FDJAC_JFTR_FUSE"); s->fuse_p = !(e && *e && atoi(e) == 0); }
         CSC_TRY(who, hipMalloc((void **)&s->d_napp, sizeof(unsigned long long)));
         CSC_TRY(who, hipMemsetAsync(s->d_napp, 0, sizeof(unsigned long long), ctx->stream));
-        // (the partial sums: 3 dots on at most ceil(N / 256) workgroups -- k_jt_p's grid, the JVP plan's nparts, is no larger)
-        return s->S.create(who, ctx->stream, TR_NSCAL, 3 * (int64_t)cs_tiles(N, kBlock));
-    };
-    const int rc = build();
-    if (rc != FD_OK) {
-        (void)hipStreamSynchronize(ctx->stream);
-        s->S.free();
-        if (s->jp) (void)fd_jvp_plan_destroy(s->jp);
-        if (s->d_vec) (void)hipFree(s->d_vec);
-        if (s->d_napp) (void)hipFree(s->d_napp);
-        delete s;
-        return rc;
-    }
-    *out = s;
-    return FD_OK;
+        return FD_OK;
+    });
 }
 
-int fd_jftr_destroy(fd_jftr *s)
-{
-    if (!s) return FD_OK;
-    (void)hipSetDevice(s->ctx->device);
-    (void)hipStreamSynchronize(s->ctx->stream);
-    s->S.free();
-    (void)fd_jvp_plan_destroy(s->jp);
-    (void)hipFree(s->d_vec);
-    (void)hipFree(s->d_napp);
-    delete s;
-    return FD_OK;
-}
+int fd_jftr_destroy(fd_jftr *s) { return csc_handle_destroy(s); }
 
 int fd_jftr_set_options(fd_jftr *s, double rtol, int max_iterations)
 {
@@ -323,16 +205,13 @@ int fd_jftr_set_policy(fd_jftr *s, int keep_unconverged)
 int fd_jftr_set_steps(fd_jftr *s, double relstep, double absstep, double dir)
 {
     FD_REQUIRE(s != nullptr, FD_ERR_ARG, "tr is NULL");
-    s->relstep = relstep; s->absstep = absstep; s->dir = dir;
-    return FD_OK;
+    return s->set_steps(relstep, absstep, dir);
 }
 
 int fd_jftr_set_lazy_f(fd_jftr *s, fd_f_launch_lazy_jvp lazy, int caps)
 {
     FD_REQUIRE(s != nullptr, FD_ERR_ARG, "tr is NULL");
-    FD_REQUIRE(lazy != nullptr || caps == 0, FD_ERR_ARG, "no lazy launcher installed");
-    const int rc = fd_jvp_plan_set_lazy_f(s->jp, lazy);
-    return rc != FD_OK ? rc : fd_jvp_plan_set_lazy_caps(s->jp, caps);
+    return s->set_lazy(lazy, caps);
 }
 
 int fd_jftr_set_diagonal(fd_jftr *s, const void *m_dev)
@@ -351,7 +230,7 @@ int fd_jftr_apply_async(fd_jftr *s, double lambda, double beta, fd_f_launch f, v
     FD_HIP_CHECK(hipSetDevice(s->ctx->device));
     const double *fin;
     bool own;
-    int rc = jt_base(s, f, fctx, (const double *)x, (const double *)f_in, &fin, &own);
+    int rc = s->base(f, fctx, (const double *)x, (const double *)f_in, kJtBaseSlot, &fin, &own);
     if (rc == FD_OK) {
         s->applies += 1;
         rc = jt_operator(s, lambda, beta, 0.0, f, fctx, (const double *)x, fin, own, (const double *)v, (double *)w, false, false);
@@ -381,7 +260,7 @@ int fd_jftr_step_async(fd_jftr *s, double lambda, double beta, double radius, fd
     const auto run = [&]() -> int {
         const double *fin;
         bool own;
-        const int rb = jt_base(s, f, fctx, xd, (const double *)f_in, &fin, &own);
+        const int rb = s->base(f, fctx, xd, (const double *)f_in, kJtBaseSlot, &fin, &own);
         if (rb != FD_OK) return rb;
         FD_HIP_CHECK(hipMemsetAsync(S.d_words, 0, sizeof(int) * W_NWORDS, st));
         hipLaunchKernelGGL(k_jt_start, dim3(gv), dim3(kBlock), 0, st, N, s->d_diag, (const double *)g, V, S.rtol, S.d_scal, S.d_words, S.d_part);

@@ -10,63 +10,43 @@
 #include <new>
 
 #include "fdjac_internal.h"
+#include "fdjac_dotx.h"
 
 namespace fdjac {
 
 int balanced_grid(int64_t tiles, int64_t cap);
 
-__device__ __forceinline__ double wave_sum_j(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
 typedef r2_t d2j_t;
 
 // VEC: x and v are 16-B aligned -> one 16-B load per array per lane (2 elements); else scalar.  Each variant is
-// deterministic (fixed per-thread order, fixed shuffle tree, partials reduced in fixed order by k_jvp_eps).
+// deterministic (fixed per-thread order, fixed shuffle tree, partials reduced in fixed order by k_jvp_eps): fdjac_dotx.h.
 template <bool VEC>
 __global__ void __launch_bounds__(kBlock)
 k_dot_partial(const real_t *__restrict__ x, const real_t *__restrict__ v, int64_t n, double *__restrict__ partial)
 {
-    double acc = 0.0;   // Float64 accumulation for either element type
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    if (VEC) {
-        const int64_t n2 = n >> 1;
-        for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n2; i += stride) {
+    double acc[1] = {0.0};   // Float64 accumulation for either element type
+    dotx_for_each<VEC>(n,
+        [&](int64_t i) {
             const d2j_t a = reinterpret_cast<const d2j_t *>(x)[i], b = reinterpret_cast<const d2j_t *>(v)[i];
-            acc += (double)a.x * (double)b.x;
-            acc += (double)a.y * (double)b.y;
-        }
-        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) acc += (double)x[n - 1] * (double)v[n - 1];
-    } else {
-        for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) acc += (double)x[i] * (double)v[i];
-    }
-    __shared__ double red[kBlock / 64];
-    acc = wave_sum_j(acc);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int w = 0; w < kBlock / 64; ++w) t += red[w];
-        partial[blockIdx.x] = t;
-    }
+            acc[0] += (double)a.x * (double)b.x;
+            acc[0] += (double)a.y * (double)b.y;
+        },
+        [&](int64_t i) { acc[0] += (double)x[i] * (double)v[i]; });
+    __shared__ double red[1][kBlock / 64];
+    dotx_finish<1>(acc, red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = acc[0];
 }
 
 __global__ void __launch_bounds__(kBlock)
 k_jvp_eps(const double *__restrict__ partial, int nparts, double relstep, double absstep, double dir, int is_forward,
           real_t *__restrict__ eps)
 {
-    double acc = 0.0;
-    for (int k = threadIdx.x; k < nparts; k += kBlock) acc += partial[k];
-    __shared__ double red[kBlock / 64];
-    acc = wave_sum_j(acc);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
+    double acc[1] = {0.0};
+    for (int k = threadIdx.x; k < nparts; k += kBlock) acc[0] += partial[k];
+    __shared__ double red[1][kBlock / 64];
+    dotx_finish<1>(acc, red);
     if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int w = 0; w < kBlock / 64; ++w) t += red[w];
+        const double t = acc[0];
         const real_t tmp = sqrt(fabs((real_t)t));      // the dot product in Float64, the step rule in the element type
         const real_t a = (real_t)relstep * fabs(tmp);
         real_t e = eps_max<real_t>(a, (real_t)absstep);   // src/epsilons.jl:26-29,50-53 (NaN propagates)
@@ -119,16 +99,13 @@ __global__ void __launch_bounds__(kJvpSmallBlock)
 k_jvp_small(const real_t *__restrict__ x, const real_t *__restrict__ v, int64_t n, double relstep, double absstep,
             double dir, int central, int base_row, real_t *__restrict__ eps, real_t *__restrict__ X, int64_t ld)
 {
-    __shared__ double red[kJvpSmallBlock / 64];
+    __shared__ double red[1][kJvpSmallBlock / 64];
     __shared__ real_t s_e;
-    double acc = 0.0;
-    for (int64_t i = threadIdx.x; i < n; i += kJvpSmallBlock) acc += (double)x[i] * (double)v[i];
-    acc = wave_sum_j(acc);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
+    double acc[1] = {0.0};
+    for (int64_t i = threadIdx.x; i < n; i += kJvpSmallBlock) acc[0] += (double)x[i] * (double)v[i];
+    dotx_finish<1, kJvpSmallBlock>(acc, red);
     if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int w = 0; w < kJvpSmallBlock / 64; ++w) t += red[w];
+        const double t = acc[0];
         const real_t tmp = sqrt(fabs((real_t)t));
         const real_t a = (real_t)relstep * fabs(tmp);
         real_t e = eps_max<real_t>(a, (real_t)absstep);   // src/epsilons.jl:26-29,50-53 (NaN propagates)
@@ -220,6 +197,40 @@ int fd_jvp_plan_destroy(fd_jvp_plan *p)
     return FD_OK;
 }
 
+// The launches that jvp_enqueue's routes share.  The step size of (x, v): the dot's partial sums, unless the caller's kernel has left
+// them in d_partial (hk->have_partials), then k_jvp_eps.  vx: x and v are on a pair.
+static void launch_dot_eps(fd_jvp_plan *p, const real_t *xd, const real_t *vd, bool vx, const JvpHooks *hk, double relstep, double absstep,
+                           double dir)
+{
+    hipStream_t s = p->ctx->stream;
+    if (hk && hk->have_partials) {}
+    else if (vx) hipLaunchKernelGGL(k_dot_partial<true>, dim3(p->nparts), dim3(kBlock), 0, s, xd, vd, p->N, p->d_partial);
+    else hipLaunchKernelGGL(k_dot_partial<false>, dim3(p->nparts), dim3(kBlock), 0, s, xd, vd, p->N, p->d_partial);
+    hipLaunchKernelGGL(k_jvp_eps, dim3(1), dim3(kBlock), 0, s, p->d_partial, p->nparts, relstep, absstep, dir,
+                       p->fdtype == FD_CENTRAL ? 0 : 1, p->d_eps);
+}
+// the perturbed point(s) into d_X, from the step on the device
+static void launch_points(fd_jvp_plan *p, const real_t *xd, const real_t *vd, bool vx)
+{
+    hipStream_t s = p->ctx->stream;
+    const int central = p->fdtype == FD_CENTRAL;
+    if (vx) hipLaunchKernelGGL(k_jvp_points<true>, dim3((unsigned)((p->N + 2 * kBlock - 1) / (2 * kBlock))), dim3(kBlock), 0, s,
+                               xd, vd, p->d_eps, central, p->N, p->d_X, p->ldx);
+    else hipLaunchKernelGGL(k_jvp_points<false>, dim3(balanced_grid((p->N + kBlock - 1) / kBlock, (int64_t)p->ctx->num_cus * 8)), dim3(kBlock), 0, s,
+                            xd, vd, p->d_eps, central, p->N, p->d_X, p->ldx);
+}
+// out = (a - b) / eps (central: 2 eps), a pair per thread when all three are on one
+static void launch_diff(fd_jvp_plan *p, const real_t *a, const real_t *b, real_t *out)
+{
+    hipStream_t s = p->ctx->stream;
+    const int central = p->fdtype == FD_CENTRAL;
+    if (((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)out)) & kPairMask) == 0)
+        hipLaunchKernelGGL(k_jvp_diff<true>, dim3((unsigned)((p->M + 2 * kBlock - 1) / (2 * kBlock))), dim3(kBlock), 0, s, a, b,
+                           p->d_eps, central, p->M, out);
+    else hipLaunchKernelGGL(k_jvp_diff<false>, dim3(balanced_grid((p->M + kBlock - 1) / kBlock, (int64_t)p->ctx->num_cus * 8)), dim3(kBlock), 0, s,
+                            a, b, p->d_eps, central, p->M, out);
+}
+
 // hk (fdjac_internal.h, JvpHooks): a caller inside the library that has the dot product's partial sums already and closes with a kernel
 // of its own; NULL (fd_jvp, fd_jvp_async): every launch below as it always was
 static int jvp_enqueue(fd_jvp_plan *p, fd_f_launch f, void *fctx, const real_t *xd, const real_t *vd, const real_t *fin,
@@ -232,8 +243,6 @@ static int jvp_enqueue(fd_jvp_plan *p, fd_f_launch f, void *fctx, const real_t *
         relstep = central ? (double)std::cbrt(e) : (double)std::sqrt(e);
     }
     if (absstep < 0) absstep = relstep;
-    const int g = balanced_grid((p->N + kBlock - 1) / kBlock, (int64_t)p->ctx->num_cus * 8);
-    const int gm = balanced_grid((p->M + kBlock - 1) / kBlock, (int64_t)p->ctx->num_cus * 8);
     const bool small = p->small_ok && p->N <= kSmallN;   // (FDJAC_SMALL is read at plan creation)
     const bool base_in_batch = small && !central && !fin;
     const bool vx = ((((uintptr_t)xd) | ((uintptr_t)vd)) & kPairMask) == 0;
@@ -241,11 +250,7 @@ static int jvp_enqueue(fd_jvp_plan *p, fd_f_launch f, void *fctx, const real_t *
     // step as usual, then ONE f! launch that perturbs while loading -- the points pass and, in the forward arm, the
     // separate f(x) launch disappear.  A launcher that declines falls through to the materialised points.
     if (!small && p->lazy_fn) {
-        if (hk && hk->have_partials) {}      // (the caller's kernel has left them in d_partial)
-        else if (vx) hipLaunchKernelGGL(k_dot_partial<true>, dim3(p->nparts), dim3(kBlock), 0, s, xd, vd, p->N, p->d_partial);
-        else hipLaunchKernelGGL(k_dot_partial<false>, dim3(p->nparts), dim3(kBlock), 0, s, xd, vd, p->N, p->d_partial);
-        hipLaunchKernelGGL(k_jvp_eps, dim3(1), dim3(kBlock), 0, s, p->d_partial, p->nparts, relstep, absstep, dir,
-                           central ? 0 : 1, p->d_eps);
+        launch_dot_eps(p, xd, vd, vx, hk, relstep, absstep, dir);
         FD_HIP_CHECK(hipGetLastError());
         fd_lazy_jvp_points lp = {};
         lp.x = xd;
@@ -266,29 +271,18 @@ static int jvp_enqueue(fd_jvp_plan *p, fd_f_launch f, void *fctx, const real_t *
             const real_t *la = central ? p->d_FX + p->ldf : p->d_FX;
             const real_t *lb = central ? p->d_FX : (fin ? fin : p->d_fx);
             if (hk) return hk->close(hk->user, la, lb, p->d_eps, central);
-            if (((((uintptr_t)la) | ((uintptr_t)lb) | ((uintptr_t)out)) & kPairMask) == 0)
-                hipLaunchKernelGGL(k_jvp_diff<true>, dim3((unsigned)((p->M + 2 * kBlock - 1) / (2 * kBlock))), dim3(kBlock), 0, s,
-                                   la, lb, p->d_eps, central, p->M, out);
-            else hipLaunchKernelGGL(k_jvp_diff<false>, dim3(gm), dim3(kBlock), 0, s, la, lb, p->d_eps, central, p->M, out);
+            launch_diff(p, la, lb, out);
             FD_HIP_CHECK(hipGetLastError());
             return FD_OK;
         }
         // declined: the step is already on the device, only the points remain to be written
-        if (vx) hipLaunchKernelGGL(k_jvp_points<true>, dim3((unsigned)((p->N + 2 * kBlock - 1) / (2 * kBlock))), dim3(kBlock), 0, s,
-                                   xd, vd, p->d_eps, central, p->N, p->d_X, p->ldx);
-        else hipLaunchKernelGGL(k_jvp_points<false>, dim3(g), dim3(kBlock), 0, s, xd, vd, p->d_eps, central, p->N, p->d_X, p->ldx);
+        launch_points(p, xd, vd, vx);
     } else if (small) {
         hipLaunchKernelGGL(k_jvp_small, dim3(1), dim3(kJvpSmallBlock), 0, s, xd, vd, p->N, relstep, absstep, dir, central,
                            base_in_batch ? 1 : -1, p->d_eps, p->d_X, p->ldx);
     } else {
-        if (hk && hk->have_partials) {}      // (the caller's kernel has left them in d_partial)
-        else if (vx) hipLaunchKernelGGL(k_dot_partial<true>, dim3(p->nparts), dim3(kBlock), 0, s, xd, vd, p->N, p->d_partial);
-        else hipLaunchKernelGGL(k_dot_partial<false>, dim3(p->nparts), dim3(kBlock), 0, s, xd, vd, p->N, p->d_partial);
-        hipLaunchKernelGGL(k_jvp_eps, dim3(1), dim3(kBlock), 0, s, p->d_partial, p->nparts, relstep, absstep, dir,
-                           central ? 0 : 1, p->d_eps);
-        if (vx) hipLaunchKernelGGL(k_jvp_points<true>, dim3((unsigned)((p->N + 2 * kBlock - 1) / (2 * kBlock))), dim3(kBlock), 0, s,
-                                   xd, vd, p->d_eps, central, p->N, p->d_X, p->ldx);
-        else hipLaunchKernelGGL(k_jvp_points<false>, dim3(g), dim3(kBlock), 0, s, xd, vd, p->d_eps, central, p->N, p->d_X, p->ldx);
+        launch_dot_eps(p, xd, vd, vx, hk, relstep, absstep, dir);
+        launch_points(p, xd, vd, vx);
     }
     FD_HIP_CHECK(hipGetLastError());
     const real_t *a, *b;
@@ -316,10 +310,7 @@ static int jvp_enqueue(fd_jvp_plan *p, fd_f_launch f, void *fctx, const real_t *
         a = p->d_FX;
     }
     if (hk) return hk->close(hk->user, a, b, p->d_eps, central);
-    if (((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)out)) & kPairMask) == 0)
-        hipLaunchKernelGGL(k_jvp_diff<true>, dim3((unsigned)((p->M + 2 * kBlock - 1) / (2 * kBlock))), dim3(kBlock), 0, s, a, b,
-                           p->d_eps, central, p->M, out);
-    else hipLaunchKernelGGL(k_jvp_diff<false>, dim3(gm), dim3(kBlock), 0, s, a, b, p->d_eps, central, p->M, out);
+    launch_diff(p, a, b, out);
     FD_HIP_CHECK(hipGetLastError());
     return FD_OK;
 }

@@ -1698,12 +1698,13 @@ class Plan:
 
 
 def _opts(fdtype, col_window=None, x_window=None, scratch_bytes=0, color_range=None, eps_contiguous=False, fingerprint=False,
-          store_csc=False, store_csc_always=False, store_rows=False):
+          store_csc=False, store_csc_always=False, store_rows=False, handover_rows=False):
+    store_rows = store_rows or handover_rows      # (FD_PLAN_HANDOVER_ROWS walks the row lists: it implies them, and the compact copy they come from)
     o = _l.PlanOpts()
     o.fdtype = _l.FDTYPES[_norm_fdtype(fdtype)]
     o.flags = ((_l.PLAN_EPS_CONTIGUOUS if eps_contiguous else 0) | (_l.PLAN_FINGERPRINT if fingerprint else 0) |
                (_l.PLAN_STORE_CSC if (store_csc or store_csc_always or store_rows) else 0) | (_l.PLAN_STORE_CSC_ALWAYS if store_csc_always else 0) |
-               (_l.PLAN_STORE_CSC_ROWS if store_rows else 0))
+               (_l.PLAN_STORE_CSC_ROWS if store_rows else 0) | (_l.PLAN_HANDOVER_ROWS if handover_rows else 0))
     if col_window is not None:
         o.col_begin, o.col_end = int(col_window[0]), int(col_window[1])
     if x_window is not None:
@@ -1720,17 +1721,23 @@ def _vp(a):
 
 def make_plan(J, sparsity, colorvec, fdtype, ctx=None, col_window=None, x_window=None, scratch_bytes=0,
               color_range=None, dtype=np.float64, eps_contiguous=False, complex_x=False, fingerprint=False, store_csc=False,
-              store_csc_always=False, store_rows=False):
+              store_csc_always=False, store_rows=False, handover_rows=False):
     """Compile (J type, sparsity, colorvec) into a device plan -- the dispatch the reference performs
     per call through `_colorediteration!` / `_use_findstructralnz` / `_use_sparseCSC_common_sparsity`
-    (src/jacobians.jl:524-535; ext/*.jl)."""
+    (src/jacobians.jl:524-535; ext/*.jl).
+
+    handover_rows (opt-in, FD_PLAN_HANDOVER_ROWS; implies store_rows and store_csc): an opaque f!'s hand-over path decompresses row by
+    row through the plan's row lists (k_decompress_rows) -- the same bits as the automatic route; plan.info(lib.INFO_HANDOVER_ROWS)
+    tells whether this plan does (it needs every column, real x and a CSC destination; any other plan keeps its route)."""
+    store_rows = store_rows or handover_rows
     ctx = ctx or Context.default()
     L = _l.typed(ctx.L, dtype)      # fd_* for Float64, fd32_* for Float32 (eltype(x) in the reference)
     fdtype = _norm_fdtype(fdtype)
     o = _opts(fdtype, col_window, x_window, scratch_bytes, color_range, eps_contiguous, fingerprint,
               (store_csc or store_csc_always or store_rows) and not complex_x and isinstance(J, SparseMatrixCSC),
               store_csc_always and not complex_x and isinstance(J, SparseMatrixCSC),
-              store_rows and not complex_x and isinstance(J, SparseMatrixCSC))
+              store_rows and not complex_x and isinstance(J, SparseMatrixCSC),
+              handover_rows and not complex_x and isinstance(J, SparseMatrixCSC))
     if complex_x:      # returntype <: Complex with forward / central differences: the library lowers it (FD_PLAN_COMPLEX_X)
         o.flags |= _l.PLAN_COMPLEX_X
     if isinstance(J, DevicePatternCSC):

@@ -114,7 +114,7 @@ struct LoweredScope {
     LoweredScope() { t_lowered_cx = true; }
     ~LoweredScope() { t_lowered_cx = false; }
 };
-constexpr int32_t kPlanKnownFlags = FD_PLAN_EPS_CONTIGUOUS | FD_PLAN_COMPLEX_X | FD_PLAN_FINGERPRINT | FD_PLAN_STORE_CSC | FD_PLAN_STORE_CSC_ALWAYS | FD_PLAN_STORE_CSC_ROWS;
+constexpr int32_t kPlanKnownFlags = FD_PLAN_EPS_CONTIGUOUS | FD_PLAN_COMPLEX_X | FD_PLAN_FINGERPRINT | FD_PLAN_STORE_CSC | FD_PLAN_STORE_CSC_ALWAYS | FD_PLAN_STORE_CSC_ROWS | FD_PLAN_HANDOVER_ROWS;
 
 static int apply_opts(fd_plan *p, const fd_plan_opts *opts)
 {
@@ -124,6 +124,9 @@ static int apply_opts(fd_plan *p, const fd_plan_opts *opts)
                "Unrecognized fdtype: valid values are Val{:forward}, Val{:central} and Val{:complex}.");
     FD_REQUIRE((opts->flags & ~kPlanKnownFlags) == 0, FD_ERR_ARG, "unknown fd_plan_opts.flags bits 0x%x (zero the struct before filling it)",
                (unsigned)(opts->flags & ~kPlanKnownFlags));
+    FD_REQUIRE(!(opts->flags & FD_PLAN_HANDOVER_ROWS) || (opts->flags & FD_PLAN_STORE_CSC_ROWS), FD_ERR_ARG,
+               "fd_plan_opts.flags bits 0x%x: FD_PLAN_HANDOVER_ROWS needs FD_PLAN_STORE_CSC_ROWS (the row-wise hand-over kernel walks the plan's row lists)",
+               (unsigned)opts->flags);
     FD_REQUIRE(!(opts->flags & FD_PLAN_COMPLEX_X), FD_ERR_UNSUPPORTED,
                "complex-valued x (FD_PLAN_COMPLEX_X) reaches this plan kind through its lowering only");
     p->fdtype = opts->fdtype;
@@ -167,6 +170,7 @@ static int apply_opts(fd_plan *p, const fd_plan_opts *opts)
     p->store_allowed = env_int("FDJAC_LAZY_STORE", 1) != 0;
     p->want_store_csc = (opts->flags & FD_PLAN_STORE_CSC) != 0;
     p->want_store_rows = (opts->flags & FD_PLAN_STORE_CSC_ROWS) != 0;
+    p->want_handover_rows = (opts->flags & FD_PLAN_HANDOVER_ROWS) != 0;
     p->store_csc_always = (opts->flags & FD_PLAN_STORE_CSC_ALWAYS) != 0;   // a compact device copy of the pattern for column-centric storing launches
     p->own_c0 = 0;
     p->own_c1 = -1;
@@ -429,7 +433,7 @@ int fd_plan_destroy(fd_plan *p)
     if (p->ctx->check_stream && p->d_fpx) (void)hipStreamSynchronize(p->ctx->check_stream);      // (a deferred check of this plan may still be reading d_fpx)
     void *ptrs[] = {p->d_color, p->d_rowval, p->d_nzcolor, p->d_dest, p->d_spos, p->d_wtiles, p->d_wcode, p->d_w2desc, p->d_cr_rlo, p->d_cr_cnt, p->d_cr_off,
                     p->d_perm, p->d_cptr, p->d_X, p->d_FX, p->d_fx, p->d_eps, p->d_partial, p->d_gsum, p->d_tick, p->d_fpx, p->d_xstage,
-                    p->d_finstage, p->d_outstage[0], p->d_outstage[1], p->d_outstage[2], p->d_zero_own, p->d_eps2, p->d_tile_order, p->d_fxwin, p->d_fp, p->d_sc_colptr, p->d_sc_rowval, p->d_sc_note, p->d_sr_ptr, p->d_sr_col, p->d_sr_slot, p->d_sr_order, p->d_sr_tile, p->d_se_col, p->d_se_slot, p->d_se_info, p->d_split, p->d_bbb_off, p->d_bbb_blk, p->d_bbb_start, p->d_bbb_stride};
+                    p->d_finstage, p->d_outstage[0], p->d_outstage[1], p->d_outstage[2], p->d_zero_own, p->d_eps2, p->d_tile_order, p->d_fxwin, p->d_fp, p->d_sc_colptr, p->d_sc_rowval, p->d_sc_note, p->d_sr_ptr, p->d_sr_col, p->d_sr_slot, p->d_sr_order, p->d_sr_tile, p->d_sr_color, p->d_se_col, p->d_se_slot, p->d_se_info, p->d_split, p->d_bbb_off, p->d_bbb_blk, p->d_bbb_start, p->d_bbb_stride};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     if (p->h_pstale) (void)hipHostFree(p->h_pstale);
@@ -507,6 +511,7 @@ int fd_plan_info(const fd_plan *p, int key, int64_t *value)
         *value = (p->lazy_fn && (p->lazy_caps & FD_LAZY_CAP_DIFF) && p->lazy_diff && p->fdtype != FD_COMPLEX && p->kind != K_DENSE) ? 1 : 0;
         break;
     case FD_INFO_BUILT_ON_DEVICE: *value = p->built_on_device ? 1 : 0; break;
+    case FD_INFO_HANDOVER_ROWS: *value = handover_rows_active(p) ? 1 : 0; break;
     default: set_error("unknown info key %d", key); return FD_ERR_ARG;
     }
     return FD_OK;

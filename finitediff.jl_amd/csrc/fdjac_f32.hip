@@ -3,6 +3,7 @@
 // error text, colouring and the copy probe stay with the Float64 build (their definitions are skipped here).
 #define FDJAC_F32 1
 #include "fdjac_kernels.hip"
+#include "fdjac_decompress_rows.hip"
 #include "fdjac_api.hip"
 #include "fdjac_match.hip"
 #include "fdjac_builtin_f.hip"

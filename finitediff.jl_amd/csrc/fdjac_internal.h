@@ -484,6 +484,8 @@ struct fd_plan {
     int32_t *d_sc_colptr = nullptr, *d_sc_rowval = nullptr;
     bool want_store_rows = false;                // FD_PLAN_STORE_CSC_ROWS: the same pattern by rows (fd_csc_store.row_ptr / row_col / row_slot), full column range only
     int32_t *d_sr_ptr = nullptr, *d_sr_col = nullptr, *d_sr_slot = nullptr, *d_sr_order = nullptr, *d_sr_tile = nullptr;
+    bool want_handover_rows = false;             // FD_PLAN_HANDOVER_ROWS: the hand-over decompression walks the row lists (k_decompress_rows)
+    void *d_sr_color = nullptr;                  //   ... and the entries' colours in row-list order (the plan's colour width; built only with that flag)
     int se_tile_max = 0;
     int32_t *d_se_col = nullptr, *d_se_slot = nullptr, *d_se_info = nullptr;      // the entries in the tiles' row order (fd_csc_store.ent_*), or none
     unsigned long long *d_sc_note = nullptr;     // fd_csc_store.note: four words of launcher memory about this pattern, zero at creation
@@ -627,6 +629,11 @@ static inline bool store_csc_active(const fd_plan *p)
 {
     return p->lazy_fn && (p->lazy_caps & FD_LAZY_CAP_STORE_CSC) && p->store_csc_ok && p->kind == fdjac::K_CSC &&
            (p->fdtype != FD_COMPLEX || (p->lazy_caps & FD_LAZY_CAP_STORE_CSC_COMPLEX)) && p->store_allowed;
+}
+// does the hand-over decompression of this plan run the row-wise kernel (FD_PLAN_HANDOVER_ROWS; FD_INFO_HANDOVER_ROWS)?
+static inline bool handover_rows_active(const fd_plan *p)
+{
+    return p->want_handover_rows && p->kind == fdjac::K_CSC && p->d_sr_color && p->d_sr_order && p->d_sr_tile && p->d_sr_ptr && p->d_sr_slot;
 }
 static inline bool store_active(const fd_plan *p)
 {

@@ -1513,6 +1513,8 @@ static void launch_window_m(fd_plan *p, const real_t *fx, const real_t *FXa, con
     });
 }
 
+int launch_decompress_rows(fd_plan *p, const real_t *FXa, const real_t *FXb, int c_lo, int c_hi, real_t *out, int mode);   // fdjac_decompress_rows.hip
+
 template <typename CT, int MODE>
 static int launch_decompress_tm(fd_plan *p, const real_t *fx, int c_lo, int c_hi, real_t *const *outs)
 {
@@ -1527,6 +1529,8 @@ static int launch_decompress_tm(fd_plan *p, const real_t *fx, int c_lo, int c_hi
     case K_CSC_DENSE:
     case K_COO_DENSE: {
         if (p->nnz_local == 0) break;
+        // FD_PLAN_HANDOVER_ROWS (opt-in) on a plan that keeps its pattern by rows: the row-wise kernel, ahead of the plan builder's choice
+        if (handover_rows_active(p)) return launch_decompress_rows(p, FXa, FXb, c_lo, c_hi, outs[0], MODE);
         if (p->sorted_gather && p->kind == K_CSC) {
             const bool ldsq = B <= kEpsLdsMax;
             const bool allw = (p->nchunks == 1) && !p->has_none && p->own_c0 == 0 && (p->own_c1 < 0 || p->own_c1 >= p->C);

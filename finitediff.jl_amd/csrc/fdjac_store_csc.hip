@@ -231,6 +231,16 @@ static int build_store_csc_t(fd_plan *p, const IT *colptr_dev, const IT *rowval_
                     FD_HIP_CHECK(hipMemcpy(p->d_se_info, ei.data(), sizeof(int) * ei.size(), hipMemcpyHostToDevice));
                 }
             }
+            // ... and (FD_PLAN_HANDOVER_ROWS) every entry's COLOUR in the order of row_col / row_slot, in the plan's colour width and with
+            // the list kernel's "none" (all ones): k_decompress_rows reads it beside row_slot instead of the dependent gather color[row_col[k]]
+            if (p->want_handover_rows) {
+                const size_t cb = p->color8 ? 1 : 4;
+                std::vector<unsigned char> col((size_t)ncols * cb), rcl((size_t)n * cb);
+                FD_HIP_CHECK(hipMemcpy(col.data(), (const char *)p->d_color + (size_t)p->col0 * cb, col.size(), hipMemcpyDeviceToHost));
+                for (int64_t k = 0; k < n; ++k) memcpy(rcl.data() + (size_t)k * cb, col.data() + (size_t)rc[(size_t)k] * cb, cb);
+                FD_HIP_CHECK(hipMalloc(&p->d_sr_color, rcl.size()));
+                FD_HIP_CHECK(hipMemcpy(p->d_sr_color, rcl.data(), rcl.size(), hipMemcpyHostToDevice));
+            }
             FD_HIP_CHECK(hipMalloc((void **)&p->d_sr_ptr, sizeof(int) * rp.size()));
             FD_HIP_CHECK(hipMalloc((void **)&p->d_sr_col, sizeof(int) * rc.size()));
             FD_HIP_CHECK(hipMalloc((void **)&p->d_sr_slot, sizeof(int) * rs.size()));
@@ -246,7 +256,9 @@ static int build_store_csc_t(fd_plan *p, const IT *colptr_dev, const IT *rowval_
 
 static bool store_csc_wanted(const fd_plan *p)
 {
-    return p->want_store_csc && p->kind == K_CSC && !p->cx && (p->store_csc_always || (!p->store_ok && !p->store5_ok)) && p->store_allowed && p->nnz_local > 0 &&
+    // (FD_PLAN_HANDOVER_ROWS: the row lists serve the hand-over path, which FDJAC_LAZY_STORE=0 selects -- store_csc_active still asks store_allowed)
+    return p->want_store_csc && p->kind == K_CSC && !p->cx && (p->store_csc_always || (!p->store_ok && !p->store5_ok)) &&
+           (p->store_allowed || (p->want_handover_rows && p->want_store_rows)) && p->nnz_local > 0 &&
            p->nnz_local < ((int64_t)1 << 31) && p->M < ((int64_t)1 << 31) && p->d_color != nullptr;
 }
 

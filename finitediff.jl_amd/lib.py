@@ -28,11 +28,12 @@ STAGES = ("eps", "perturb", "f", "decompress", "total", "exchange")
  INFO_ROW_END, INFO_NCHUNKS, INFO_SCRATCH_BYTES, INFO_NNZ_LOCAL, INFO_FCALLS_LAST, INFO_ENTRY_BEGIN,
  INFO_SORTED_GATHER, INFO_LINES_DIRECT_X100, INFO_LINES_SORTED_X100, INFO_WINDOW,
  INFO_WIN_OVERREAD_X100, INFO_WINDOW2D, INFO_WIN_PERIOD, INFO_COLRANGE_WG, INFO_SMALL_FUSED, _INFO_23,
- INFO_EPS_CYCLIC, INFO_EPS_NT, _INFO_26, INFO_BUILT_ON_DEVICE, _INFO_28, INFO_LAZY_DIFF, _INFO_30, INFO_BAND_DESC, INFO_LAZY_STORE, INFO_STORE_CSC, INFO_STORE_LAUNCH) = range(35)
+ INFO_EPS_CYCLIC, INFO_EPS_NT, _INFO_26, INFO_BUILT_ON_DEVICE, _INFO_28, INFO_LAZY_DIFF, _INFO_30, INFO_BAND_DESC, INFO_LAZY_STORE, INFO_STORE_CSC, INFO_STORE_LAUNCH, INFO_HANDOVER_ROWS) = range(36)
 # FD_INFO_STORE_LAUNCH: the kernel of the plan's last column-store launch (include/fdjac.h, fd_store_launch)
 STORE_LAUNCH_NONE, STORE_LAUNCH_COLS, STORE_LAUNCH_COLS_WIN, STORE_LAUNCH_ROWS, STORE_LAUNCH_ENTS, STORE_LAUNCH_FAMILY = range(6)
 LAZY_CAP_IMAG_ONLY, LAZY_CAP_ROW_WINDOW, LAZY_CAP_DIFF, LAZY_CAP_STORE, LAZY_CAP_STORE_CSC, LAZY_CAP_STORE_CSC_BASE, LAZY_CAP_STORE_CSC_COMPLEX, LAZY_CAP_FUSED_EPS, LAZY_CAP_STORE_COLRANGE = 1, 2, 4, 8, 16, 32, 64, 128, 256
 PLAN_EPS_CONTIGUOUS, PLAN_COMPLEX_X, PLAN_FINGERPRINT, PLAN_STORE_CSC, PLAN_STORE_CSC_ALWAYS, PLAN_STORE_CSC_ROWS = 1, 2, 4, 8, 16, 32
+PLAN_HANDOVER_ROWS = 64      # (with PLAN_STORE_CSC | PLAN_STORE_CSC_ROWS) opt-in: the hand-over decompression walks the row lists (INFO_HANDOVER_ROWS)
 LAZY_JVP_CAP_QUOTIENT = 1
 (F_TRIDIAG, F_TRIDIAG_NL, F_LAP5, F_CLAMP5, F_BLOCKCOUPLED, F_NONSQUARE, F_LAP5_NL, F_LAP7, F_SPARSE) = range(9)
 FAMILIES = {"tridiag": F_TRIDIAG, "tridiag_nl": F_TRIDIAG_NL, "lap5": F_LAP5, "clamp5": F_CLAMP5,

@@ -180,6 +180,15 @@ typedef struct fd_plan_opts {
                                    /* per row its entries' columns and their slots in nzval (fd_csc_store.row_ptr / row_col / row_slot, 8 bytes */
                                    /* per stored entry + 4 per row) -- for the row-wise store of SEPARABLE residuals (fd_csc_store_rows,       */
                                    /* include/fdjac_device.h; fd_f_compile_terms); fd_plan_row_lists hands the lists out                     */
+#define FD_PLAN_HANDOVER_ROWS 64      /* (with FD_PLAN_STORE_CSC | FD_PLAN_STORE_CSC_ROWS; without FD_PLAN_STORE_CSC_ROWS: FD_ERR_ARG) OPT-IN: the hand-over   */
+                                   /* path of an opaque f! decompresses ROW BY ROW through those lists (k_decompress_rows: a thread per row, the      */
+                                   /* entries' colours kept in row-list order, 1 or 4 more bytes per stored entry) instead of entry by entry in       */
+                                   /* storage order -- the same quotients of the same operands, the same bits.  Needs what the row lists need: a      */
+                                   /* plan that holds every column, real x, a CSC destination; a plan without the lists (FD_INFO_HANDOVER_ROWS = 0)    */
+                                   /* keeps its route.  The lists are then built whatever FDJAC_LAZY_STORE says.  MEASURED NO FASTER on the random   */
+                                   /* band 2e6 x 6 (2.9x the colour-sorted gather's time) and on the 1.2e6 x 1e6 random pattern (1.4 - 1.6x the list  */
+                                   /* kernel's): its scattered 8-byte stores write four times the bytes (DESIGN.md section 4.2,                     */
+                                   /* profiles/handover_rows.md).  It stays opt-in, for experiments                                                 */
 #define FD_PLAN_FINGERPRINT 4        /* record 64-bit content fingerprints of the pattern / colour arrays the plan is compiled from, so  */
                                    /* that fd_plan_matches can later tell whether the caller's arrays still hold that content        */
 
@@ -318,7 +327,8 @@ enum fd_plan_info_key {
     FD_INFO_LAZY_DIFF = 29,           /* 1 if the plan asks a FD_LAZY_CAP_DIFF launcher for differences (FDJAC_LAZY_DIFF=0: never) */
     FD_INFO_BUILT_ON_DEVICE = 27,     /* 1 if the pattern was compiled by the device plan builder */
     FD_INFO_STORE_CSC = 33,           /* number of local entries of the compact pattern copy of FD_PLAN_STORE_CSC, 0 = none */
-    FD_INFO_STORE_LAUNCH = 34         /* which kernel the plan's last column-store launch (store_kind = FD_STORE_CSC) ran: FD_STORE_LAUNCH_* below; read-only */
+    FD_INFO_STORE_LAUNCH = 34,        /* which kernel the plan's last column-store launch (store_kind = FD_STORE_CSC) ran: FD_STORE_LAUNCH_* below; read-only */
+    FD_INFO_HANDOVER_ROWS = 35        /* 1 if the plan's hand-over decompression runs the row-wise kernel (FD_PLAN_HANDOVER_ROWS and the plan keeps row lists), else 0 */
 };
 /* FD_INFO_STORE_LAUNCH: the kernel a launcher of the LIBRARY (built-in families, runtime-compiled functors) enqueued for the last batch of
    colours it stored through a fd_csc_store -- a launcher chooses silently between them (colouring verified or not, the pattern's reach,
